@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- env-steps/s of the imitation rollout hot path on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--num-envs E] [--no-contact] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--num-envs E] [--no-contact] [--dump-outputs DIR] [--full] ...
 
 With --gpus N > 1 and no torch.distributed environment the script launches itself as N ranks (python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...), one rank per GPU over RCCL; started under an external torchrun it
@@ -14,7 +14,14 @@ post: new target, obs, reward, reset); every `horizon`=32 steps the per-epoch `r
 context window) runs INSIDE the timed region, as in the reference's play_steps.  Policy inference is excluded.  Envs shard across
 ranks with no data-path collective ("scaling": "weak").
 
-One JSON line on rank 0, with
+A plain run sets up, warms up, times exactly K steps and prints one JSON line on rank 0: value = env-steps/s of those K steps,
+ms_per_step = their milliseconds per step.  --dump-outputs DIR writes what the last timed step returned to its caller (observations,
+rewards, reset / terminate flags, sub-rewards of rank 0's envs, float32) as DIR/<name>.npy; the inputs are seeded, so two builds
+compare output for output.
+
+--full adds everything else the line has carried (each of these costs time or runs of its own):
+  whole_epoch   when K is not a whole number of >= 2 epochs, a separately timed block of whole epochs after the K steps; the headline
+                of a --full line is then taken from that block (the rollout average), the K steps stay beside it as requested_region.
   roofline      dominant kernel = physics_ll_kernel.  kernel_ms = its mean duration over the TIMED steps themselves, from HIP
                 events the engine records on the launch stream around one launch in eight, the bracketed position rotating through
                 the epoch (v2p_env_profile_begin_sampled/_end; --kernel-events 1: every launch, which costs 2 %).  achieved =
@@ -133,14 +140,17 @@ class StubTask:
         self.num_envs, self.device = num_envs, "cpu"
         self._target_dof_pos = torch.zeros((num_envs, 331))[:, 7:76]
         self.reset_buf = torch.zeros(num_envs, dtype=torch.long)
-        self._x = torch.zeros(num_envs, 75)
+        self.obs_buf = torch.zeros(num_envs, 75)
+        self.rew_buf = torch.zeros(num_envs)
+        self.extras = {"terminate": torch.zeros(num_envs, dtype=torch.long), "sub_rewards": torch.zeros(num_envs, 4)}
         self._launches = 0
 
     def reset(self):
         self.reset_buf.zero_()
 
     def step_fused(self, a):
-        self._x = 0.5 * self._x + a
+        self.obs_buf.mul_(0.5).add_(a)
+        torch.sum(self.obs_buf, 1, out=self.rew_buf)
         self._launches += 1
 
     def profile_begin(self, n):
@@ -214,6 +224,33 @@ def make_epoch_actions(task, noise_all, out):
     torch.add(noise_all[..., :69], task.context_feat[:, pad:pad + noise_all.shape[0], 168:237].transpose(0, 1), out=out[..., :69])
     out[..., 69:].copy_(noise_all[..., 69:])
     return out
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def step_outputs(tasks):
+    """What a caller of the timed step receives after it (VecTask.step: observations, rewards, reset flags and the extras
+    'terminate' / 'sub_rewards'), the rollout groups concatenated in env order, as float32 host arrays."""
+    def cat(get):
+        return torch.cat([get(tk).reshape(tk.num_envs, -1) for tk in tasks]).to(torch.float32).cpu().numpy()
+
+    return {"obs": cat(lambda tk: tk.obs_buf), "rew": cat(lambda tk: tk.rew_buf)[:, 0], "reset": cat(lambda tk: tk.reset_buf)[:, 0],
+            "terminate": cat(lambda tk: tk.extras["terminate"])[:, 0], "sub_rewards": cat(lambda tk: tk.extras["sub_rewards"])}
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy for every array (first axis = env).  When they hold more than `limit` bytes in all, every array keeps the same
+    fixed, seeded sample of env rows, sorted, and DIR/env_ids.npy says which."""
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes for a in arrays.values()) // n
+    if row_bytes * n > limit:
+        keep = (limit - 256 * (len(arrays) + 1)) // (row_bytes + 8)  # (256 B for each .npy header)
+        ids = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = dict({k: a[ids] for k, a in arrays.items()}, env_ids=ids.astype(np.float64))
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), np.ascontiguousarray(a))
 
 
 def host_cpu_model():
@@ -477,8 +514,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--num-envs", type=int, default=8192, help="envs per GPU")
     ap.add_argument("--no-contact", action="store_true", help="BASELINE config 2 (PD only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--kernel-events", type=int, default=8, help="HIP events around one physics launch in K of the timed steps (1 = every launch)")
+    ap.add_argument("--full", action="store_true", help="also the whole-epoch block behind a short / ragged --steps, the roofline (HIP events around "
+                    "physics launches, committed counter profiles) and the CPU baseline: the plain run times only the requested steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned (rank 0's envs) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--kernel-events", type=int, default=8, help="--full: HIP events around one physics launch in K of the timed steps (1 = every launch)")
     ap.add_argument("--actions-per-step", action="store_true", help="stand-in policy evaluated before every step (one elementwise kernel between the physics launches) instead of once per epoch from the context window")
     ap.add_argument("--action-noise", type=float, default=0.17, help="sigma of the stand-in policy (0.17 = SURVEY 8d; small values = tracking-quality actions, fewer falls)")
     ap.add_argument("--solver", choices=["pgs", "tgs"], default="pgs")
@@ -505,6 +545,8 @@ def main():
     ap.add_argument("--ppo-reference-critic-passes", action="store_true", help="--ppo: evaluate the critic twice per step like the reference (A/B of reuse_next_values)")
     ap.add_argument("--stub-task", action="store_true", help=argparse.SUPPRESS)  # launch-logic test without GPUs (gloo, CPU); never a measurement
     args = ap.parse_args()
+    if args.dump_outputs and args.ppo:
+        raise SystemExit("--dump-outputs: the rollout benchmark only, not --ppo")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus, sys.argv[1:], args.stub_task))
@@ -598,11 +640,14 @@ def main():
 
     def timed_block(nsteps, ev_stride):
         """Time `nsteps` steps (each run() starts with the per-epoch reset: positions 0 .. nsteps-1 of the epoch, over and over) between two
-        barrier + synchronize pairs; HIP events around one physics launch in ev_stride (recorded by the engine on the launch stream, the
-        bracketed position rotating through the epoch).  Returns (seconds of this rank, mean kernel ms, launches bracketed)."""
+        barrier + synchronize pairs; with an ev_stride (--full), HIP events around one physics launch in ev_stride (recorded by the engine on
+        the launch stream, the bracketed position rotating through the epoch).  Returns (seconds of this rank, mean kernel ms, launches
+        bracketed); (seconds, None, 0) without events."""
         barrier()
         for tk in tasks:
-            if stub:
+            if ev_stride is None:
+                pass
+            elif stub:
                 tk.profile_begin(nsteps)
             else:
                 tk.profile_begin(nsteps, stride=ev_stride, period=HORIZON)
@@ -612,11 +657,12 @@ def main():
         el = time.perf_counter() - t0
         ms_total, cnt = 0.0, 0
         for tk in tasks:
-            a_, b_ = tk.profile_end()
-            ms_total, cnt = ms_total + a_, cnt + b_
+            if ev_stride is not None:
+                a_, b_ = tk.profile_end()
+                ms_total, cnt = ms_total + a_, cnt + b_
             if hasattr(tk, "check"):
                 tk.check()  # device-side errors (a substep job that timed out) fail the run instead of producing a number
-        return el, ms_total / max(cnt, 1), cnt
+        return el, (ms_total / max(cnt, 1) if ev_stride is not None else None), cnt
 
     def over_ranks(x):
         """[value of every rank] (all-gather; one entry without a process group)."""
@@ -627,21 +673,24 @@ def main():
         dist.all_gather(allt, t)
         return [float(v.item()) for v in allt]
 
+    full = args.full
     # (short runs bracket more launches, at least five: 20 steps -> one in four)
-    ev_stride = 1 if stub else max(1, min(args.kernel_events, args.steps // 5))
+    ev_stride = (1 if stub else max(1, min(args.kernel_events, args.steps // 5))) if full else None
     run(args.warmup)
     elapsed_local, phys_ms, launches = timed_block(args.steps, ev_stride)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(tasks))
     times = over_ranks(elapsed_local)
     elapsed = max(times)  # MAX over ranks
     per_rank = [n * args.steps / x for x in times]
-    per_rank_kernel_ms = over_ranks(phys_ms)
+    per_rank_kernel_ms = over_ranks(phys_ms) if full else None
     alive = float(torch.cat([(tk.reset_buf == 0).float() for tk in tasks]).mean().item())
     # Every run() starts an epoch (reset + positions 0, 1, ...), and the early positions of an epoch - standing humanoids - are lighter
     # than the late ones (profiles/*_epoch_profile.txt: 0.32 ms at step 3, 0.61 ms at step 31).  A timed region that is not a whole
-    # number of epochs is therefore NOT the rollout average: such runs (the driver's --steps 20) are followed by a separately timed
+    # number of epochs is therefore NOT the rollout average: with --full such runs (e.g. --steps 20) are followed by a separately timed
     # block of WHOLE_EPOCHS whole epochs, reported as `whole_epoch`; the roofline fractions are taken from that block.
     whole = None
-    if args.steps % HORIZON or args.steps < 2 * HORIZON:
+    if full and (args.steps % HORIZON or args.steps < 2 * HORIZON):
         wsteps = WHOLE_EPOCHS * HORIZON
         w_el, w_ms, w_cnt = timed_block(wsteps, max(1, args.kernel_events))
         w_el = max(over_ranks(w_el))
@@ -658,35 +707,37 @@ def main():
             sys.stderr.write("bench.py: --steps %d is not a whole number of %d-step epochs (positions 0..%d of an epoch are the light ones: %.2f M env-steps/s); "
                              "value = the %d-epoch block timed after it (%.2f M)\n" % (args.steps, HORIZON, args.steps - 1, req_value / 1e6, WHOLE_EPOCHS, value / 1e6))
         nresets = (args.steps + HORIZON - 1) // HORIZON
-        valu, traffic = profiles_view()
-        # the fractions describe the rollout average: from the whole-epoch block when the requested region is not whole epochs
-        k_ms, k_cnt, k_stride = (whole["kernel_ms"], whole["kernel_launches_timed"], max(1, args.kernel_events)) if whole else (phys_ms, launches, ev_stride)
-        achieved = ALGO_BYTES_PER_ENV_STEP * ng / (k_ms * 1e-3) / 1e9
-        roof = {"bound": "valu-issue", "bound_note": "the contract's choices are hbm | mfma; this kernel is bound by neither: while its wave slots are full its SIMDs issue one VALU "
-                "instruction per ~3.4 cycles against a measured ceiling of ~2.7 (valu.valu_issue), at ~24 of 64 lanes active; late in an epoch a launch is as long as "
-                "its heaviest env pair (DESIGN.md 4-5).  achieved / peak / frac are the HBM figures BASELINE.json asks for; valu_frac says how good the kernel is",
-                "kernel": "physics_ll_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "frac_of": "hbm",
-                "traffic": None if traffic is None else traffic["bytes_per_launch"],
-                "traffic_fetch_x2": None if traffic is None else traffic.get("bytes_per_launch_fetch_x2"),
-                "traffic_note": None if traffic is None else traffic.get("note"),
-                "traffic_source": None if traffic is None else traffic["source"],
-                "traffic_kernel_source_sha16": None if traffic is None else traffic["kernel_source_sha16"], "kernel_ms": k_ms, "kernel_launches_timed": k_cnt,
-                "kernel_ms_region": "whole_epoch block (%d epochs)" % WHOLE_EPOCHS if whole else "the timed steps (whole epochs)",
-                "kernel_ms_source": "HIP events recorded by the engine around %s (launch stream)%s" % (
-                    "every physics launch" if k_stride == 1 else "one physics launch in %d" % k_stride,
-                    "" if k_stride == 1 else "; the bracketed step rotates through the positions of the epoch (two event records cost ~8 us of dispatch per bracketed launch: --kernel-events 1 brackets all, -2 % throughput)"),
-                "algorithmic_bytes_per_launch": ALGO_BYTES_PER_ENV_STEP * ng}
-        if whole:
-            roof["requested_region"] = {"kernel_ms": phys_ms, "kernel_launches_timed": launches, "events_around_one_launch_in": ev_stride,
-                                        "frac": ALGO_BYTES_PER_ENV_STEP * ng / (phys_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if launches else None}
-            whole["frac"] = roof["frac"]
-        if G > 1:
-            roof["bound_note"] += "; %d ROLLOUT GROUPS: the launches of the groups overlap on the GPU, kernel_ms is the duration of one group's launch WHILE the others run" % G
-        if valu is not None and n == 8192 and G == 1 and not args.no_contact:
-            tflops = valu["flops_per_launch"] / (k_ms * 1e-3) / 1e12
-            roof.update({"valu_tflops": tflops, "valu_peak_tflops": FP32_VECTOR_PEAK_TFLOPS, "valu_frac": tflops / FP32_VECTOR_PEAK_TFLOPS, "valu": valu})
+        roof = None
+        if full:
+            valu, traffic = profiles_view()
+            # the fractions describe the rollout average: from the whole-epoch block when the requested region is not whole epochs
+            k_ms, k_cnt, k_stride = (whole["kernel_ms"], whole["kernel_launches_timed"], max(1, args.kernel_events)) if whole else (phys_ms, launches, ev_stride)
+            achieved = ALGO_BYTES_PER_ENV_STEP * ng / (k_ms * 1e-3) / 1e9
+            roof = {"bound": "valu-issue", "bound_note": "the contract's choices are hbm | mfma; this kernel is bound by neither: while its wave slots are full its SIMDs issue one VALU "
+                    "instruction per ~3.4 cycles against a measured ceiling of ~2.7 (valu.valu_issue), at ~24 of 64 lanes active; late in an epoch a launch is as long as "
+                    "its heaviest env pair (DESIGN.md 4-5).  achieved / peak / frac are the HBM figures BASELINE.json asks for; valu_frac says how good the kernel is",
+                    "kernel": "physics_ll_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "frac_of": "hbm",
+                    "traffic": None if traffic is None else traffic["bytes_per_launch"],
+                    "traffic_fetch_x2": None if traffic is None else traffic.get("bytes_per_launch_fetch_x2"),
+                    "traffic_note": None if traffic is None else traffic.get("note"),
+                    "traffic_source": None if traffic is None else traffic["source"],
+                    "traffic_kernel_source_sha16": None if traffic is None else traffic["kernel_source_sha16"], "kernel_ms": k_ms, "kernel_launches_timed": k_cnt,
+                    "kernel_ms_region": "whole_epoch block (%d epochs)" % WHOLE_EPOCHS if whole else "the timed steps (whole epochs)",
+                    "kernel_ms_source": "HIP events recorded by the engine around %s (launch stream)%s" % (
+                        "every physics launch" if k_stride == 1 else "one physics launch in %d" % k_stride,
+                        "" if k_stride == 1 else "; the bracketed step rotates through the positions of the epoch (two event records cost ~8 us of dispatch per bracketed launch: --kernel-events 1 brackets all, -2 % throughput)"),
+                    "algorithmic_bytes_per_launch": ALGO_BYTES_PER_ENV_STEP * ng}
             if whole:
-                whole["valu_frac"] = roof["valu_frac"]
+                roof["requested_region"] = {"kernel_ms": phys_ms, "kernel_launches_timed": launches, "events_around_one_launch_in": ev_stride,
+                                            "frac": ALGO_BYTES_PER_ENV_STEP * ng / (phys_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if launches else None}
+                whole["frac"] = roof["frac"]
+            if G > 1:
+                roof["bound_note"] += "; %d ROLLOUT GROUPS: the launches of the groups overlap on the GPU, kernel_ms is the duration of one group's launch WHILE the others run" % G
+            if valu is not None and n == 8192 and G == 1 and not args.no_contact:
+                tflops = valu["flops_per_launch"] / (k_ms * 1e-3) / 1e12
+                roof.update({"valu_tflops": tflops, "valu_peak_tflops": FP32_VECTOR_PEAK_TFLOPS, "valu_frac": tflops / FP32_VECTOR_PEAK_TFLOPS, "valu": valu})
+                if whole:
+                    whole["valu_frac"] = roof["valu_frac"]
         rccl = None
         if dist is not None and not stub:
             try:
@@ -696,7 +747,7 @@ def main():
         out = {
             "metric": "env-steps/sec at num_envs=%d, SMPL humanoid imitation" % n, "value": value, "unit": "env-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "value_region": "the %d timed steps (whole epochs)" % args.steps if not whole else
+            "value_region": "the %d timed steps (%s)" % (args.steps, "whole epochs" if args.steps % HORIZON == 0 else "not whole epochs: --full adds a whole-epoch block") if not whole else
                             "whole_epoch block: %d steps = %d whole epochs timed right after the %d requested steps, same barriers (a region that is not whole epochs "
                             "times the light start of an epoch: requested_region)" % (whole["steps"], WHOLE_EPOCHS, args.steps),
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -707,7 +758,7 @@ def main():
                                       (", stand-in policy evaluated once per epoch (targets = context frames)" if per_epoch else ", stand-in policy evaluated before every step") + (", TERMINATED ENVS FROZEN (not reference behaviour)" if args.freeze_terminated else "") + (", STUB TASK (launch-logic test, not a measurement)" if stub else "")),
                        "num_envs_per_gpu": n, "global_envs": world * n, "parallelism": "env-sharded x%d, no data-path collective" % world,
                        "world_size_seen": world_seen, "world_size_matches_gpus": world_seen == args.gpus, "backend": None if dist is None else ("gloo" if stub else "nccl(rccl)"),
-                       "rccl_version": rccl, "per_rank_env_steps_per_s": per_rank, "per_rank_kernel_ms": per_rank_kernel_ms,
+                       "rccl_version": rccl, "per_rank_env_steps_per_s": per_rank, "full": full,
                        "alive_fraction_at_end": alive, "substep_jobs": bool(args.substep_jobs),
                        # (early steps of an epoch - standing humanoids - are lighter than late ones: only whole epochs average like a rollout does)
                        "timed_steps_cover_whole_epochs": args.steps % HORIZON == 0,
@@ -716,8 +767,10 @@ def main():
                        "resets_in_timed_region": nresets,
                        "scaling_curve": "no multi-GPU curve has been measured for this engine (the driver's 8-GPU runs were skipped in every round so far: "
                                         "more than one RCCL rank has never run)"},
-            "roofline": roof,
         }
+        if full:
+            out["roofline"] = roof
+            out["config"]["per_rank_kernel_ms"] = per_rank_kernel_ms
         if whole:
             out["whole_epoch"] = whole
             out["requested_region"] = {"steps": args.steps, "value": req_value, "ms_per_step": 1e3 * elapsed / args.steps, "epoch_positions": out["config"]["timed_epoch_positions"]}
@@ -725,7 +778,7 @@ def main():
             from vid2player3d_amd import build
             out["build"] = build.build_info()
             out["build"]["physics_kernel_build"] = task.kernel_build()
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if full and world == 1 and not args.no_cpu_baseline and not stub:
             out["cpu_baseline"] = cpu_baseline()
         line = json.dumps(out)
     else:

@@ -11,6 +11,7 @@ keys whose VALUE passes through one of those helpers are therefore compared with
 as far as that helper's conventions go (SELF_REFERENTIAL_KEYS below; the helpers' mathematics is pinned separately, against independent
 closed forms, in tests/test_rl_games_helpers.py).  Everything else in the file - buffer contents, returns, advantages, the RunningNorm
 of the observations, the reference's loss formulas, Adam - is the reference's own arithmetic."""
+import json
 import os
 import types
 
@@ -414,19 +415,15 @@ AMASS_IM_PARAMS = {  # the `params` block of embodied_pose/cfg/amass_im.yaml:55-
 def test_agent_from_the_references_yaml_block():
     from vid2player3d_amd.ppo import PPOAgent
 
-    params = AMASS_IM_PARAMS
-    ref_yaml = "/root/reference/embodied_pose/cfg/amass_im.yaml"
-    if os.path.exists(ref_yaml):  # (build container only) the literal above IS what the reference's file says
-        import yaml
-
-        with open(ref_yaml) as f:
-            real = yaml.safe_load(f)["params"]
-        for blk in ("config", "network"):
-            for k, v in AMASS_IM_PARAMS[blk].items():
-                if k not in ("mlp", "space"):
-                    assert real[blk][k] == v or str(real[blk][k]) == str(v), (blk, k, real[blk][k], v)
-        assert real["network"]["mlp"]["units"] == [1024, 1024, 512] and real["network"]["space"]["continuous"]["sigma_init"]["val"] == -1.756
-        params = real
+    # the literal above IS what the reference's file says (its params block as recorded by oracle/gen_golden_ref_pins.py)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "amass_im_params.json")) as f:
+        real = json.load(f)
+    for blk in ("config", "network"):
+        for k, v in AMASS_IM_PARAMS[blk].items():
+            if k not in ("mlp", "space"):
+                assert real[blk][k] == v or str(real[blk][k]) == str(v), (blk, k, real[blk][k], v)
+    assert real["network"]["mlp"]["units"] == [1024, 1024, 512] and real["network"]["space"]["continuous"]["sigma_init"]["val"] == -1.756
+    params = real
     a = PPOAgent.from_config(stub_task(8192), params, units=(32, 16))  # (small MLPs: the test only reads the hyper-parameters)
     assert (a.horizon_length, a.gamma, a.tau, a.last_lr, a.e_clip, a.critic_coef, a.mini_epochs, a.minibatch_envs, a.grad_norm) == (32, 0.99, 0.95, 2e-5, 0.2, 5, 6, 512, 50.0)
     assert a.normalize_value and a.normalize_advantage and not a.mixed_precision and a.max_epochs == 10000 and a.save_freq == 200

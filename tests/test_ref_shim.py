@@ -1,13 +1,11 @@
 """The stand-in for `isaacgym.torch_utils` that the golden generator imports the reference through (oracle/ref_shim: Isaac Gym itself is a
-closed binary and absent) is pinned to two independent implementations: scipy's Rotation, and - in the build container, where
-/root/reference exists - the reference's OWN quaternion library (poselib/poselib/core/rotation3d.py), which uses the same xyzw convention.
-A wrong sign or order in the shim would otherwise be baked into goldens, oracle and kernels alike."""
+closed binary and absent) is pinned to two independent implementations: scipy's Rotation, and the reference's OWN quaternion library
+(poselib/poselib/core/rotation3d.py), which uses the same xyzw convention, through vectors recorded from it (oracle/gen_golden_ref_pins.py ->
+tests/golden/ref_rotation3d.npz).  A wrong sign or order in the shim would otherwise be baked into goldens, oracle and kernels alike."""
 import importlib.util
 import os
-import sys
 
 import numpy as np
-import pytest
 import torch
 from scipy.spatial.transform import Rotation
 
@@ -47,22 +45,16 @@ def test_against_scipy():
     assert np.allclose(np.linalg.norm(S.quat_unit(torch.tensor(3.0 * a)).numpy(), axis=1), 1.0)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/poselib/poselib/core/rotation3d.py"), reason="the reference tree is only present in the build container")
 def test_against_the_references_own_quaternion_library():
-    prev, sys.dont_write_bytecode = sys.dont_write_bytecode, True  # never leave __pycache__ in the read-only reference mount
-    sys.path.insert(0, "/root/reference/poselib")
-    try:
-        from poselib.core import rotation3d as R3
-    finally:
-        sys.path.pop(0)
-        sys.dont_write_bytecode = prev
-    a, b = torch.tensor(_rand_quats(100), dtype=torch.float32), torch.tensor(_rand_quats(100), dtype=torch.float32)
-    assert torch.allclose(S.quat_mul(a, b), R3.quat_mul(a, b), atol=1e-6)
-    assert torch.allclose(S.quat_conjugate(a), R3.quat_conjugate(a))
-    ang = torch.tensor(RNG.uniform(-3, 3, size=100), dtype=torch.float32)
-    ax = torch.tensor(RNG.normal(size=(100, 3)), dtype=torch.float32)
-    _same_rotation(S.quat_from_angle_axis(ang, ax).numpy(), R3.quat_from_angle_axis(ang, ax).numpy(), tol=1e-5)
-    # the reference's own rotation test (poselib/core/tests/test_rotation.py:27-32): rotating by q then by its inverse is the identity
-    v = torch.tensor(RNG.normal(size=(100, 3)), dtype=torch.float32)
-    back = R3.quat_rotate(S.quat_conjugate(a), R3.quat_rotate(a, v))
-    assert torch.allclose(back, v, atol=1e-5)
+    with np.load(os.path.join(HERE, "golden", "ref_rotation3d.npz"), allow_pickle=False) as z:
+        R3 = {k: torch.as_tensor(z[k]) for k in z.files}
+    a, b = R3["a"], R3["b"]
+    assert torch.allclose(S.quat_mul(a, b), R3["quat_mul_ab"], atol=1e-6)
+    assert torch.allclose(S.quat_conjugate(a), R3["quat_conjugate_a"])
+    _same_rotation(S.quat_from_angle_axis(R3["ang"], R3["ax"]).numpy(), R3["quat_from_angle_axis"].numpy(), tol=1e-5)
+    # the reference's own rotation test (poselib/core/tests/test_rotation.py:27-32): rotating by q then by its inverse is the identity -
+    # here the reference's rotation of v by q, undone by the shim's conjugate of q
+    v, rot = R3["v"].numpy().astype(np.float64), R3["quat_rotate_a_v"].numpy().astype(np.float64)
+    assert np.allclose(Rotation.from_quat(a.numpy()).apply(v), rot, atol=1e-5)
+    back = Rotation.from_quat(S.quat_conjugate(a).numpy()).apply(rot)
+    assert np.allclose(back, v, atol=1e-5)

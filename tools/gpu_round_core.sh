@@ -11,8 +11,8 @@ timeout 1500 python -m pytest tests -m gpu -q -x -s > $O/pytest_full.log 2>&1
 tail -30 $O/pytest_full.log > $O/pytest_gpu.log
 grep -h "^\[selection\]\|^\[schedules\]" $O/pytest_full.log > $O/selection.log; grep -h "^\[rows\]\|^\[close\]\|^\[vfric\]\|^\[limits\]\|^\[racket-ball" $O/pytest_full.log > $O/rows.log; rm -f $O/pytest_full.log
 timeout 300 python __graft_entry__.py --smoke > $O/smoke.log 2>&1
-timeout 600 python bench.py > $O/bench.log 2>&1
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver_cmd.log 2>&1
+timeout 600 python bench.py --full > $O/bench.log 2>&1
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_cmd.log 2>&1
 for v in "--num-envs 1024 --no-contact" "--num-envs 1024" "--num-envs 4096" "--djokovic" "--racket-ball" "--racket-ball --solver tgs" "--racket-ball --joint-limits 0" "--racket-ball --ball-body-contacts 0" "--racket-ball --per-clip-shapes" "--per-clip-shapes" "--solver tgs" "--friction-frame velocity" "--groups 2" "--action-noise 0.03" "--num-envs 16384 --steps 96 --warmup 32" "--num-envs 32768 --steps 96 --warmup 32" "--num-envs 65536 --steps 64 --warmup 32" "--substep-jobs 0"; do
   echo "[$v] $(timeout 300 python bench.py --no-cpu-baseline $v 2>&1 | tail -1)"
 done > $O/bench_variants.log 2>&1
@@ -21,7 +21,7 @@ rm -rf $O/prof && mkdir -p $O/prof
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o stats -- python $R/bench.py --no-cpu-baseline > $O/rocprof.log 2>&1)
 python $R/tools/rocprof_summary.py $O/prof/stats_results.db > $O/rocprof_stats_default_cmd.txt 2>&1
 rm -rf $O/prof && mkdir -p $O/prof
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o stats -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/rocprof2.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o stats -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/rocprof2.log 2>&1)
 python $R/tools/rocprof_summary.py $O/prof/stats_results.db > $O/rocprof_stats_driver_cmd.txt 2>&1
 rm -rf $O/prof && mkdir -p $O/prof
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o stats -- python $R/bench.py --racket-ball --steps 64 --warmup 32 --no-cpu-baseline > $O/rocprof_rb.log 2>&1)

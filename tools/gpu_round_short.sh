@@ -9,8 +9,8 @@ cd $R
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -5 > $O/pytest_gpu.log
 timeout 300 python __graft_entry__.py --smoke > $O/smoke.log 2>&1
-timeout 600 python bench.py > $O/bench.log 2>&1
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver_cmd.log 2>&1
+timeout 600 python bench.py --full > $O/bench.log 2>&1
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_cmd.log 2>&1
 for v in "--num-envs 1024 --no-contact" "--num-envs 1024" "--num-envs 4096" "--num-envs 4096 --kernel-build 1" "--num-envs 4096 --racket-ball" "--racket-ball" "--solver tgs" "--djokovic"; do
   echo "[$v] $(timeout 300 python bench.py --no-cpu-baseline $v 2>&1 | tail -1)"
 done > $O/bench_variants.log 2>&1

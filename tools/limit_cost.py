@@ -17,7 +17,7 @@ if %d:
         pass
     racket.PLAYERS["djokovic"]["limits"] = {k: tuple((-170.0, 170.0) if r is not None else None for r in v) for k, v in racket.PLAYERS["djokovic"]["limits"].items()}
 import bench
-sys.argv = ["bench.py", "--no-cpu-baseline", "--racket-ball", "--steps", "192", "--warmup", "64"] + %r
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--racket-ball", "--steps", "192", "--warmup", "64"] + %r
 bench.main()
 """
 for name, wide, extra in (("player ranges", 0, []), ("+-170 deg (rows never act)", 1, []), ("no limit rows", 0, ["--joint-limits", "0"])):

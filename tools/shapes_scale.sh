@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 for S in ${SHAPES:-0 64 2048 8192}; do
   if [ $S = 0 ]; then A=""; else A="--per-clip-shapes --num-shapes $S"; fi
   T0=$SECONDS
-  timeout 900 python bench.py --no-cpu-baseline $A > $O/bench_$S.log 2> $O/bench_$S.err
+  timeout 900 python bench.py --full --no-cpu-baseline $A > $O/bench_$S.log 2> $O/bench_$S.err
   echo "wall $((SECONDS - T0)) s (process start to exit: import, task construction, 64 + 320 steps)" >> $O/bench_$S.err
   echo "[shapes $S] $(tail -1 $O/bench_$S.log | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.3f M env-steps/s  kernel %.4f ms  alive %.3f' % (d['value']/1e6, d['roofline']['kernel_ms'], d['config']['alive_fraction_at_end']))")  $(grep -h "compiled on the device\|wall" $O/bench_$S.err | tr '\n' ' ')"
   if [ -n "${BENCH_ONLY:-}" ]; then continue; fi

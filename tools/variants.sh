@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O; cd $R
 L=vid2player3d_amd/libv2p_rollout.so
 cp $L /tmp/default.so
-run() { timeout 300 python bench.py --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
+run() { timeout 300 python bench.py --full --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); print('%-28s %10.0f env-steps/s  ms/step %.4f  kernel ms %.4f' % ('$NAME', d['value'], d['ms_per_step'], d['roofline']['kernel_ms']))
