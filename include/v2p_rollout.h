@@ -34,6 +34,7 @@ extern "C" {
 #define V2P_NUM_OBS 461
 #define V2P_MOTION_STATE_DIM 331  /* root_pos3 root_rot4 dof_pos69 root_vel3 root_ang_vel3 dof_vel69 key_pos12 rb_pos72 rb_rot96 */
 #define V2P_CONTEXT_DIM 378       /* body_pos72 body_rot96 dof_pos69 body_pos_gt72 dof_pos_gt69 (humanoid_smpl_im.py:202) */
+#define V2P_CONTEXT_DIM_CONF 402  /* ... + joint_conf24: the frame of a batch with a context transform (humanoid_smpl_im.py:202-205) */
 #define V2P_ABI_VERSION 14
 
 typedef enum {
@@ -152,6 +153,19 @@ int v2p_policy_head(int64_t n, float* mu, const float* context_feat, int64_t ctx
  * its own - env.step masks the rows of finished envs in place, the buffer keeps the sampled actions. */
 int v2p_policy_head_record(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t frame, const float* logstd,
                            const float* noise, float* action, float* sigma_row, float* neglogp_row, float* action_row, float* mu_row, void* stream);
+
+/* The three calls above with the width of a context frame given (ctx_dim floats, >= V2P_CONTEXT_DIM): the frames of a batch with a
+ * context transform are V2P_CONTEXT_DIM_CONF wide (v2p_env_set_context_transform).  Only the first V2P_CONTEXT_DIM floats of a frame are
+ * read - the network reads body_pos / body_rot / dof_pos of the context, never joint_conf.  The calls without `_w` are these with
+ * ctx_dim = V2P_CONTEXT_DIM. */
+int v2p_obs_imitation_packed_w(int64_t rows, int64_t steps, const float* obs, const float* context_feat /*[rows/steps,ctx_frames,ctx_dim]*/,
+                               int64_t ctx_frames, int64_t ctx_dim, int64_t first_frame, const float* norm_mean, const float* norm_std,
+                               float norm_clip, float* out, void* stream);
+int v2p_policy_head_w(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t ctx_dim, int64_t frame, const float* logstd,
+                      const float* noise, float* action, float* sigma, float* neglogp, void* stream);
+int v2p_policy_head_record_w(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t ctx_dim, int64_t frame,
+                             const float* logstd, const float* noise, float* action, float* sigma_row, float* neglogp_row, float* action_row,
+                             float* mu_row, void* stream);
 
 /* The critic's output of a rollout step into the experience buffer (im_agent.py:292-303, 355, 398): value_raw [n] (the network's output) is
  * un-normalised with the value normaliser (running_mean / running_var: DEVICE float64 scalars of rl_games' RunningMeanStd; both NULL = no
@@ -352,6 +366,37 @@ int v2p_env_reset(v2p_env* e, const int64_t* env_ids, int64_t n, const float* mo
  * current clip times (players/im_player.py:238-240): an evaluation rollout runs past the 32-step window without a reset.
  * V2P_ERR_INVALID when the env was created without a context buffer. */
 int v2p_env_context(v2p_env* e, const int64_t* env_ids, int64_t n, const float* motion_times, void* stream);
+
+/* Context transform (cfg env.transform_specs; HumanoidSMPLIM._transform_target, humanoid_smpl_im.py:565-592): the policy's context
+ * window is corrupted the way a pose estimated from video is - joints dropped, joints noised - and carries a joint_conf channel.
+ * The ops run in the yaml's key order, on each (env, frame, body) of the window, AFTER the clean sample and before anything is stored:
+ *   V2P_CTX_MASK_JOINTS   (:569-573)  the ORIGINAL ones tensor is zeroed at the bodies of `mask_joints` (bit b = body b) and
+ *                                     body_pos *= it.  After noisy_joints, the reported confidence is another tensor and stays.
+ *   V2P_CTX_NOISY_JOINTS  (:574-586)  noised = u_noise < noise_prob (root included); body_pos += z * (noised ? noise_std : 0);
+ *                                     conf = 2 (1 - Phi(|noise| / (sqrt(3) conf_std))) for EVERY body (un-noised: exactly 1);
+ *                                     conf < min_conf: conf = 0, body_pos = 0.
+ *   V2P_CTX_MASK_RANDOM_JOINTS (:587-591)  dropped = u_drop < drop_prob, never the root: conf = 0, body_pos = 0.
+ * Only body_pos [0,72) and joint_conf [378,402) of a frame change: body_rot, dof_pos, the _gt blocks and context_mask are the clean
+ * window's.  The draws stay on the caller's side (the reference draws with torch.bernoulli / torch.randn_like): `draws` [N,W,24,5]
+ * (device, W = context_length + 2 context_padding) holds per (env id, frame, body) u_noise, z.xyz, u_drop, and is read by every
+ * v2p_env_reset / v2p_env_context for the envs it touches - the caller refills it before each such call.  A Bernoulli(p) is u < p. */
+enum { V2P_CTX_MASK_JOINTS = 1, V2P_CTX_NOISY_JOINTS = 2, V2P_CTX_MASK_RANDOM_JOINTS = 3 };
+typedef struct {
+    int32_t num_ops;       /* 0..3 (0: no corruption, the joint_conf column is all ones: `transform_specs: {}`) */
+    int32_t ops[3];        /* V2P_CTX_* in the order they run; each at most once */
+    uint32_t mask_joints;  /* mask_joints.joints: bit b = body b (24 bits) */
+    float noise_prob;      /* noisy_joints.prob, in [0,1] */
+    float noise_std;       /* noisy_joints.noise_std */
+    float conf_std;        /* noisy_joints.conf_std, > 0 */
+    float min_conf;        /* noisy_joints.min_conf */
+    float drop_prob;       /* mask_random_joints.prob, in [0,1] */
+} v2p_context_transform;
+/* Attaches the transform to the batch and switches it to V2P_CONTEXT_DIM_CONF-float frames (the caller's context_feat must be
+ * [N,W,402]); must be called before the first v2p_env_reset / v2p_env_context.  Refused (V2P_ERR_INVALID, nothing changed): unknown
+ * or repeated ops, bits above body 23, probabilities outside [0,1], conf_std <= 0, draws NULL when noisy_joints or
+ * mask_random_joints is present, a batch without a context buffer, or one that has already built a window.  The transform is
+ * checked before the batch, so a NULL `e` reports what is wrong with `t` first. */
+int v2p_env_set_context_transform(v2p_env* e, const v2p_context_transform* t, float* draws /*[N,W,24,5] device, nullable*/);
 
 /* BaseTask.step(actions) (base_task.py:147-165) = pre_physics_step + _physics_step +
  * post_physics_step.  actions [N,75] is masked IN PLACE for envs whose reset flag is set

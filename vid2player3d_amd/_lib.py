@@ -11,6 +11,8 @@ LIB_PATH = os.path.join(HERE, "libv2p_rollout.so")
 
 NUM_BODIES, NUM_DOF, NUM_ACTIONS, NUM_OBS = 24, 69, 75, 461
 MOTION_STATE_DIM, CONTEXT_DIM = 331, 378
+CONTEXT_DIM_CONF = CONTEXT_DIM + NUM_BODIES  # frames of a batch with a context transform: + joint_conf (humanoid_smpl_im.py:202-205)
+CTX_MASK_JOINTS, CTX_NOISY_JOINTS, CTX_MASK_RANDOM_JOINTS = 1, 2, 3  # v2p_context_transform.ops
 ABI_VERSION = 14
 
 c_f = C.POINTER(C.c_float)
@@ -69,6 +71,11 @@ class BallBuffers(C.Structure):
                 ("has_racket_contact_now", vp), ("contact_force_sum", vp)]
 
 
+class ContextTransform(C.Structure):
+    _fields_ = [("num_ops", C.c_int32), ("ops", C.c_int32 * 3), ("mask_joints", C.c_uint32), ("noise_prob", C.c_float), ("noise_std", C.c_float),
+                ("conf_std", C.c_float), ("min_conf", C.c_float), ("drop_prob", C.c_float)]
+
+
 _lib = None
 
 
@@ -100,6 +107,9 @@ def load():
         "v2p_obs_imitation_packed": [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_float, vp, vp],
         "v2p_policy_head": [C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp],
         "v2p_policy_head_record": [C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp],
+        "v2p_obs_imitation_packed_w": [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_float, vp, vp],
+        "v2p_policy_head_w": [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp],
+        "v2p_policy_head_record_w": [C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp],
         "v2p_gae": [C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp],
         "v2p_value_record": [C.c_int64, vp, vp, vp, C.c_float, vp, vp, vp, vp],
         "v2p_rollout_record": [C.c_int64, vp, C.c_int64] + [vp] * 15,
@@ -109,6 +119,7 @@ def load():
         "v2p_env_create_shapes": [C.POINTER(vp), C.c_int32, c_i32, vp, C.POINTER(SimCfg), vp, C.c_int64, C.POINTER(EnvBuffers), C.c_int, C.POINTER(vp)],
         "v2p_env_reset": [vp, vp, C.c_int64, vp, vp],
         "v2p_env_context": [vp, vp, C.c_int64, vp, vp],
+        "v2p_env_set_context_transform": [vp, C.POINTER(ContextTransform), vp],
         "v2p_env_step": [vp, vp, vp],
         "v2p_env_pre_physics": [vp, vp, vp],
         "v2p_env_physics": [vp, vp],
@@ -144,7 +155,7 @@ def load():
 
 EXPORTED_SYMBOLS = (
     "v2p_model_create", "v2p_model_destroy", "v2p_mlib_create", "v2p_mlib_destroy", "v2p_motion_state", "v2p_reward", "v2p_reset_flags",
-    "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
+    "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_obs_imitation_packed_w", "v2p_policy_head_w", "v2p_policy_head_record_w", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_set_context_transform", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
     "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_last_error", "v2p_abi_version",
 )
 

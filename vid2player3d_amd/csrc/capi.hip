@@ -298,32 +298,53 @@ int v2p_obs_imitation(int64_t n, const float* body_pos, const float* body_rot, c
                                 motion_bodies, norm_mean, norm_std, norm_clip, obs, (hipStream_t)stream);
 }
 
-int v2p_obs_imitation_packed(int64_t rows, int64_t steps, const float* obs, const float* context_feat, int64_t ctx_frames, int64_t first_frame,
-                             const float* norm_mean, const float* norm_std, float norm_clip, float* out, void* stream) {
+int v2p_obs_imitation_packed_w(int64_t rows, int64_t steps, const float* obs, const float* context_feat, int64_t ctx_frames, int64_t ctx_dim,
+                               int64_t first_frame, const float* norm_mean, const float* norm_std, float norm_clip, float* out, void* stream) {
     if (rows < 0 || steps < 1 || rows % steps || !obs || !context_feat || !out || first_frame < 0 || first_frame + steps > ctx_frames ||
-        ((norm_mean == nullptr) != (norm_std == nullptr))) {
+        ctx_dim < V2P_CONTEXT_DIM || ((norm_mean == nullptr) != (norm_std == nullptr))) {
         set_error("v2p_obs_imitation_packed: bad argument");
         return V2P_ERR_INVALID;
     }
-    return launch_obs_imitation_packed(rows, steps, obs, context_feat, ctx_frames, first_frame, norm_mean, norm_std, norm_clip, out, (hipStream_t)stream);
+    return launch_obs_imitation_packed(rows, steps, obs, context_feat, ctx_frames, ctx_dim, first_frame, norm_mean, norm_std, norm_clip, out,
+                                       (hipStream_t)stream);
+}
+
+int v2p_obs_imitation_packed(int64_t rows, int64_t steps, const float* obs, const float* context_feat, int64_t ctx_frames, int64_t first_frame,
+                             const float* norm_mean, const float* norm_std, float norm_clip, float* out, void* stream) {
+    return v2p_obs_imitation_packed_w(rows, steps, obs, context_feat, ctx_frames, V2P_CONTEXT_DIM, first_frame, norm_mean, norm_std, norm_clip, out,
+                                      stream);
+}
+
+int v2p_policy_head_w(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t ctx_dim, int64_t frame, const float* logstd,
+                      const float* noise, float* action, float* sigma, float* neglogp, void* stream) {
+    if (n < 0 || !mu || !context_feat || !logstd || !noise || !action || !neglogp || frame < 0 || frame >= ctx_frames || ctx_dim < V2P_CONTEXT_DIM) {
+        set_error("v2p_policy_head: bad argument");
+        return V2P_ERR_INVALID;
+    }
+    return launch_policy_head(n, mu, context_feat, ctx_frames, ctx_dim, frame, logstd, noise, action, sigma, neglogp, (hipStream_t)stream);
 }
 
 int v2p_policy_head(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t frame, const float* logstd, const float* noise,
                     float* action, float* sigma, float* neglogp, void* stream) {
-    if (n < 0 || !mu || !context_feat || !logstd || !noise || !action || !neglogp || frame < 0 || frame >= ctx_frames) {
-        set_error("v2p_policy_head: bad argument");
+    return v2p_policy_head_w(n, mu, context_feat, ctx_frames, V2P_CONTEXT_DIM, frame, logstd, noise, action, sigma, neglogp, stream);
+}
+
+int v2p_policy_head_record_w(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t ctx_dim, int64_t frame,
+                             const float* logstd, const float* noise, float* action, float* sigma_row, float* neglogp_row, float* action_row,
+                             float* mu_row, void* stream) {
+    if (n < 0 || !mu || !context_feat || !logstd || !noise || !action || !neglogp_row || frame < 0 || frame >= ctx_frames ||
+        ctx_dim < V2P_CONTEXT_DIM) {
+        set_error("v2p_policy_head_record: bad argument");
         return V2P_ERR_INVALID;
     }
-    return launch_policy_head(n, mu, context_feat, ctx_frames, frame, logstd, noise, action, sigma, neglogp, (hipStream_t)stream);
+    return launch_policy_head(n, mu, context_feat, ctx_frames, ctx_dim, frame, logstd, noise, action, sigma_row, neglogp_row, (hipStream_t)stream,
+                              action_row, mu_row);
 }
 
 int v2p_policy_head_record(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t frame, const float* logstd, const float* noise,
                            float* action, float* sigma_row, float* neglogp_row, float* action_row, float* mu_row, void* stream) {
-    if (n < 0 || !mu || !context_feat || !logstd || !noise || !action || !neglogp_row || frame < 0 || frame >= ctx_frames) {
-        set_error("v2p_policy_head_record: bad argument");
-        return V2P_ERR_INVALID;
-    }
-    return launch_policy_head(n, mu, context_feat, ctx_frames, frame, logstd, noise, action, sigma_row, neglogp_row, (hipStream_t)stream, action_row, mu_row);
+    return v2p_policy_head_record_w(n, mu, context_feat, ctx_frames, V2P_CONTEXT_DIM, frame, logstd, noise, action, sigma_row, neglogp_row,
+                                    action_row, mu_row, stream);
 }
 
 int v2p_gae(int64_t horizon, int64_t n, const float* fdones, const float* values, const float* rewards, const float* next_values, float gamma,
@@ -411,6 +432,7 @@ static int env_create_impl(const v2p_model* const* shapes, int32_t num_shapes, c
     e->mlib = mlib;
     e->buf = *b;
     e->n = n;
+    e->ctx.ctx_dim = V2P_CONTEXT_DIM;  // no context transform: 378-float frames
     e->device = device;
     e->motion_id = env_motion_id;
     if (c->schedule != 0 && c->schedule != 1) { set_error("v2p_env_create: schedule must be 0 or 1"); delete e; return V2P_ERR_INVALID; }
@@ -630,14 +652,59 @@ int v2p_env_reset(v2p_env* e, const int64_t* env_ids, int64_t n, const float* mo
     if (!e || !motion_times || n < 0 || n > e->n) { set_error("v2p_env_reset: bad argument"); return V2P_ERR_INVALID; }
     DeviceGuard g(e->device);
     if (!env_ids || n == e->n) e->build_latched = 0;  // an epoch boundary: the next launch may choose its build anew (kernel_build 0)
+    if (e->buf.context_feat) e->context_built = 1;
     return launch_env_reset(e, env_ids, env_ids ? n : e->n, motion_times, (hipStream_t)stream);
 }
 
 int v2p_env_context(v2p_env* e, const int64_t* env_ids, int64_t n, const float* motion_times, void* stream) {
     if (!e || !motion_times || n < 0 || n > e->n) { set_error("v2p_env_context: bad argument"); return V2P_ERR_INVALID; }
     if (!e->buf.context_feat) { set_error("v2p_env_context: the env was created without a context buffer"); return V2P_ERR_INVALID; }
+    e->context_built = 1;
     DeviceGuard g(e->device);
     return launch_env_context(e, env_ids, env_ids ? n : e->n, motion_times, (hipStream_t)stream);
+}
+
+int v2p_env_set_context_transform(v2p_env* e, const v2p_context_transform* t, float* draws) {
+    // the transform first: its refusals do not need a batch (or a GPU)
+    if (!t) { set_error("v2p_env_set_context_transform: null transform"); return V2P_ERR_INVALID; }
+    if (t->num_ops < 0 || t->num_ops > 3) { set_error("v2p_env_set_context_transform: num_ops %d not in [0, 3]", t->num_ops); return V2P_ERR_INVALID; }
+    bool seen[4] = {false, false, false, false};
+    for (int k = 0; k < t->num_ops; ++k) {
+        const int op = t->ops[k];
+        if (op < V2P_CTX_MASK_JOINTS || op > V2P_CTX_MASK_RANDOM_JOINTS) {
+            set_error("v2p_env_set_context_transform: unknown op %d", op);
+            return V2P_ERR_INVALID;
+        }
+        if (seen[op]) { set_error("v2p_env_set_context_transform: op %d repeated", op); return V2P_ERR_INVALID; }
+        seen[op] = true;
+    }
+    if (t->mask_joints >> V2P_NUM_BODIES) { set_error("v2p_env_set_context_transform: mask_joints names bodies above 23"); return V2P_ERR_INVALID; }
+    const bool noisy = seen[V2P_CTX_NOISY_JOINTS], drop = seen[V2P_CTX_MASK_RANDOM_JOINTS];
+    if (noisy && !(t->noise_prob >= 0.f && t->noise_prob <= 1.f)) {
+        set_error("v2p_env_set_context_transform: noisy_joints prob %g not in [0, 1]", (double)t->noise_prob);
+        return V2P_ERR_INVALID;
+    }
+    if (noisy && !(t->conf_std > 0.f)) { set_error("v2p_env_set_context_transform: conf_std %g <= 0", (double)t->conf_std); return V2P_ERR_INVALID; }
+    if (drop && !(t->drop_prob >= 0.f && t->drop_prob <= 1.f)) {
+        set_error("v2p_env_set_context_transform: mask_random_joints prob %g not in [0, 1]", (double)t->drop_prob);
+        return V2P_ERR_INVALID;
+    }
+    if ((noisy || drop) && !draws) { set_error("v2p_env_set_context_transform: a random op needs the draws buffer"); return V2P_ERR_INVALID; }
+    if (!e) { set_error("v2p_env_set_context_transform: null env"); return V2P_ERR_INVALID; }
+    if (!e->buf.context_feat) { set_error("v2p_env_set_context_transform: the env was created without a context buffer"); return V2P_ERR_INVALID; }
+    if (e->context_built) { set_error("v2p_env_set_context_transform: must be called before the first reset / context call"); return V2P_ERR_INVALID; }
+    CtxTransform& x = e->ctx;
+    x.ctx_dim = V2P_CONTEXT_DIM_CONF;
+    x.num_ops = t->num_ops;
+    for (int k = 0; k < 3; ++k) x.ops[k] = k < t->num_ops ? t->ops[k] : 0;
+    x.mask_joints = t->mask_joints;
+    x.noise_prob = t->noise_prob;
+    x.noise_std = t->noise_std;
+    x.conf_div = noisy ? (float)(1.7320508075688772 * (double)t->conf_std) : 1.f;  // np.sqrt(3) * conf_std (:578)
+    x.min_conf = t->min_conf;
+    x.drop_prob = t->drop_prob;
+    x.draws = (noisy || drop) ? draws : nullptr;
+    return V2P_OK;
 }
 
 int v2p_env_pre_physics(v2p_env* e, float* actions, void* stream) {

@@ -192,11 +192,12 @@ int launch_obs_imitation(int64_t n, const float* body_pos, const float* body_rot
 }
 
 // the network's own inputs: obs rows [rows,461] in the order of humanoid_smpl_im.py:198 and context frames [envs,ctx_frames,378] in the
-// order of :202 (body_pos 72 | body_rot 96 | dof_pos 69 | ...); rows = envs * steps, row env*steps+k pairs with frame first_frame+k
-int launch_obs_imitation_packed(int64_t rows, int64_t steps, const float* obs461, const float* context_feat, int64_t ctx_frames, int64_t first_frame,
-                                const float* nmean, const float* nstd, float nclip, float* obs, hipStream_t s) {
+// order of :202 (body_pos 72 | body_rot 96 | dof_pos 69 | ...); rows = envs * steps, row env*steps+k pairs with frame first_frame+k;
+// frames are ctx_dim floats apart (378, or 402 with the joint_conf column of a context transform)
+int launch_obs_imitation_packed(int64_t rows, int64_t steps, const float* obs461, const float* context_feat, int64_t ctx_frames, int64_t ctx_dim,
+                                int64_t first_frame, const float* nmean, const float* nstd, float nclip, float* obs, hipStream_t s) {
     ObsImSrc in = {obs461, obs461 + 72, obs461 + 168, obs461 + 237, obs461 + 306, obs461 + 378, obs461 + 450, NOBS, NOBS, NOBS, NOBS, NOBS, NOBS, NOBS,
-                   context_feat, context_feat + 72, context_feat + 168, V2P_CONTEXT_DIM, V2P_CONTEXT_DIM, V2P_CONTEXT_DIM, steps, ctx_frames, first_frame};
+                   context_feat, context_feat + 72, context_feat + 168, ctx_dim, ctx_dim, ctx_dim, steps, ctx_frames, first_frame};
     return launch_obs_imitation_src(rows, in, nmean, nstd, nclip, obs, s);
 }
 
@@ -331,13 +332,13 @@ int launch_rollout_record(int64_t n, const float* obs, int64_t obs_dim, const fl
 // of randomness), `mu` holds the network's output on entry and the residual mean on exit.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void policy_head_kernel(int64_t n, float* __restrict__ mu, const float* __restrict__ context_feat, int64_t ctx_frames,
-                                                          int64_t frame, const float* __restrict__ logstd, const float* __restrict__ noise,
+                                                          int64_t ctx_dim, int64_t frame, const float* __restrict__ logstd, const float* __restrict__ noise,
                                                           float* __restrict__ action, float* __restrict__ sigma_out, float* __restrict__ neglogp,
                                                           float* __restrict__ action_row, float* __restrict__ mu_row) {
     const int lane = threadIdx.x & 63;
     const int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (e >= n) return;
-    const float* tgt = context_feat + (e * ctx_frames + frame) * V2P_CONTEXT_DIM + 168;  // dof_pos block of the context frame
+    const float* tgt = context_feat + (e * ctx_frames + frame) * ctx_dim + 168;  // dof_pos block of the context frame
     float quad = 0.f, lsum = 0.f;
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
@@ -365,10 +366,10 @@ __global__ __launch_bounds__(256) void policy_head_kernel(int64_t n, float* __re
     if (lane == 0) neglogp[e] = 0.5f * quad + 0.5f * 1.8378770664093453f * (float)NACT + lsum;  // log(2 pi)
 }
 
-int launch_policy_head(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t frame, const float* logstd, const float* noise,
+int launch_policy_head(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t ctx_dim, int64_t frame, const float* logstd, const float* noise,
                        float* action, float* sigma_out, float* neglogp, hipStream_t s, float* action_row, float* mu_row) {
     if (n <= 0) return V2P_OK;
-    hipLaunchKernelGGL(policy_head_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, mu, context_feat, ctx_frames, frame, logstd, noise, action,
+    hipLaunchKernelGGL(policy_head_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, mu, context_feat, ctx_frames, ctx_dim, frame, logstd, noise, action,
                        sigma_out, neglogp, action_row, mu_row);
     return check_hip(hipGetLastError(), "policy_head_kernel");
 }
@@ -457,9 +458,46 @@ __global__ __launch_bounds__(EB_BLOCK) void env_reset_kernel(EnvView v, const in
     sample_body(v.t, fr1, j, e, packed_out(v.b.target[v.cur]));
 }
 
+// ---- context transform (transform_specs; _transform_target, humanoid_smpl_im.py:565-592), one (env, frame, body) of the window.
+// The reference's tensors, per body: `orig` is the ones tensor it makes first (the local `joint_conf`, which mask_joints zeroes and
+// multiplies body_pos with); `conf` is context_dict['joint_conf'], which IS `orig` until noisy_joints replaces it by a new tensor -
+// so a mask_joints after noisy_joints zeroes positions but not the reported confidence, and noisy_joints reports 1 for every
+// un-noised body, masked ones included.  Built without FP contraction: body_pos + z * std and the products round as torch's do.
+__device__ __forceinline__ float apply_context_transform(const CtxTransform& x, const float* __restrict__ d, int j, V3& p) {
+    float orig = 1.f, conf = 1.f;
+    bool replaced = false;
+    for (int k = 0; k < x.num_ops; ++k) {
+        const int op = x.ops[k];
+        if (op == V2P_CTX_MASK_JOINTS) {  // :569-573
+            if ((x.mask_joints >> j) & 1u) orig = 0.f;
+            p = V3{p.x * orig, p.y * orig, p.z * orig};
+        } else if (op == V2P_CTX_NOISY_JOINTS) {  // :574-586
+            const float sd = d[0] < x.noise_prob ? x.noise_std : 0.f;
+            const V3 nz{d[1] * sd, d[2] * sd, d[3] * sd};
+            const float nn = sqrtf(nz.x * nz.x + nz.y * nz.y + nz.z * nz.z) / x.conf_div;
+            const float phi = 0.5f * erfcf(-nn * 0.70710678118654752f);  // scipy's norm.cdf, rounded to float32 like the reference's cast
+            float c = (1.f - phi) * 2.f;
+            p = V3{p.x + nz.x, p.y + nz.y, p.z + nz.z};
+            if (c < x.min_conf) {
+                c = 0.f;
+                p = V3{0.f, 0.f, 0.f};
+            }
+            conf = c;
+            replaced = true;
+        } else {  // V2P_CTX_MASK_RANDOM_JOINTS, :587-591 (the root is never dropped)
+            if (j > 0 && d[4] < x.drop_prob) {
+                if (replaced) conf = 0.f;
+                else orig = 0.f;
+                p = V3{0.f, 0.f, 0.f};
+            }
+        }
+    }
+    return replaced ? conf : orig;
+}
+
 // ---- context window (_init_context, humanoid_smpl_im.py:530-563)
 __global__ __launch_bounds__(EB_BLOCK) void env_context_kernel(EnvView v, const int64_t* __restrict__ env_ids, int64_t n,
-                                                               const float* __restrict__ motion_times) {
+                                                               const float* __restrict__ motion_times, CtxTransform x) {
     const int W = v.p.context_length + 2 * v.p.context_padding;
     int lq = threadIdx.x / NB, j = threadIdx.x % NB;
     int64_t q = (int64_t)blockIdx.x * ENVS_PER_BLOCK + lq;
@@ -471,8 +509,13 @@ __global__ __launch_bounds__(EB_BLOCK) void env_context_kernel(EnvView v, const 
     float t = (motion_times[i] + v.p.dt) + v.p.dt * (float)(w - v.p.context_padding);
     FrameRef fr = frame_lookup(v.t, mid, t, 1, v.p.ground_tolerance);
     BodySample s = sample_body_values(v.t, fr, j);
-    float* o = v.b.context_feat + (e * W + w) * V2P_CONTEXT_DIM;
-    st3(o + 3 * j, s.pos);
+    float* o = v.b.context_feat + (e * W + w) * (int64_t)x.ctx_dim;
+    V3 pos = s.pos;
+    if (x.ctx_dim != V2P_CONTEXT_DIM) {
+        const float* d = x.draws ? x.draws + ((e * W + w) * NB + j) * 5 : nullptr;  // (NULL: mask_joints alone, which draws nothing)
+        o[V2P_CONTEXT_DIM + j] = apply_context_transform(x, d, j, pos);
+    }
+    st3(o + 3 * j, pos);
     st4(o + 72 + 4 * j, s.rot);
     st3(o + 237 + 3 * j, s.pos);
     if (j > 0) {
@@ -499,7 +542,7 @@ int launch_env_context(v2p_env* env, const int64_t* env_ids, int64_t n, const fl
     EnvView v = make_view(env);
     int64_t q = n * (env->p.context_length + 2 * env->p.context_padding);
     unsigned cb = (unsigned)((q + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK);
-    hipLaunchKernelGGL(env_context_kernel, dim3(cb), dim3(EB_BLOCK), 0, s, v, env_ids, n, motion_times);
+    hipLaunchKernelGGL(env_context_kernel, dim3(cb), dim3(EB_BLOCK), 0, s, v, env_ids, n, motion_times, env->ctx);
     return check_hip(hipGetLastError(), "env_context_kernel");
 }
 

@@ -69,6 +69,17 @@ struct DevTables {
     v2p_motion_tables t;
 };
 
+// the context transform of a batch as env_context_kernel reads it (v2p_env_set_context_transform)
+struct CtxTransform {
+    int32_t ctx_dim;    // floats per context frame: V2P_CONTEXT_DIM (no transform) or V2P_CONTEXT_DIM_CONF (joint_conf at [378, 402))
+    int32_t num_ops;
+    int32_t ops[3];
+    uint32_t mask_joints;
+    float noise_prob, noise_std, conf_div, min_conf;  // conf_div = float(sqrt(3) * conf_std)
+    float drop_prob;
+    const float* draws;  // [N][W][24][5]: u_noise, z.xyz, u_drop
+};
+
 }  // namespace v2p
 
 struct v2p_model {
@@ -178,6 +189,8 @@ struct v2p_env {
     int64_t prof_seen;        // physics launches since v2p_env_profile_begin
     int32_t prof_stride, prof_period;  // which of them are bracketed (v2p_env_profile_begin_sampled)
     int pair_have;            // the last physics launch left (key, pos, start) that have not been scattered into perm yet
+    v2p::CtxTransform ctx;    // context frame width + transform (v2p_env_set_context_transform)
+    int context_built;        // a reset / context call has written frames: the width is fixed from now on
 };
 
 #ifndef V2P_LL_WPB
@@ -219,9 +232,9 @@ int launch_obs_imitation(int64_t n, const float* body_pos, const float* body_rot
                          const float* dof_pos, const float* dof_vel, const float* tgt_dof_pos, const float* body_vel,
                          const float* body_ang_vel, const float* motion_bodies, const float* nmean, const float* nstd, float nclip, float* obs,
                          hipStream_t s);
-int launch_obs_imitation_packed(int64_t rows, int64_t steps, const float* obs461, const float* context_feat, int64_t ctx_frames, int64_t first_frame,
-                                const float* nmean, const float* nstd, float nclip, float* obs, hipStream_t s);
-int launch_policy_head(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t frame, const float* logstd, const float* noise,
+int launch_obs_imitation_packed(int64_t rows, int64_t steps, const float* obs461, const float* context_feat, int64_t ctx_frames, int64_t ctx_dim,
+                                int64_t first_frame, const float* nmean, const float* nstd, float nclip, float* obs, hipStream_t s);
+int launch_policy_head(int64_t n, float* mu, const float* context_feat, int64_t ctx_frames, int64_t ctx_dim, int64_t frame, const float* logstd, const float* noise,
                        float* action, float* sigma_out, float* neglogp, hipStream_t s, float* action_row = nullptr, float* mu_row = nullptr);
 int launch_gae(int64_t horizon, int64_t n, const float* fdones, const float* values, const float* rewards, const float* next_values, float gamma,
                float tau, float* advs, hipStream_t s);

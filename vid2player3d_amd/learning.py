@@ -19,6 +19,12 @@ def _chk(t, shape_tail, name):
         raise RuntimeError("%s must be a contiguous float32 CUDA tensor [..., %s]" % (name, ", ".join(map(str, shape_tail))))
 
 
+def _chk_context(t):
+    """context frames [..., W, D]: D = 378, or 402 when the task carries a context transform (joint_conf column)"""
+    if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.dim() < 2 or t.shape[-1] not in (_lib.CONTEXT_DIM, _lib.CONTEXT_DIM_CONF):
+        raise RuntimeError("context_feat must be a contiguous float32 CUDA tensor [..., %d or %d]" % (_lib.CONTEXT_DIM, _lib.CONTEXT_DIM_CONF))
+
+
 class RunningNorm:
     """The policy's observation normaliser (models/running_norm.py:5-43): y = clamp((x - mean) / (std + 1e-8)) with running estimates;
     buffers `n mean var std` as in the reference's module (so its checkpoints load), training mode takes the batch into the
@@ -146,24 +152,24 @@ class ImitationObs:
         out = torch.empty((rows, OBS_IMITATION_DIM), dtype=torch.float32, device=obs.device)
         stream = torch.cuda.current_stream(obs.device).cuda_stream
         mean, std = self._stats_on(obs.device)
-        _lib.check(self._lib.v2p_obs_imitation_packed(rows, steps, _lib.ptr(obs), _lib.ptr(context_feat), context_feat.shape[1], first_frame,
-                                                      _lib.ptr(mean), _lib.ptr(std), self.clip, _lib.ptr(out), stream),
-                   "v2p_obs_imitation_packed")
+        _lib.check(self._lib.v2p_obs_imitation_packed_w(rows, steps, _lib.ptr(obs), _lib.ptr(context_feat), context_feat.shape[1],
+                                                        context_feat.shape[-1], first_frame, _lib.ptr(mean), _lib.ptr(std), self.clip, _lib.ptr(out),
+                                                        stream), "v2p_obs_imitation_packed_w")
         return out
 
     def rollout(self, obs, context_feat, t):
-        """eval / rollout flavour (flatten=False): obs [N,461], context_feat [N,L,378], step t of the epoch -> [N,734]."""
+        """eval / rollout flavour (flatten=False): obs [N,461], context_feat [N,L,378 | 402], step t of the epoch -> [N,734]."""
         _chk(obs, (_lib.NUM_OBS,), "obs")
-        _chk(context_feat, (378,), "context_feat")
+        _chk_context(context_feat)
         return self._run(obs, context_feat, 1, self.context_padding + int(t))
 
     def training(self, obs, context_feat, running_norm=None):
-        """training flavour (flatten=True): obs [N,T,461] (or [N*T,461]), context_feat [N,L,378] -> [N*T,734].
+        """training flavour (flatten=True): obs [N,T,461] (or [N*T,461]), context_feat [N,L,378 | 402] -> [N*T,734].
         running_norm: a `RunningNorm` (or the reference's module) in TRAINING mode - its statistics are updated with this batch's raw
         features first, then the batch is normalised with them (running_norm.py:32-43); the kernel then produces the raw features and
         the normalisation is the module's own.  None: the statistics given at construction, fused into the kernel (eval mode)."""
         _chk(obs, (_lib.NUM_OBS,), "obs")
-        _chk(context_feat, (378,), "context_feat")
+        _chk_context(context_feat)
         n = context_feat.shape[0]
         flat = obs.reshape(-1, _lib.NUM_OBS)
         if flat.shape[0] % n:

@@ -48,7 +48,7 @@ from .learning import OBS_IMITATION_DIM, ImitationObs, RunningNorm, discount_val
 
 LOG_2PI = math.log(2.0 * math.pi)
 NUM_DOF = 69
-CTX_DOF_POS = 168  # offset of `dof_pos` inside a 378-d context frame (body_pos 72 | body_rot 96 | dof_pos 69 | ..., humanoid_smpl_im.py:202)
+CTX_DOF_POS = 168  # offset of `dof_pos` inside a context frame, 378-d or 402-d (body_pos 72 | body_rot 96 | dof_pos 69 | ..., humanoid_smpl_im.py:202)
 
 
 def _world(group):
@@ -247,13 +247,15 @@ class PolicyInference:
             raise NotImplementedError("residual_action = False is not built (the reference's default and both configs use True)")
         if rows is not None:
             a_row, m_row, s_row, l_row = rows
-            _lib.check(self._lib.v2p_policy_head_record(n, _lib.ptr(mu), _lib.ptr(ctx), ctx.shape[1], frame, _lib.ptr(self.model.sigma), _lib.ptr(noise), _lib.ptr(action),
-                                                        _lib.ptr(s_row), _lib.ptr(l_row), _lib.ptr(a_row), _lib.ptr(m_row), _lib.current_stream(mu.device)), "v2p_policy_head_record")
+            _lib.check(self._lib.v2p_policy_head_record_w(n, _lib.ptr(mu), _lib.ptr(ctx), ctx.shape[1], ctx.shape[-1], frame, _lib.ptr(self.model.sigma),
+                                                          _lib.ptr(noise), _lib.ptr(action), _lib.ptr(s_row), _lib.ptr(l_row), _lib.ptr(a_row), _lib.ptr(m_row),
+                                                          _lib.current_stream(mu.device)), "v2p_policy_head_record_w")
             return action, s_row, l_row
         sigma = torch.empty_like(mu)
         nlp = torch.empty(n, dtype=torch.float32, device=mu.device)
-        _lib.check(self._lib.v2p_policy_head(n, _lib.ptr(mu), _lib.ptr(ctx), ctx.shape[1], frame, _lib.ptr(self.model.sigma), _lib.ptr(noise),
-                                             _lib.ptr(action), _lib.ptr(sigma), _lib.ptr(nlp), _lib.current_stream(mu.device)), "v2p_policy_head")
+        _lib.check(self._lib.v2p_policy_head_w(n, _lib.ptr(mu), _lib.ptr(ctx), ctx.shape[1], ctx.shape[-1], frame, _lib.ptr(self.model.sigma),
+                                               _lib.ptr(noise), _lib.ptr(action), _lib.ptr(sigma), _lib.ptr(nlp), _lib.current_stream(mu.device)),
+                   "v2p_policy_head_w")
         return action, sigma, nlp
 
 
@@ -276,7 +278,8 @@ class PPOAgent(PolicyInference):
         self.scaler = torch.amp.GradScaler("cuda", enabled=self.mixed_precision) if self.mixed_precision else None
         self.group = group
         self.device = torch.device(self.task.device)
-        if any(str(t.device) != str(self.task.device) or t.context_padding != self.task.context_padding for t in tasks):
+        if any(str(t.device) != str(self.task.device) or t.context_padding != self.task.context_padding or
+               (len(tasks) > 1 and t.context_feat.shape[-1] != self.task.context_feat.shape[-1]) for t in tasks):  # (frames of 378 or 402)
             raise ValueError("the rollout groups of one agent live on one GPU and share the context layout")
         self.num_actors = sum(t.num_envs for t in tasks)
         self.num_actions = self.task.num_actions

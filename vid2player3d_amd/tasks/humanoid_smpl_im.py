@@ -127,6 +127,32 @@ def default_cfg(num_envs=8192, **env_overrides):
     return {"env": env, "sim": sim, "args": None}
 
 
+CONTEXT_TRANSFORMS = {"mask_joints": _lib.CTX_MASK_JOINTS, "noisy_joints": _lib.CTX_NOISY_JOINTS, "mask_random_joints": _lib.CTX_MASK_RANDOM_JOINTS}
+
+
+def parse_transform_specs(specs, body_names):
+    """cfg env.transform_specs (HumanoidSMPLIM._transform_target, humanoid_smpl_im.py:565-592) -> v2p_context_transform.  The ops keep
+    the mapping's key order (the reference iterates `.items()`); joint names resolve through `body_names` (`.index`: an unknown name
+    raises ValueError).  An unknown transform is refused: the reference skips it silently, and a misspelt key would train on a clean
+    context without a word."""
+    if not isinstance(specs, dict):
+        raise ValueError("env.transform_specs must be a mapping of transform name -> specs, got %r" % (specs,))
+    t = _lib.ContextTransform()
+    for k, (name, spec) in enumerate(specs.items()):
+        if name not in CONTEXT_TRANSFORMS:
+            raise ValueError("env.transform_specs: unknown transform %r (built: %s)" % (name, ", ".join(CONTEXT_TRANSFORMS)))
+        t.ops[k] = CONTEXT_TRANSFORMS[name]
+        if name == "mask_joints":
+            for joint in spec["joints"]:
+                t.mask_joints |= 1 << list(body_names).index(joint)
+        elif name == "noisy_joints":
+            t.noise_prob, t.noise_std, t.conf_std, t.min_conf = (float(spec[x]) for x in ("prob", "noise_std", "conf_std", "min_conf"))
+        else:
+            t.drop_prob = float(spec["prob"])
+    t.num_ops = len(specs)
+    return t
+
+
 # uhc/smpllib/smpl_parser.py:10-35: the SMPL joints in SMPL order, by the names the MJCF bodies carry
 from ..body_shapes import SMPL_JOINT_NAMES as _SMPL_JOINT_NAMES  # noqa: E402
 
@@ -219,8 +245,11 @@ class HumanoidSMPLIM:
         self.obs_shapes = [shape_dict[x] for x in self.obs_names]
         self.obs_dims = [int(np.prod(x)) for x in self.obs_shapes]
         self.context_names = ["body_pos", "body_rot", "dof_pos", "body_pos_gt", "dof_pos_gt"]
+        # transform_specs (:202-205, 565-592): the context window is corrupted inside the context kernel and gains a joint_conf column
+        self._context_transform = None
         if "transform_specs" in env:
-            raise NotImplementedError("transform_specs (joint masking / noise on the context) is not built")
+            self._context_transform = parse_transform_specs(env["transform_specs"], self.body_names)
+            self.context_names.append("joint_conf")
         self.context_shapes = [shape_dict[x] for x in self.context_names]
         self.context_dims = [int(np.prod(x)) for x in self.context_shapes]
         self.is_env_dim_setup = False
@@ -403,7 +432,11 @@ class HumanoidSMPLIM:
         self._reset_ref_motion_times = torch.zeros(n, **f)
         self._target_bufs = [torch.zeros((n, _lib.MOTION_STATE_DIM), **f) for _ in range(2)]
         w = self.context_length + 2 * self.context_padding
-        self.context_feat = torch.zeros((n, w, _lib.CONTEXT_DIM), **f)
+        xf = self._context_transform
+        self.context_feat = torch.zeros((n, w, _lib.CONTEXT_DIM if xf is None else _lib.CONTEXT_DIM_CONF), **f)
+        # the draws of the context transform's random ops, per (env, frame, body): u_noise, z.xyz, u_drop (refilled before every window)
+        random_ops = xf is not None and any(xf.ops[k] != _lib.CTX_MASK_JOINTS for k in range(xf.num_ops))
+        self._context_draws = torch.zeros((n, w, self.num_bodies, 5), **f) if random_ops else None
         self._context_mask_u8 = torch.zeros((n, w), dtype=torch.uint8, device=dev)
         self._humanoid_actor_ids = torch.arange(n, device=dev, dtype=torch.int32)
         self._prev_dof_pos = None
@@ -527,6 +560,9 @@ class HumanoidSMPLIM:
             _lib.check(lib.v2p_env_create_shapes(hs, len(self._h_models), iarr(self._env_shape_ids), self._motion_lib.handle(), C.byref(c),
                                                  _lib.ptr(self._reset_ref_motion_ids), self.num_envs, C.byref(b), self.device_id,
                                                  C.byref(self._h_env)), "v2p_env_create_shapes")
+        if self._context_transform is not None:
+            _lib.check(lib.v2p_env_set_context_transform(self._h_env, C.byref(self._context_transform), _lib.ptr(self._context_draws)),
+                       "v2p_env_set_context_transform")
         self._lib = lib
         self._cur = 0
         self._motion_lib._borrowed = True  # the batch keeps the table pointers: no merge from now on
@@ -640,9 +676,26 @@ class HumanoidSMPLIM:
         """Reference-state init at explicit clip times (parity tests; _reset_ref_state_init :489-528)."""
         times = motion_times.to(device=self.device, dtype=torch.float32).contiguous()
         n = self.num_envs if env_ids is None else env_ids.shape[0]
+        self._draw_context(env_ids, n)
         _lib.check(self._lib.v2p_env_reset(self._h_env, _lib.ptr(env_ids), n, _lib.ptr(times), self._stream()), "v2p_env_reset")
         self._reset_ref_env_ids = env_ids
         self._forward_context()
+
+    def _draw_context(self, env_ids, n):
+        """The draws of the context transform for the windows about to be built (torch.bernoulli / torch.randn_like of
+        _transform_target, :575-576, 588; a Bernoulli(p) is u < p): rows of `env_ids` (None: all) of _context_draws, from the device's
+        global generator like every other draw of the task, so that torch.manual_seed reproduces a run."""
+        d = self._context_draws
+        if d is None:
+            return
+        if env_ids is not None and n != self.num_envs:
+            fresh = torch.empty((n,) + tuple(d.shape[1:]), dtype=d.dtype, device=d.device)
+            fresh.uniform_()
+            fresh[..., 1:4].normal_()
+            d.index_copy_(0, env_ids, fresh)
+            return
+        d.uniform_()
+        d[..., 1:4].normal_()
 
     def _forward_context(self):
         """The tail of the reference's _init_context (humanoid_smpl_im.py:557-563): a registered model is told the new window."""
@@ -667,6 +720,7 @@ class HumanoidSMPLIM:
         times = motion_times.to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(times.shape) != (self.num_envs,):
             raise RuntimeError("_init_context: motion_times must have one entry per env")
+        self._draw_context(None, self.num_envs)
         _lib.check(self._lib.v2p_env_context(self._h_env, None, self.num_envs, _lib.ptr(times), self._stream()), "v2p_env_context")
         self._forward_context()
 
