@@ -937,7 +937,7 @@ static int substep_impl(const v2p_omodel *m, const v2p_oparams *p, v2p_ostate *s
                     bias[3 * c] = fmin(bias[3 * c], rbias[c]);
                 }
             }
-            /* Experiment of round 4 (g_experiment bit 2, value 4; the engine's counterpart is the build switch V2P_LL_ALT_SWEEP): PGS sweeps
+            /* Experiment of round 4 (g_experiment bit 2, value 4; the engine's counterpart was a build switch, since removed): PGS sweeps
              * in ALTERNATING direction over the STOPS (a stop = everything that belongs to one body: the limit rows of its joint, its hull
              * points, the ball point on its hull / the ball x racket points; the ball x ground point is a stop of its own after the last
              * body) - odd sweeps take the stops in descending order, the rows inside a stop in the same order as ever.  A sweep that starts

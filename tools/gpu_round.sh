@@ -35,7 +35,6 @@ V2P_DEBUG=1 V2P_WAVE_TIMES=$O/wave_times.bin timeout 300 python bench.py --full 
 python tools/wave_times.py $O/wave_times.bin > $O/wave_times.txt 2>&1; rm -f $O/wave_times.bin
 V2P_DEBUG=1 V2P_PHASE_TIMING=1 timeout 300 python bench.py --steps 64 --warmup 0 --no-cpu-baseline 2>&1 | grep phase > $O/phase.log
 V2P_PHASE_HEAVY=1 V2P_DEBUG=1 V2P_PHASE_TIMING=1 timeout 300 python bench.py --steps 64 --warmup 0 --no-cpu-baseline 2>&1 | grep phase > $O/phase_heavy.log
-[ -f variants/libv2p_nowalk.so ] && bash tools/walk_ab.sh > $O/walk_ab.log 2>&1
 python tools/epoch_profile.py --epochs 4 > $O/epoch_profile.txt 2>&1
 timeout 600 python tools/limit_cost.py > $O/limit_cost.txt 2>&1
 timeout 900 python tools/soak.py 6000 2>&1 | tail -4 > $O/soak.log

@@ -1,8 +1,9 @@
 #!/bin/bash
-# A/B of the in-tree library against variants/libv2p_<name>.so (default nowalk) on identical inputs (tools/walk_ab.py).
-# The variant: V2P_FLAGS_PHYSICS_LL="-O3 -DV2P_LL_WALK=0" python -c "from vid2player3d_amd import build; build.build(force=True, lib_out='variants/libv2p_nowalk.so', tag='_nowalk')"
+# A/B of the in-tree library against variants/libv2p_<name>.so on identical inputs (tools/walk_ab.py).
+# usage: tools/walk_ab.sh <name>   (the variant: tools/mkvariant.sh <name> [ref], per-file flags through V2P_FLAGS_PHYSICS_LL etc.)
+[ -n "$1" ] || { echo "usage: $0 <name>  (A/B against variants/libv2p_<name>.so)" >&2; exit 2; }
 cd ${GRAFT_REPO_ROOT:-/root/repo}
-L=vid2player3d_amd/libv2p_rollout.so; V=variants/libv2p_${1:-nowalk}.so
+L=vid2player3d_amd/libv2p_rollout.so; V=variants/libv2p_$1.so
 cp $L /tmp/default.so
 echo "== in-tree"; python tools/walk_ab.py /tmp/a.npz ${NENV:-512} 2>&1 | grep -v "^\[selection\]\|amdgpu.ids"
 cp $V $L

@@ -115,13 +115,6 @@ __device__ __forceinline__ void cload4x2(const float* p0, const float* p1, f4& a
     asm volatile("global_load_dwordx4 %0, %2, off sc0 sc1\n\tglobal_load_dwordx4 %1, %3, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(a), "=&v"(b) : "v"(p0), "v"(p1) : "memory");
 }
 
-// five chunks in one block (one wait for all of them): the whole hand-over of a lane
-__device__ __forceinline__ void cload4x5(const float* p0, const float* p1, const float* p2, const float* p3, const float* p4, f4& a, f4& b, f4& c, f4& d, f4& e) {
-    asm volatile("global_load_dwordx4 %0, %5, off sc0 sc1\n\tglobal_load_dwordx4 %1, %6, off sc0 sc1\n\tglobal_load_dwordx4 %2, %7, off sc0 sc1\n\t"
-                 "global_load_dwordx4 %3, %8, off sc0 sc1\n\tglobal_load_dwordx4 %4, %9, off sc0 sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d), "=&v"(e) : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "v"(p4) : "memory");
-}
-
 __device__ __forceinline__ float pull(float v, int src_lane) {
     return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
 }
@@ -142,10 +135,7 @@ __device__ __forceinline__ M3 pull(const M3& a, int s) {
 // (bound_ctrl: the lane without a source - lane 63 - gets 0 from the hardware; with bound_ctrl off it KEEPS the `old` operand, which the
 // compiler then has to materialise with a v_mov 0 in front of every one of these moves, and which keeps it from folding the move into the
 // add that consumes it)
-#ifndef V2P_LL_DPP_BOUND_CTRL
-#define V2P_LL_DPP_BOUND_CTRL 1
-#endif
-__device__ __forceinline__ float from_next(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, V2P_LL_DPP_BOUND_CTRL != 0)); }
+__device__ __forceinline__ float from_next(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true)); }
 __device__ __forceinline__ V3 from_next(V3 v) { return V3{from_next(v.x), from_next(v.y), from_next(v.z)}; }
 __device__ __forceinline__ Sym3 from_next(const Sym3& a) {
     return Sym3{from_next(a.xx), from_next(a.xy), from_next(a.xz), from_next(a.yy), from_next(a.yz), from_next(a.zz)};
@@ -156,52 +146,28 @@ __device__ __forceinline__ M3 from_next(const M3& a) {
     for (int i = 0; i < 9; ++i) r.m[i] = from_next(a.m[i]);
     return r;
 }
-// lane i <- lane i-1 through the DPP network (wave_shr:1): the parent of a link that directly follows it
-__device__ __forceinline__ float from_prev(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x138, 0xf, 0xf, false)); }
-#ifndef V2P_LL_DPP_PARENT
-#define V2P_LL_DPP_PARENT 0
-#endif
-// value held by the parent lane.  `nonchain` = some link of the level being processed does not directly follow its parent: then the
-// pull goes through ds_bpermute (an LDS round trip, ~100+ cycles of exposed latency per level for a wave whose partner is stalled
-// too); on chain-only levels (V2P_LL_DPP_PARENT) it is a DPP shift, a VALU-speed move.  The branch is wave-uniform.
+// value held by the parent lane (ds_bpermute).  (`nonchain` = some link of the level being processed does not directly follow its parent;
+// a DPP shift on the other levels measured slower: docs/NOTES.md.)  Calls through this struct instead of pull(v, plane) directly: the two
+// forms compile to different machine code under -fassociative-math (other rounding), and the parity tests pin this one.
 struct ParentPull {
     int plane;
     bool chain;
-    template <typename F>
-    __device__ __forceinline__ static void each(float* dst, const float* src, int n, F f) {
-#pragma unroll
-        for (int i = 0; i < n; ++i) dst[i] = f(src[i]);
-    }
     __device__ __forceinline__ float operator()(float v, bool nonchain) const {
-        if (V2P_LL_DPP_PARENT && !nonchain) return from_prev(v);
         return pull(v, plane);
     }
-    // DPP on chain-only levels whatever V2P_LL_DPP_PARENT says (the per-update propagation of the sweep, V2P_LL_DPP_DOWN)
-    __device__ __forceinline__ V3 fast(V3 v, bool nonchain) const {
-        if (!nonchain) return V3{from_prev(v.x), from_prev(v.y), from_prev(v.z)};
-        return V3{pull(v.x, plane), pull(v.y, plane), pull(v.z, plane)};
-    }
     __device__ __forceinline__ V3 operator()(V3 v, bool nonchain) const {
-        if (V2P_LL_DPP_PARENT && !nonchain) return V3{from_prev(v.x), from_prev(v.y), from_prev(v.z)};
         return V3{pull(v.x, plane), pull(v.y, plane), pull(v.z, plane)};
     }
     __device__ __forceinline__ Q4 operator()(Q4 q, bool nonchain) const {
-        if (V2P_LL_DPP_PARENT && !nonchain) return Q4{from_prev(q.x), from_prev(q.y), from_prev(q.z), from_prev(q.w)};
         return Q4{pull(q.x, plane), pull(q.y, plane), pull(q.z, plane), pull(q.w, plane)};
     }
     __device__ __forceinline__ Sym3 operator()(const Sym3& a, bool nonchain) const {
-        if (V2P_LL_DPP_PARENT && !nonchain) return Sym3{from_prev(a.xx), from_prev(a.xy), from_prev(a.xz), from_prev(a.yy), from_prev(a.yz), from_prev(a.zz)};
         return Sym3{pull(a.xx, plane), pull(a.xy, plane), pull(a.xz, plane), pull(a.yy, plane), pull(a.yz, plane), pull(a.zz, plane)};
     }
     __device__ __forceinline__ M3 operator()(const M3& a, bool nonchain) const {
         M3 r;
-        if (V2P_LL_DPP_PARENT && !nonchain) {
 #pragma unroll
-            for (int i = 0; i < 9; ++i) r.m[i] = from_prev(a.m[i]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) r.m[i] = pull(a.m[i], plane);
-        }
+        for (int i = 0; i < 9; ++i) r.m[i] = pull(a.m[i], plane);
         return r;
     }
 };
@@ -262,46 +228,8 @@ constexpr bool PARK2 = V2P_LL_PARK2 != 0;
 #define V2P_LL_PARK3 1
 #endif
 constexpr bool PARK3 = V2P_LL_PARK3 != 0;
-#ifndef V2P_LL_KIN_JUMP
-#define V2P_LL_KIN_JUMP 1     // pass 1 (kinematics) by pointer doubling over the tree instead of level by level
-#endif
-#ifndef V2P_LL_PREFETCH_ROWS
-#define V2P_LL_PREFETCH_ROWS 1
-#endif
-#ifndef V2P_LL_FAST_HANDOVER
-#define V2P_LL_FAST_HANDOVER 0  // prologue of a job that takes a hand-over: hand-over slots indexed by WAVE SLOT (not by env), every chunk of a lane in ONE
-                                // load block, the env looked up from the pairing tables while the first poll of the progress word is in flight
-                                // (0, the default: progress word -> env index -> chunks 0,1 -> chunks 48,49 -> chunk 54, up to five dependent round
-                                // trips.  Measured round 4, profiles/r04_ab_handover_targethead.txt: no difference at 8192 / 32768 envs, racket + ball,
-                                // TGS - with three waves per SIMD a job's prologue latency is covered by the other waves; the shorter chain is kept
-                                // as a build switch, bit-identical to the default in the substep-job tests)
-#endif
 #ifndef V2P_LL_WAIT_SLEEP
 #define V2P_LL_WAIT_SLEEP 16  // s_sleep argument (x 64 clocks) between two polls of a job that waits for its predecessor's hand-over
-#endif
-#ifndef V2P_LL_TARGET_HEAD
-#define V2P_LL_TARGET_HEAD 0  // 1: fused step, the next target is sampled by the job of an env's FIRST substep (it depends on the clip and the time
-                              // only) instead of by its last one, so that the jobs that end a launch get shorter.  Measured round 4 (same file):
-                              // 19.89 vs 19.92 M at 8192 envs, 12.74 vs 12.86 M racket + ball, 24.48 vs 24.35 M at 32768: nothing - the tail of a
-                              // launch is set by when the last jobs START, not by the ~8 us they lose
-#endif
-#ifndef V2P_LL_WALK
-#define V2P_LL_WALK 1  // 0: the sweep with a leaf -> root -> leaves propagation after every touched group (A/B; the ball / joint-limit kernels use it)
-#endif
-#ifndef V2P_LL_ALT_SWEEP
-#define V2P_LL_ALT_SWEEP 0  // 1 = experiment of round 4: PGS sweeps alternate their direction over the touched links (oracle: v2p_oracle_experiment(4)),
-                            // the walk goes back and forth and never returns from the last link to the first: 8 % fewer instructions, +3.5 % at
-                            // 8192 envs, +6 % at 32768 - and 1.5 x the distance to the converged solution after 4 sweeps (the link a sweep ends on is
-                            // solved twice in a row): the gain is paid with solver accuracy, so it is NOT the model.  Parity of
-                            // the switched build with the switched oracle was green on all 110 GPU tests (profiles/r04f_*).
-#endif
-#ifndef V2P_LL_DPP_DOWN
-#define V2P_LL_DPP_DOWN 0
-#endif
-#ifndef V2P_LL_EXP
-#define V2P_LL_EXP 0   // TIMING experiments of round 6 (tools/mkvariant.sh; bits 1, 2, 4 break the physics on purpose - they measure what a part costs):
-                       // 1 no post-bounce after limit rows, 2 limit rows never change anything, 4 limit stops taken out of the walk (Lambda depth kept),
-                       // 8 Lambda recursion only as deep as the CONTACT stops, 16 no joint ever has an active limit row (the code stays)
 #endif
 constexpr int PARK_TAR = 0, PARK_W0 = 3, PARK_XD0 = 6, PARK_Q = 9, PARK_X = 13, PARK_CR = 16, PARK_CB = 28, PARK_CL = 32,
               PARK_SCR = PARK3 ? 44 : 16,  // (one row of 64 dwords per wave: lane of the k-th near link)
@@ -319,15 +247,7 @@ constexpr int LDS_FLOATS_PER_WAVE = PARK_SLOTS * 64 + 2 * BL_SLOTS + ROOTLAM_FLO
 // registers would be spilled around on every substep
 // (the closest point comes back BY VALUE, xyz = point, w = distance: an out-parameter by reference is a stack slot of the caller that the
 // callee writes through a pointer)
-#ifndef V2P_LL_GJK_INLINE
-#define V2P_LL_GJK_INLINE 0
-#endif
-#if V2P_LL_GJK_INLINE
-__device__ __forceinline__
-#else
-__device__ __noinline__
-#endif
-f4 ball_hull_distance(ConstShape* S, int v0, int nv, V3 c) {
+__device__ __noinline__ f4 ball_hull_distance(ConstShape* S, int v0, int nv, V3 c) {
     V3 p;
     const float d = hull_closest([&](int k) { return V3{S->hull_verts[v0 + k][0], S->hull_verts[v0 + k][1], S->hull_verts[v0 + k][2]}; }, nv, c, p);
     return f4{p.x, p.y, p.z, d};
@@ -397,7 +317,6 @@ __device__ __forceinline__ void vfric_frame(const V3& w0, const V3& xd0, const V
 // gives them (~+40 % instructions in the friction rows), which the default kernel must not pay.
 template <bool CONTACT, bool MULTI, bool TGS, bool DIAG, bool BALL, bool JOBS, bool LIMITS, bool VFRIC = false>
 __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (LIMITS ? V2P_LL_WPS_LIMITS : V2P_LL_WPS))) void physics_ll_kernel(PhysArgs a) {
-    constexpr bool WALK = V2P_LL_WALK != 0;  // the sweep as one walk over the tree (see the sweep)
     constexpr bool OPAQUE_H = BALL || LIMITS;  // (the headline instantiation keeps its 0 - 12 B of scratch either way: measured no difference, profiles/r06d_variants_spill.log)
     const int64_t N = a.n;
     const int lane = threadIdx.x & 63;
@@ -438,10 +357,6 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     // the inputs of this job were written by another workgroup of this launch - unless that one did not show up in time (below)
     bool handed = !mono && sjob > 0;
     int* const progress = JOBS ? a.job_progress + (bid * LL_WPB + (threadIdx.x >> 6)) : nullptr;
-    // (FAST_HANDOVER: the first poll of the progress word is issued HERE and looked at behind the env lookup below - the two round trips
-    // of a job's prologue that do not depend on each other overlap)
-    int poll0 = 0;
-    if constexpr (JOBS && V2P_LL_FAST_HANDOVER != 0) if (handed && lane == 0) poll0 = __hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     // A job of a cut pair that starts after the pair's step is COMPLETE - its successors gave up waiting, replayed its substeps and the
     // last of them has written the results - must not run: the inputs of the step (state, actions, reset flags) are already those of the
     // next one.  The job of an env's last substep leaves the word at launch x (nsub + 1) + nsub when it ends; every other job looks before
@@ -449,7 +364,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     // per-call ball records or hand-overs from the wrong inputs.)
     if constexpr (JOBS) if (!mono) {
         int done = 0;
-        if (lane == 0) done = (handed && V2P_LL_FAST_HANDOVER != 0 ? poll0 : __hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) >= a.job_epoch * (a.p.nsub + 1) + a.p.nsub;
+        if (lane == 0) done = __hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) >= a.job_epoch * (a.p.nsub + 1) + a.p.nsub;
         if (__builtin_amdgcn_readfirstlane(done)) {
             // (counted: what this job owns besides its substeps - the exposed PD targets, the in-place action masking, the ball's per-call
             // records - was published by nobody for that step; v2p_env_check reports it as an error, not as lost time)
@@ -457,6 +372,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             return;
         }
     }
+    // (a lambda called once: written out in place, the same code compiles to other machine code - see ParentPull)
     auto wait_for_predecessor = [&]() {
     if constexpr (JOBS) if (handed) {
         // wait for the previous substep of this env pair
@@ -467,7 +383,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         int ok = 1;
         if (lane == 0) {
             long spins = 0;
-            while ((V2P_LL_FAST_HANDOVER != 0 && spins == 0 ? poll0 : __hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) < want) {
+            while (__hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < want) {
                 if (spins >= a.job_timeout_spins) {
                     // The predecessor is late beyond reason (jobs are dispatched in index order as far as observed, but nothing promises
                     // it).  This job then runs the pair's EARLIER substeps itself, from the inputs of the step, before its own: every job
@@ -486,9 +402,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         __builtin_amdgcn_wave_barrier();
     }
     };
-    if constexpr (V2P_LL_FAST_HANDOVER == 0) wait_for_predecessor();
+    wait_for_predecessor();
     int64_t e = live_env ? slot : N - 1;
-    if (V2P_LL_FAST_HANDOVER == 0 && a.pl_start && handed) {
+    if (a.pl_start && handed) {
         // (looked up by the job of the pair's first substep, which has handed it over with everything else)
         e = __hip_atomic_load(&a.pl_slot_env[live_env ? slot : N - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     } else if (a.pl_start) {
@@ -506,9 +422,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         const int c1 = __popcll(__ballot(st.x <= r1)) + __popcll(__ballot(st.y <= r1)) + __popcll(__ballot(st.z <= r1)) + __popcll(__ballot(st.w <= r1));
         const int bin = half ? c1 - 1 : c0 - 1, rk = half ? r1 : r0;
         e = a.pl_list[(int64_t)bin * N + (rk - a.pl_start[bin])];
-        if (V2P_LL_FAST_HANDOVER == 0 && JOBS && !mono && lb == 0 && live_env) __hip_atomic_store(&a.pl_slot_env[slot], (int32_t)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (JOBS && !mono && lb == 0 && live_env) __hip_atomic_store(&a.pl_slot_env[slot], (int32_t)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    if constexpr (V2P_LL_FAST_HANDOVER != 0) wait_for_predecessor();
     // the env index behind an opaque move: addresses formed from it inside the substep loop are computed where they are used instead of
     // being hoisted in front of the loop and kept (spilled: 64-bit pointers, 8 bytes of scratch per lane each) across all of it
     auto env_here = [&]() -> int64_t { int64_t v = e; asm volatile("" : "+v"(v)); return v; };
@@ -609,18 +524,6 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     // skips the substeps altogether (frozen envs sort to the end of the launch order, so they share waves)
     const bool frozen = P.freeze_terminated && a.reset[e] == 1;
     const int nsub = (P.freeze_terminated && !any64(!frozen)) ? 0 : P.nsub;
-#if defined(V2P_LL_PRIO_MONO)
-    if (JOBS && mono) __builtin_amdgcn_s_setprio(V2P_LL_PRIO_MONO);  // the heaviest pairs are the critical path of the launch
-#endif
-#if defined(V2P_LL_PRIO)
-    {   // issue priority by predicted load: the heaviest pairs are the critical path of the launch, light waves fill the gaps they leave
-        const int k0 = a.pair_key ? a.pair_key[e] : 0;
-        const int kmax = __builtin_amdgcn_readfirstlane(max(k0, __shfl_xor(k0, 32)));
-        if (kmax >= 96) __builtin_amdgcn_s_setprio(3);
-        else if (kmax >= 64) __builtin_amdgcn_s_setprio(2);
-        else if (kmax >= 40) __builtin_amdgcn_s_setprio(1);
-    }
-#endif
     // substeps of this job (a job that gave up waiting replays the earlier ones)
     const int sub0 = handed ? jstart(sjob) : 0, sub1 = mono ? nsub : (nsub ? (jstart(sjob + 1) < nsub ? jstart(sjob + 1) : nsub) : 0);
     auto ldin = [&](const float* p) -> float { return handed ? cload(p) : *p; };
@@ -645,41 +548,10 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     // (JOBS: the job of an env's first substep reads the engine's state, the others what the job before them handed over: 16-byte chunks,
     // chunk 2b, 2b+1 = joint b (quaternion | rate), chunks 0, 1, 48, 49 = the root (quat | pos, vx | vy, vz, wx, wy | wz))
     // (one hand-over slot per substep: slot s holds the state after substep s)
-    // (FAST_HANDOVER: the slot of a hand-over is the WAVE SLOT of the pair - known from the workgroup index alone - not the env)
-    const int64_t hidx = V2P_LL_FAST_HANDOVER != 0 ? (live_env ? slot : N - 1) : e;
-    float* const hand = JOBS && handed ? a.job_hand + ((int64_t)(sjob - 1) * N + hidx) * HAND_FLOATS : nullptr;
+    float* const hand = JOBS && handed ? a.job_hand + ((int64_t)(sjob - 1) * N + e) * HAND_FLOATS : nullptr;
     bool got = false;
     bool bgot = false;  // (BALL) the ball lane has its state from the hand-over
-    if constexpr (JOBS && V2P_LL_FAST_HANDOVER != 0) if (handed) {
-        // every chunk of this lane in one block of five loads and ONE wait: a link lane its two chunks (the other three addresses repeat
-        // the first), the root lane chunks 0, 1, 48, 49, 54, the ball lane chunks 50 .. 53
-        const bool isball = BALL && lb == NB;
-        const int k0 = isball ? 50 : 2 * b, k1 = isball ? 51 : 2 * b + 1, k2 = isball ? 52 : (b == 0 ? 48 : 2 * b), k3 = isball ? 53 : (b == 0 ? 49 : 2 * b),
-                  k4 = (!isball && b == 0) ? 54 : k0;
-        f4 c0, c1, c2, c3, c4;
-        cload4x5(hand + 4 * k0, hand + 4 * k1, hand + 4 * k2, hand + 4 * k3, hand + 4 * k4, c0, c1, c2, c3, c4);
-        if (isball) {
-            lds_vfloat* const blh = (lds_vfloat*)(park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + PARK_SLOTS * 64 + half * BL_SLOTS);
-            blh[0] = c0.x; blh[1] = c0.y; blh[2] = c0.z; blh[3] = c0.w; blh[4] = c1.x; blh[5] = c1.y; blh[6] = c1.z; blh[7] = c1.w;
-            blh[8] = c2.x; blh[9] = c2.y; blh[10] = c2.z; blh[11] = c2.w; blh[12] = c3.x; blh[13] = c3.y; blh[14] = c3.z; blh[15] = c3.w;
-            bgot = true;
-        } else if (b == 0) {
-            q = Q4{c0.x, c0.y, c0.z, c0.w};
-            x = V3{c1.x, c1.y, c1.z};
-            xd = V3{c1.w, c2.x, c2.y};
-            w = V3{c2.z, c2.w, c3.x};
-            if (a.actions && valid && jstart(sjob) < a.p.hold_sub) {
-                float* const wp = park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + base;
-                wp[PARK_TAR * 64] = c3.y; wp[(PARK_TAR + 1) * 64] = c3.z; wp[(PARK_TAR + 2) * 64] = c3.w;
-                wp[25 + PARK_TAR * 64] = c4.x; wp[25 + (PARK_TAR + 1) * 64] = c4.y; wp[25 + (PARK_TAR + 2) * 64] = c4.z;
-            }
-        } else {
-            jq = Q4{c0.x, c0.y, c0.z, c0.w};
-            wt = V3{c1.x, c1.y, c1.z};
-        }
-        got = true;
-    }
-    if constexpr (JOBS && V2P_LL_FAST_HANDOVER == 0) if (handed) {
+    if constexpr (JOBS) if (handed) {
         f4 c0, c1;
         cload4x2(hand + 8 * b, hand + 8 * b + 4, c0, c1);
         if (b == 0) {
@@ -764,21 +636,12 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         }
     }
 
-    if constexpr (JOBS && !DIAG && V2P_LL_TARGET_HEAD != 0) {
-        // ---- the NEXT target (reference state one step ahead of the new time), sampled here, in the job of the env's first substep: it
-        // depends on the clip and the time only.  Same function, same arguments as the staged post-physics: the same bits.  (target[cur] -
-        // what the reward of this step compares with - is not touched; the buffer written here held the target before it.)
-        if (a.post.on && first_job && valid && live_env) {
-            const PostArgs& Z = a.post;
-            strict::post_sample_target(Z.b, Z.t, P, Z.motion_id[e], Z.b.cur_time[e] + P.dt, Z.cur, e, b);
-        }
-    }
     if (valid && b != 0) park_put3(PARK_TAR, tar);  // constant for the whole launch (the columns of lanes 0 and 25 hold the wrench there)
     const BallDev& BP = a.ball;
     const bool ball_lane = BALL && lb == NB;  // the first idle lane of the env carries the ball
     if (ball_lane) {
         // (JOBS: state and aerodynamic force - held over a simulate() call - come from the job of the substep before: chunks 50 .. 53)
-        if constexpr (JOBS && V2P_LL_FAST_HANDOVER == 0) if (handed) {
+        if constexpr (JOBS) if (handed) {
             f4 c0, c1, c2, c3;
             cload4x2(hand + 4 * 50, hand + 4 * 51, c0, c1);
             cload4x2(hand + 4 * 52, hand + 4 * 53, c2, c3);
@@ -831,9 +694,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         int bo = b;
         asm volatile("" : "+v"(bo));
         const V3 lpos{S->local_pos[bo][0], S->local_pos[bo][1], S->local_pos[bo][2]};
-        // ================================================================ pass 1: kinematics, root -> leaves by level
+        // ================================================================ pass 1: kinematics, by pointer doubling (kin_jump)
         V3 zw{0.f, 0.f, 0.f}, zv{0.f, 0.f, 0.f};
-#if V2P_LL_KIN_JUMP
         {
             V3 wrel{0.f, 0.f, 0.f};
             kin_jump(q, x, w, xd, jq, wt, lpos, r, wrel);
@@ -843,24 +705,6 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 zv = cross(pw, wpr);
             }
         }
-#else
-        for (int d = 1; d <= maxd; ++d) {
-            const bool nc = (nonchain >> d) & 1;
-            Q4 pq = pp(q, nc);
-            V3 px = pp(x, nc), pw = pp(w, nc), pxd = pp(xd, nc);
-            if (dep == d) {
-                q = qnormalize(qmul(pq, jq));
-                r = mul(q2mat(pq), lpos);
-                x = px + r;
-                V3 wrel = mul(q2mat(q), wt);
-                w = pw + wrel;
-                V3 wpr = cross(pw, r);
-                xd = pxd + wpr;
-                zw = cross(pw, wrel);
-                zv = cross(pw, wpr);
-            }
-        }
-#endif
         // (racket + ball: the ball lane and the ball x hull narrow phase run HERE, right after the kinematics, where a lane holds little
         // more than its pose and velocity: further down, next to the link's inertia blocks, their temporaries did not fit)
         if (BALL) {
@@ -1432,7 +1276,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 }
                 limact = anyrow;
             }
-            const unsigned long long lmb = (LIMITS && !(V2P_LL_EXP & 16)) ? __ballot(valid && limact) : 0ull;
+            const unsigned long long lmb = LIMITS ? __ballot(valid && limact) : 0ull;
             const unsigned lm0 = (unsigned)lmb, lm1 = (unsigned)(lmb >> 32);
             if (DIAG && a.wave_times) { const int tt = __popc(half ? m1 : m0); tsum += tt; tmaxs = tt > tmaxs ? tt : tmaxs; }
             if (last) {
@@ -1442,15 +1286,15 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 for (unsigned t = mine; t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; kdep = dd > kdep ? dd : kdep; }
             }
             if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) { atomicAdd((unsigned long long*)&a.prof[9], (unsigned long long)(__popc(m0) + __popc(m1))); atomicAdd((unsigned long long*)&a.prof[10], 1ull); }
-            const bool sweep_on = ((m0 | m1 | ((V2P_LL_EXP & 32) ? 0u : (lm0 | lm1))) || (BALL && any64(ballground))) && P.n_iter > 0;
+            const bool sweep_on = ((m0 | m1 | lm0 | lm1) || (BALL && any64(ballground))) && P.n_iter > 0;
             if (PARK2 && !sweep_on) unpark_vel(w, xd);
             if (sweep_on) {
                 // deepest touched link of either env: links below it are never read during the sweep, so Lambda and the
                 // per-update propagation stop there; their velocities catch up once at the end (the propagation is linear)
                 // (each env stops at ITS deepest touched link, so its arithmetic does not depend on which env shares the wave)
                 int dn0 = 0, dn1 = 0;
-                for (unsigned t = (V2P_LL_EXP & 8) ? m0 : (m0 | lm0); t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; dn0 = dd > dn0 ? dd : dn0; }
-                for (unsigned t = (V2P_LL_EXP & 8) ? m1 : (m1 | lm1); t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; dn1 = dd > dn1 ? dd : dn1; }
+                for (unsigned t = m0 | lm0; t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; dn0 = dd > dn0 ? dd : dn0; }
+                for (unsigned t = m1 | lm1; t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; dn1 = dd > dn1 ? dd : dn1; }
                 const int dneed = dn0 > dn1 ? dn0 : dn1, dmin = dn0 < dn1 ? dn0 : dn1;
                 const bool insweep = dep <= (half ? dn1 : dn0);  // this link moves with every update; the others catch up afterwards
                 LLPH(4);
@@ -1557,8 +1401,11 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     park_put3(PARK_W0, w);  // the sweep's total delta-velocity of a link = its velocity at the end - these
                     park_put3(PARK_XD0, xd);
                 }
-                // touched links whose parent is the touched link right before them (ascending): they continue a group (below)
-                unsigned chain0 = 0u, chain1 = 0u;
+                // touched links whose parent is the touched link right before them (ascending).  Nothing reads these masks any more (the
+                // per-group sweep that did is gone), but without this loop the compiler lowers the control flow of the sweep differently:
+                // 3 more scalar instructions in the headline instantiation, 0.5 % slower in an A/B.  It goes with the next change that
+                // moves the sweep's code anyway.
+                [[maybe_unused]] unsigned chain0 = 0u, chain1 = 0u;
                 {
                     int prev = -1;
                     for (unsigned t = m0; t; t &= t - 1) {
@@ -1580,10 +1427,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 float tgs_irem = 1.f / h;                // TGS: 1 / (time left in the substep) for separated points
                 const float tgs_pen = P.erp / hs;
                 auto rowbias = [&](float v) -> float { return TGS ? (v >= 0.f ? v * tgs_irem : fmaxf(tgs_pen * v, -P.max_depen)) : v; };
-                static_assert(!VFRIC || (WALK && CONTACT), "the velocity-aligned friction frame exists in the walk form of the sweep");
-                if constexpr (WALK) {
                 // ---- the sweep as ONE WALK over the tree.  Solving the touched links one by one in ascending order visits them in depth-first
-                // order, cyclically, iteration after iteration (back and forth with the experimental ALT switch below); between two of them only
+                // order, cyclically, iteration after iteration; between two of them only
                 // the links on the tree path cur -> LCA -> next need anything:
                 //   up    cur .. LCA: every link hands what its subtree has collected since it last did so (un_new, uf_new) to its parent,
                 //         and the LCA answers what arrives with its own Lambda (Lambda_cc is the response of the whole system at c);
@@ -1603,15 +1448,11 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 // the move INTO each touched link, from the touched link before it (cyclically): depth of their lowest common ancestor |
                 // depth of the link before << 4 | own depth << 8 | side-entry levels << 12 (12 bits).  (A link has depth + 1 ancestors-or-self: depths from ballots.)
                 // LIMITS: the walk also stops at the joints that carry limit rows (their block comes right before the contact block of the link)
-                const unsigned v0 = (LIMITS && !(V2P_LL_EXP & 4)) ? m0 | lm0 : m0, v1 = (LIMITS && !(V2P_LL_EXP & 4)) ? m1 | lm1 : m1;
+                const unsigned v0 = LIMITS ? m0 | lm0 : m0, v1 = LIMITS ? m1 | lm1 : m1;
                 V3 jt_new{0.f, 0.f, 0.f};  // LIMITS: limit impulse of this joint not yet handed up (its reaction, -jt, goes to the parent)
-                // ALT (experiment, off by default: V2P_LL_ALT_SWEEP): odd PGS sweeps visit the stops in DESCENDING order - minfo_rev = the move into a
-                // stop from the stop AFTER it (same fields; the highest stop has none: a backward sweep starts on it, where the forward sweep ended)
-                constexpr bool ALT = V2P_LL_ALT_SWEEP != 0 && !TGS;
-                int minfo = 0, minfo_rev = 0;
+                int minfo = 0;
                 {
                     int p0 = v0 ? 31 - __clz(v0) : 0, p1 = v1 ? 31 - __clz(v1) : 0;
-                    bool first = true;
                     for (unsigned s0 = v0, s1 = v1; s0 | s1; s0 &= s0 - 1, s1 &= s1 - 1) {
                         const int b0 = s0 ? __ffs(s0) - 1 : p0, b1 = s1 ? __ffs(s1) - 1 : p1;
                         const int selp = half ? p1 : p0, selb = half ? b1 : b0;
@@ -1623,12 +1464,6 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         const int sd = (half ? M.side_depths[p1] : M.side_depths[p0]) & ~((2 << dl) - 1);
                         // (bit 28: the link itself is not its parent's first child - the one-joint bounce of a limit block needs it)
                         if (valid && lb == selb && ((half ? s1 : s0) != 0u)) minfo = dl | (du << 4) | (dn << 8) | (sd << 12) | ((LIMITS && !firstchild) ? 1 << 28 : 0);
-                        if (ALT && !first) {
-                            // the same pair walked the other way: from the stop b (deeper in the order) back into the stop before it
-                            const int sdr = (half ? M.side_depths[b1] : M.side_depths[b0]) & ~((2 << dl) - 1);
-                            if (valid && lb == selp && ((half ? s1 : s0) != 0u)) minfo_rev = dl | (dn << 4) | (du << 8) | (sdr << 12) | ((LIMITS && !firstchild) ? 1 << 28 : 0);
-                        }
-                        first = false;
                         p0 = b0;
                         p1 = b1;
                     }
@@ -1748,8 +1583,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     }
                     LLSUB(14);
                 };
-                // ---- ball x ground: a stop of its own after the last link - the last rows of a forward sweep, the first of a backward one (point
-                // at -R z of the centre; rows n = z, t1 = x, t2 = y); returns whether any lane's rows changed something
+                // ---- ball x ground: a stop of its own after the last link - the last rows of a sweep (point at -R z of the centre; rows
+                // n = z, t1 = x, t2 = y); returns whether any lane's rows changed something
                 auto ball_ground_rows = [&](int done) -> int {
                     bool bmoved = false;
                     if (ballground && !((done >> half) & 1)) {
@@ -1781,15 +1616,12 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     return ((unsigned)bm != 0u ? 1 : 0) | ((unsigned)(bm >> 32) != 0u ? 2 : 0);
                 };
                 // an env whose whole sweep changed nothing has reached the fixed point of its rows: it takes no part in the remaining sweeps,
-                // whatever the env it shares the wave with still does.  (Its later sweeps change nothing: exactly so with ascending sweeps,
-                // where the same moves re-derive the same velocities - the block updates they would take are saved; with the ALT experiment a
-                // sweep in the other direction reaches the same links over other moves, i.e. with other rounding, and an env that kept
-                // iterating for its wave partner's sake would depend on it.)
+                // whatever the env it shares the wave with still does.  (Its later sweeps change nothing: the same moves re-derive the same
+                // velocities - the block updates they would take are saved.)
                 int done = 0;
                 for (int it = 0; it < P.n_iter; ++it) {
                     unsigned t0 = (done & 1) ? 0u : v0, t1 = (done & 2) ? 0u : v1;
                     int moved = 0;  // bit h: env h changed something in this sweep (wave-uniform)
-                    const bool backward = ALT && (it & 1);  // (wave-uniform)
                     if (TGS && it > 0) {
                         // gaps advance with the normal velocity the points have after the previous sweep (touched links are current)
 #pragma unroll
@@ -1819,9 +1651,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             }
                         }
                     }
-                    if (BALL && backward) moved |= ball_ground_rows(done);  // (the last stop of a forward sweep is the first of a backward one)
                     while (t0 | t1) {
-                        const int b0 = t0 ? (backward ? 31 - __clz(t0) : __ffs(t0) - 1) : -1, b1 = t1 ? (backward ? 31 - __clz(t1) : __ffs(t1) - 1) : -1;
+                        const int b0 = t0 ? __ffs(t0) - 1 : -1, b1 = t1 ? __ffs(t1) - 1 : -1;
                         t0 &= ~(b0 < 0 ? 0u : 1u << b0);
                         t1 &= ~(b1 < 0 ? 0u : 1u << b1);
                         if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[8], 1ull);
@@ -1829,8 +1660,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         const int smv = __builtin_amdgcn_readfirstlane(((live0 && b0 >= 0 && b0 != cur0) ? 1 : 0) | ((live1 && b1 >= 0 && b1 != cur1) ? 2 : 0));
                         int came_down = 0;  // LIMITS: bit h = env h has just come DOWN to its link (the lowest common ancestor of the move lies above it)
                         if (smv) {
-                            const int msel = backward ? minfo_rev : minfo;
-                            const int i0 = __builtin_amdgcn_readlane(msel, b0 < 0 ? 0 : b0), i1 = __builtin_amdgcn_readlane(msel, 32 + (b1 < 0 ? 0 : b1));
+                            const int i0 = __builtin_amdgcn_readlane(minfo, b0 < 0 ? 0 : b0), i1 = __builtin_amdgcn_readlane(minfo, 32 + (b1 < 0 ? 0 : b1));
                             walk_to(b0 < 0 ? 0 : b0, b1 < 0 ? 0 : b1, i0, i1, (smv & 1) != 0, (smv & 2) != 0);
                             if (LIMITS) came_down = smv & (((i0 & 15) < ((i0 >> 8) & 15) ? 1 : 0) | ((i1 & 15) < ((i1 >> 8) & 15) ? 2 : 0));
                         }
@@ -1877,7 +1707,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                                     jt_new = jt_new + jt;
                                     lchg = tq[0] != 0.f || tq[1] != 0.f || tq[2] != 0.f;
                                 }
-                                const unsigned long long lc = __ballot((V2P_LL_EXP & 2) ? false : lchg);
+                                const unsigned long long lc = __ballot(lchg);
                                 const int sl = __builtin_amdgcn_readfirstlane(((unsigned)lc != 0u ? 1 : 0) | ((unsigned)(lc >> 32) != 0u ? 2 : 0));
                                 if (sl) {
                                     // the joint answers, and so does everything above it: one joint up (the parent turns), one joint down again
@@ -1887,7 +1717,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                                     // (deferring this move to the env's next one - it goes up through the parent anyway, or can be widened by a level when it
                                     // goes down into the joint's subtree - was built and measured in round 6: +0.4 %, inside the noise, because most limit
                                     // stops of the racket arm carry contact rows too and need the link current at once; not kept)
-                                    if (!(V2P_LL_EXP & 1)) walk_to(b0 < 0 ? 0 : b0, b1 < 0 ? 0 : b1, j0i, j1i, (sl & 1) != 0, (sl & 2) != 0);
+                                    walk_to(b0 < 0 ? 0 : b0, b1 < 0 ? 0 : b1, j0i, j1i, (sl & 1) != 0, (sl & 2) != 0);
                                 }
                             }
                         }
@@ -1993,7 +1823,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         if (DIAG && a.prof && !chg && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[19], 1ull);
                         LLSUB(11);
                     }
-                    if (BALL && !backward) moved |= ball_ground_rows(done);
+                    if (BALL) moved |= ball_ground_rows(done);
                     if (TGS && (live0 || live1)) {
                         walk_close(dneed, false);  // (the links below catch up once, after the last iteration)
                         un_tot = un_new = uf_new = Dw = Dv = V3{0.f, 0.f, 0.f};
@@ -2005,266 +1835,10 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     }
                 }
                 if (!TGS && (live0 || live1)) walk_close(maxd, true);
-                } else
-                for (int it = 0; it < P.n_iter; ++it) {
-                    static_assert(WALK || !(TGS && (BALL || LIMITS)), "the per-group propagation (V2P_LL_WALK=0) solves the ball and limit rows under PGS only");
-                    unsigned t0 = m0, t1 = m1, l0 = lm0, l1 = lm1;
-                    bool moved = false;
-                    if (TGS && it > 0) {
-                        // gaps advance with the normal velocity the points have after the previous sweep (touched links are current)
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) { const V3 rc = CS.cr(c); CS.set_bias(c, CS.bias(c) + hs * (rc.y * w.x - rc.x * w.y + xd.z)); }
-                        tgs_irem = 1.f / (h - (float)it * hs);
-                    }
-                    while (t0 | t1 | l0 | l1) {
-                        // ---- one GROUP per env: a touched link and, while the next touched link (ascending order) is a child of the
-                        // one just solved, that child too.  Inside a group a link sees its parent's impulses through the parent's own
-                        // response (Lambda_parent x impulse, propagated over one joint), and the leaf->root->leaves propagation runs
-                        // ONCE for the whole chain (a limb lying on the ground, ankle + toe of a standing foot) - linear, so the
-                        // sequence of row updates is exactly the one of solving the links one by one.
-                        int b0 = t0 ? __ffs(t0) - 1 : -1, b1 = t1 ? __ffs(t1) - 1 : -1;
-                        // LIMITS: the next event of an env is the limit block of joint j when no touched link below j is left
-                        const int j0 = l0 ? __ffs(l0) - 1 : 99, j1 = l1 ? __ffs(l1) - 1 : 99;
-                        const bool lim0 = LIMITS && j0 != 99 && (b0 < 0 || j0 <= b0), lim1 = LIMITS && j1 != 99 && (b1 < 0 || j1 <= b1);
-                        if (lim0) { b0 = j0; l0 &= l0 - 1; } else t0 &= t0 - 1;
-                        if (lim1) { b1 = j1; l1 &= l1 - 1; } else t1 &= t1 - 1;
-                        const bool mylim = half ? lim1 : lim0;
-                        int last0 = b0, last1 = b1;
-                        long long tsub = DIAG && a.prof ? clock64() : 0;
-                        if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[8], 1ull);
-                        V3 un{0.f, 0.f, 0.f}, uf{0.f, 0.f, 0.f};
-                        V3 Dw{0.f, 0.f, 0.f}, Dv{0.f, 0.f, 0.f};  // velocity change of the link just solved due to the group's impulses so far
-                        V3 jt{0.f, 0.f, 0.f};  // LIMITS: the joint impulse of this block, world axes (its reaction goes to the parent)
-                        if (LIMITS && (lim0 || lim1)) {
-                            const V3 pw = pp(w, true);  // all links are current between blocks
-                            if (valid && mylim && lb == (half ? b1 : b0)) {
-                                const M3 R = q2mat(Q4{park[PARK_Q * 64], park[(PARK_Q + 1) * 64], park[(PARK_Q + 2) * 64], park[(PARK_Q + 3) * 64]});
-                                const V3 om0 = mulT(R, w - pw);  // joint rate, body axes
-                                float om[3] = {om0.x, om0.y, om0.z}, tq[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-                                for (int i = 0; i < 3; ++i) {
-                                    const V3 kc = i == 0 ? V3{Kd.xx, Kd.xy, Kd.xz} : (i == 1 ? V3{Kd.xy, Kd.yy, Kd.yz} : V3{Kd.xz, Kd.yz, Kd.zz});
-                                    const float kii = i == 0 ? kc.x : (i == 1 ? kc.y : kc.z);
-                                    const float rel = lsgn[i] * om[i] + lbias[i];
-                                    const float nl = fmaxf(llam[i] - rel * __builtin_amdgcn_rcpf(kii), 0.f);
-                                    const float dl = lsgn[i] != 0.f ? nl - llam[i] : 0.f;
-                                    llam[i] += dl;
-                                    const float sdl = lsgn[i] * dl;
-                                    tq[i] = sdl;
-                                    om[0] += kc.x * sdl; om[1] += kc.y * sdl; om[2] += kc.z * sdl;
-                                }
-                                jt = mul(R, V3{tq[0], tq[1], tq[2]});
-                                un = jt;
-                            }
-                        }
-                        for (int step = 0;; ++step) {
-                            const int bsel = half ? b1 : b0;
-                            const bool me = valid && (lb == bsel) && !(LIMITS && mylim);
-                            V3 tw{0.f, 0.f, 0.f}, tv{0.f, 0.f, 0.f};
-                            if (step > 0) {
-                                const V3 pdw = pp(Dw, true), pdv = pp(Dv, true);
-                                if (me) {
-                                    tv = pdv + cross(pdw, r);
-                                    tw = mul(Di, aug * pdw) - mul(E, tv);
-                                }
-                            }
-                            if (me) {
-                                V3 wl = w + tw, xl = xd + tv;
-#if V2P_LL_PREFETCH_ROWS
-                                // all four records of the link at once (one LDS round trip instead of one per point; unused slots hold zeros)
-                                V3 rr4[4], lam4[4];
-                                float bias4[4];
-#pragma unroll
-                                for (int c = 0; c < 4; ++c) { rr4[c] = CS.cr(c); lam4[c] = CS.lam(c); bias4[c] = CS.bias(c); }
-#endif
-#pragma unroll
-                                for (int c = 0; c < 4; ++c) {
-                                    const bool active = c < cnt;
-                                    if (!any64(active)) break;  // uniform over the (at most two) touched links solved here
-#if V2P_LL_PREFETCH_ROWS
-                                    V3 rr = rr4[c];
-                                    const V3 lam0 = lam4[c];
-#else
-                                    V3 rr = CS.cr(c);
-                                    const V3 lam0 = CS.lam(c);
-#endif
-                                    float ln = lam0.x, l1 = lam0.y, l2 = lam0.z;
-                                    // a point without normal impulse (hence without friction impulses: they are clamped to mu x normal)
-                                    // that is separating stays as it is: its three rows would change nothing
-                                    // (masked per lane as well, so that an env's numbers do not depend on what its wave partner does)
-#if V2P_LL_PREFETCH_ROWS
-                                    const float bias_c = rowbias(bias4[c]);
-#else
-                                    const float bias_c = rowbias(CS.bias(c));
-#endif
-                                    const bool act = active && !(ln == 0.f && rr.y * wl.x - rr.x * wl.y + xl.z + bias_c >= 0.f);
-                                    if (!any64(act)) continue;
-#pragma unroll
-                                    for (int ax = 0; ax < 3; ++ax) {
-                                        V3 dir = ax == 0 ? V3{0.f, 0.f, 1.f} : (ax == 1 ? V3{1.f, 0.f, 0.f} : V3{0.f, 1.f, 0.f});
-                                        V3 jn = cross(rr, dir);
-                                        V3 yw = mul(Lam.A, jn) + mul(Lam.B, dir);
-                                        V3 yv = V3{dot(col(Lam.B, 0), jn), dot(col(Lam.B, 1), jn), dot(col(Lam.B, 2), jn)} + mul(Lam.C, dir);
-                                        float wii = dot(jn, yw) + dot(dir, yv);
-                                        float rel = dot(jn, wl) + dot(dir, xl) + (ax == 0 ? bias_c : 0.f);
-                                        float old = ax == 0 ? ln : (ax == 1 ? l1 : l2);
-                                        float nl = old - rel * __builtin_amdgcn_rcpf(wii);
-                                        if (ax == 0) nl = fmaxf(nl, 0.f);
-                                        else { float lim = P.mu * ln; nl = fminf(fmaxf(nl, -lim), lim); }
-                                        float dl = act ? nl - old : 0.f;
-                                        if (ax == 0) ln += dl; else if (ax == 1) l1 += dl; else l2 += dl;
-                                        wl = wl + dl * yw;
-                                        xl = xl + dl * yv;
-                                        un = un + dl * jn;
-                                        uf = uf + dl * dir;
-                                    }
-                                    CS.set_lam(c, V3{ln, l1, l2});
-                                }
-                                if (BALL && ballhit) {
-                                    // ---- ball x racket points: two-body rows (ball point velocity minus racket point velocity); the ball side is
-                                    // a free sphere (1/m, 1/I), the link side goes through Lambda_b like every row of this block
-                                    V3 bv{bl[BL_VEL], bl[BL_VEL + 1], bl[BL_VEL + 2]}, bw{bl[BL_ANG], bl[BL_ANG + 1], bl[BL_ANG + 2]};
-#pragma unroll 1
-                                    for (int j = 0; j < NBREC; ++j) {
-                                        lds_vfloat* rk = bl + BL_RK + 16 * j;
-                                        if (rk[RK_A] == 0.f || !ball_rec_mine(j)) continue;
-                                        const V3 n{rk[RK_N], rk[RK_N + 1], rk[RK_N + 2]}, rl{rk[RK_RL], rk[RK_RL + 1], rk[RK_RL + 2]};
-                                        V3 t1, t2;
-                                        ball_dirs(n, t1, t2);
-                                        const V3 rb = -BP.radius * n;
-                                        float lamn = rk[RK_LAM];
-#pragma unroll 1
-                                        for (int ax = 0; ax < 3; ++ax) {
-                                            const V3 dir = ax == 0 ? n : (ax == 1 ? t1 : t2);
-                                            const V3 jn = cross(rl, dir), jb = cross(rb, dir);
-                                            const V3 yw = mul(Lam.A, jn) + mul(Lam.B, dir);
-                                            const V3 yv = V3{dot(col(Lam.B, 0), jn), dot(col(Lam.B, 1), jn), dot(col(Lam.B, 2), jn)} + mul(Lam.C, dir);
-                                            const float wii = dot(jn, yw) + dot(dir, yv) + BP.inv_mass + BP.inv_inertia * dot(jb, jb);
-                                            const float rel = dot(dir, bv) + dot(jb, bw) - dot(jn, wl) - dot(dir, xl) + (ax == 0 ? rk[RK_BIAS] : 0.f);
-                                            const float old = rk[RK_LAM + ax];
-                                            float nl = old - rel * __builtin_amdgcn_rcpf(wii);
-                                            if (ax == 0) nl = fmaxf(nl, 0.f);
-                                            else { const float lim = (j < 2 ? BP.fric_racket : BP.fric_body) * lamn; nl = fminf(fmaxf(nl, -lim), lim); }
-                                            const float dl = nl - old;
-                                            rk[RK_LAM + ax] = nl;
-                                            if (ax == 0) lamn = nl;
-                                            bv = bv + (dl * BP.inv_mass) * dir;      // +impulse on the ball
-                                            bw = bw + (dl * BP.inv_inertia) * jb;
-                                            wl = wl - dl * yw;                        // -impulse on the racket's link
-                                            xl = xl - dl * yv;
-                                            un = un - dl * jn;
-                                            uf = uf - dl * dir;
-                                        }
-                                    }
-                                    bl[BL_VEL] = bv.x; bl[BL_VEL + 1] = bv.y; bl[BL_VEL + 2] = bv.z;
-                                    bl[BL_ANG] = bw.x; bl[BL_ANG + 1] = bw.y; bl[BL_ANG + 2] = bw.z;
-                                }
-                                Dw = wl - w;  // = tw + Lambda (un, uf): what this link's child (if it is next) starts from
-                                Dv = xl - xd;
-                            }
-                            // does the chain go on?  (next touched link of the env, ascending, is a child of the one just solved)
-                            const int n0 = t0 ? __ffs(t0) - 1 : -1, n1 = t1 ? __ffs(t1) - 1 : -1;
-                            const bool c0 = !lim0 && b0 >= 0 && n0 >= 0 && ((chain0 >> n0) & 1u), c1 = !lim1 && b1 >= 0 && n1 >= 0 && ((chain1 >> n1) & 1u);
-                            if (!(c0 || c1)) break;
-                            b0 = c0 ? n0 : -1;
-                            b1 = c1 ? n1 : -1;
-                            if (c0) { t0 &= t0 - 1; last0 = n0; }
-                            if (c1) { t1 &= t1 - 1; last1 = n1; }
-                        }
-                        const int blast = half ? last1 : last0;
-                        const bool onpath = valid && blast >= 0 && ((desc >> blast) & 1);  // the group's deepest link or one of its ancestors
-                        LLSUB(11);
-                        // an update that changed no impulse (separated or saturated points) moves nothing: skip the propagation
-                        if (!any64(un.x != 0.f || un.y != 0.f || un.z != 0.f || uf.x != 0.f || uf.y != 0.f || uf.z != 0.f)) {
-                            if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[19], 1ull);
-                            continue;
-                        }
-                        moved = true;
-                        // ---- net impulse (un, uf) at the touched link: leaf -> root along the path, level by level
-                        // (after its own level a path link's un is final: it is the joint-space impulse the way down needs)
-                        for (int d = dneed; d >= 1; --d) {
-                            if (!any64(onpath && dep == d)) continue;  // nothing to hand up from this level
-                            V3 cn{0.f, 0.f, 0.f}, cf{0.f, 0.f, 0.f};
-                            if (dep == d && onpath) {
-                                V3 na = aug * mul(Di, un);
-                                V3 fa = uf - V3{dot(col(E, 0), un), dot(col(E, 1), un), dot(col(E, 2), un)};
-                                cn = na + cross(r, fa);
-                                if (LIMITS) cn = cn - jt;
-                                cf = fa;
-                            }
-                            if ((nonchain >> d) & 1) {
-                                un = un + mask(has0, from_next(cn));
-                                uf = uf + mask(has0, from_next(cf));
-                            } else {
-                                un = un + from_next(cn);
-                                uf = uf + from_next(cf);
-                            }
-                            if (((multi >> d) & 1) && any64(dep == d && onpath && !firstchild)) {  // path enters its parent through child 1 or 2
-                                un = un + mask(has1, pull(cn, cl1)) + mask(has2, pull(cn, cl2));
-                                uf = uf + mask(has1, pull(cf, cl1)) + mask(has2, pull(cf, cl2));
-                            }
-                        }
-                        LLSUB(12);
-                        // root response, then root -> leaves: every link moves
-                        V3 ddw{0.f, 0.f, 0.f}, ddv{0.f, 0.f, 0.f};
-                        if (lb == 0) {
-                            ddw = mul(Lam.A, un) + mul(Lam.B, uf);
-                            ddv = V3{dot(col(Lam.B, 0), un), dot(col(Lam.B, 1), un), dot(col(Lam.B, 2), un)} + mul(Lam.C, uf);
-                            w = w + ddw;
-                            xd = xd + ddv;
-                        }
-                        for (int d = 1; d <= dneed; ++d) {
-                            const bool nc = (nonchain >> d) & 1;
-#if V2P_LL_DPP_DOWN
-                            V3 pdw = pp.fast(ddw, nc), pdv = pp.fast(ddv, nc);
-#else
-                            V3 pdw = pp(ddw, nc), pdv = pp(ddv, nc);
-#endif
-                            if (dep == d && insweep) {
-                                V3 av = pdv + cross(pdw, r);
-                                ddw = mul(Di, aug * pdw + un) - mul(E, av);
-                                ddv = av;
-                                w = w + ddw;
-                                xd = xd + ddv;
-                            }
-                        }
-                        LLSUB(14);
-                    }
-                    if (BALL) {
-                        // ---- ball x ground: the last rows of the iteration (point at -R z of the centre; rows n = z, t1 = x, t2 = y)
-                        bool bmoved = false;
-                        if (ballground) {
-                            V3 bv{bl[BL_VEL], bl[BL_VEL + 1], bl[BL_VEL + 2]}, bw{bl[BL_ANG], bl[BL_ANG + 1], bl[BL_ANG + 2]};
-                            const V3 rb{0.f, 0.f, -BP.radius};
-                            float lamn = bl[BL_GLAM];
-#pragma unroll
-                            for (int ax = 0; ax < 3; ++ax) {
-                                const V3 dir = ax == 0 ? V3{0.f, 0.f, 1.f} : (ax == 1 ? V3{1.f, 0.f, 0.f} : V3{0.f, 1.f, 0.f});
-                                const V3 jb = cross(rb, dir);
-                                const float wii = BP.inv_mass + BP.inv_inertia * dot(jb, jb);
-                                const float rel = dot(dir, bv) + dot(jb, bw) + (ax == 0 ? bl[BL_GBIAS] : 0.f);
-                                const float old = bl[BL_GLAM + ax];
-                                float nl = old - rel * __builtin_amdgcn_rcpf(wii);
-                                if (ax == 0) nl = fmaxf(nl, 0.f);
-                                else { const float lim = BP.fric_ground * lamn; nl = fminf(fmaxf(nl, -lim), lim); }
-                                const float dl = nl - old;
-                                bl[BL_GLAM + ax] = nl;
-                                if (ax == 0) lamn = nl;
-                                bv = bv + (dl * BP.inv_mass) * dir;
-                                bw = bw + (dl * BP.inv_inertia) * jb;
-                                bmoved = bmoved || dl != 0.f;
-                            }
-                            bl[BL_VEL] = bv.x; bl[BL_VEL + 1] = bv.y; bl[BL_VEL + 2] = bv.z;
-                            bl[BL_ANG] = bw.x; bl[BL_ANG + 1] = bw.y; bl[BL_ANG + 2] = bw.z;
-                        }
-                        if (any64(bmoved)) moved = true;
-                    }
-                    if (!TGS && !moved) break;  // a whole iteration without any change: the remaining ones would repeat it (PGS: fixed biases)
-                }
                 // links below the deepest touched one: one catch-up pass with the accumulated motion of their parents
                 // (PGS: the walk moves every link when it closes)
                 V3 accw = w - park_get3(PARK_W0), accv = xd - park_get3(PARK_XD0);
-                for (int d = dmin + 1; d <= ((WALK && !TGS) ? 0 : maxd); ++d) {
+                for (int d = dmin + 1; d <= (TGS ? maxd : 0); ++d) {
                     const bool nc = (nonchain >> d) & 1;
                     V3 pdw = pp(accw, nc), pdv = pp(accv, nc);
                     if (dep == d && !insweep) {
@@ -2453,25 +2027,10 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     // ==================================================================== final kinematics -> state, rigid-body state, dof_pos
     // (JOBS: only the job of the last substep produces the exposed tensors and the pairing keys; the others hand the state over)
     const V3 lpos{S->local_pos[bo2][0], S->local_pos[bo2][1], S->local_pos[bo2][2]};
-#if V2P_LL_KIN_JUMP
     if (last_job) {
         V3 rr{0.f, 0.f, 0.f}, wrel{0.f, 0.f, 0.f};
         kin_jump(q, x, w, xd, jq, wt, lpos, rr, wrel);
     }
-#else
-    for (int d = 1; d <= (last_job ? maxd : 0); ++d) {
-        const bool nc = (nonchain >> d) & 1;
-        Q4 pq = pp(q, nc);
-        V3 px = pp(x, nc), pw = pp(w, nc), pxd = pp(xd, nc);
-        if (dep == d) {
-            q = qnormalize(qmul(pq, jq));
-            V3 rr = mul(q2mat(pq), lpos);
-            x = px + rr;
-            w = pw + mul(q2mat(q), wt);
-            xd = pxd + cross(pw, rr);
-        }
-    }
-#endif
     if (DIAG && a.wave_times && lane == 0) {
         long long* wt = a.wave_times + ((int64_t)blockIdx.x * LL_WPB + (threadIdx.x >> 6)) * 4;
         wt[0] = wt0; wt[1] = wall_clock64(); wt[2] = ksum * 8 + kdep + 1024 * (long long)tsum + 1048576ll * tmaxs + 1073741824ll * key_pred;
@@ -2531,7 +2090,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             const bool root = b == 0;
             const float A0 = root ? q.x : jq.x, A1 = root ? q.y : jq.y, A2 = root ? q.z : jq.z, A3 = root ? q.w : jq.w;
             const float B0 = root ? x.x : wt.x, B1 = root ? x.y : wt.y, B2 = root ? x.z : wt.z, B3 = root ? xd.x : 0.f;
-            float* const ho = a.job_hand + ((int64_t)sjob * N + (V2P_LL_FAST_HANDOVER != 0 ? slot : e)) * HAND_FLOATS;
+            float* const ho = a.job_hand + ((int64_t)sjob * N + e) * HAND_FLOATS;
             const bool second = lb & 1;
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
@@ -2552,7 +2111,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             }
         }
         if (BALL && ball_lane && live_env) {
-            float* const ho = a.job_hand + ((int64_t)sjob * N + (V2P_LL_FAST_HANDOVER != 0 ? slot : e)) * HAND_FLOATS;
+            float* const ho = a.job_hand + ((int64_t)sjob * N + e) * HAND_FLOATS;
             cstore4(ho + 4 * 50, bl[0], bl[1], bl[2], bl[3]);
             cstore4(ho + 4 * 51, bl[4], bl[5], bl[6], bl[7]);
             cstore4(ho + 4 * 52, bl[8], bl[9], bl[10], bl[11]);
@@ -2642,7 +2201,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 mid = Z.motion_id[e];
                 t_new = Z.b.cur_time[e] + P.dt;  // _cur_ref_motion_times += dt
                 rp = strict::post_body(Z.b, Z.t, P, mid, t_new, Z.cur, e, b, strict::V3{x.x, x.y, x.z}, strict::Q4{q.x, q.y, q.z, q.w}, strict::V3{xd.x, xd.y, xd.z},
-                                       strict::V3{w.x, w.y, w.z}, strict::V3{qe.x, qe.y, qe.z}, strict::V3{wt.x, wt.y, wt.z}, fl, V2P_LL_TARGET_HEAD == 0);
+                                       strict::V3{w.x, w.y, w.z}, strict::V3{qe.x, qe.y, qe.z}, strict::V3{wt.x, wt.y, wt.z}, fl, true);
             }
             // reward sums over the bodies, bodies ascending like env_post_kernel: the terms go through this lane's LDS column (the parking
             // area is idle by now; a wave's LDS accesses execute in order), lanes 0..3 of each env add one term each
