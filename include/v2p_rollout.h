@@ -484,6 +484,21 @@ typedef struct {                  /* caller-owned DEVICE buffers */
                                    * calls of the control step; overwritten by every step */
 } v2p_ball_buffers;
 int v2p_env_attach_ball(v2p_env* e, const v2p_ball_cfg* cfg, const v2p_ball_buffers* buffers);
+/* Per-shape rackets (ABI 14): in a batch of several body shapes (v2p_env_create_shapes) every shape may hold its racket on a link of its
+ * own - the reference's two-player batches (cfg_v2p dual_mode `different`: env 2k player 0, env 2k+1 player 1, one left-handed) weld it
+ * to L_Wrist (17) for one player and R_Wrist (22) for the other.  An env's racket link, cylinders and racket rigid body are then its
+ * shape's: the ball x racket rows, the ball x hull rows (which skip the racket's link), the racket-hit flags, the racket's reaction in
+ * the link's net contact force and the exported racket state all follow it.  v2p_env_attach_ball gives every shape the cfg's racket
+ * (again, when it is called again); this call, made after it, replaces them: `num_shapes` must equal the batch's shape count.
+ * Refused (V2P_ERR_INVALID, nothing changed): a count that differs, racket_link outside 1..23, num_cylinders outside 0..2, a batch
+ * without a ball. */
+typedef struct {
+    int32_t racket_link;        /* the link the racket is welded to: 22 = R_Wrist, 17 = L_Wrist */
+    int32_t num_cylinders;      /* <= 2 */
+    float cylinders[2][8];      /* centre 3, unit axis 3, half length, radius; racket_link's frame (as v2p_ball_cfg) */
+    float racket_offset[3];     /* origin of the racket rigid body in that frame */
+} v2p_racket_geom;
+int v2p_env_set_racket_shapes(v2p_env* e, const v2p_racket_geom* per_shape, int32_t num_shapes);
 
 /* measurement: HIP events around every launch of the physics kernel (the dominant kernel of the step), recorded on the launch stream
  * by v2p_env_step / v2p_env_physics between _begin and _end (at most max_launches of them).  _end synchronises the events and returns

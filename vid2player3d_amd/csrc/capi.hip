@@ -614,6 +614,7 @@ void v2p_env_destroy(v2p_env* e) {
     if (e->job_progress) (void)hipFree(e->job_progress);
     if (e->job_hand) (void)hipFree(e->job_hand);
     if (e->ball && e->ball->contact_part) (void)hipFree(e->ball->contact_part);
+    if (e->ball && e->ball->rackets) (void)hipFree((void*)e->ball->rackets);
     delete e->ball;
     if (e->err_host) { (void)hipHostFree(e->err_host); (void)hipEventDestroy(e->err_event); }
     profile_free(e);
@@ -777,10 +778,10 @@ int v2p_env_attach_ball(v2p_env* e, const v2p_ball_cfg* c, const v2p_ball_buffer
     d.radius = c->radius; d.mass = c->mass; d.inv_mass = 1.f / c->mass; d.inv_inertia = 1.f / c->inertia;
     d.rest_ground = c->restitution_ground; d.fric_ground = c->friction_ground; d.rest_racket = c->restitution_racket; d.fric_racket = c->friction_racket;
     d.bounce_thr = c->bounce_threshold_velocity; d.ang_damp = c->angular_damping; d.max_ang_vel = c->max_angular_velocity; d.spin_scale = c->spin_scale;
-    d.racket_link = c->racket_link; d.ncyl = c->num_cylinders; d.enabled = 1;
+    d.racket.racket_link = c->racket_link; d.racket.ncyl = c->num_cylinders;
+    memcpy(d.racket.cyl, c->cylinders, sizeof(d.racket.cyl));
+    memcpy(d.racket.racket_off, c->racket_offset, sizeof(d.racket.racket_off));
     d.sub_per_sim = e->substeps_per_sim;
-    memcpy(d.cyl, c->cylinders, sizeof(d.cyl));
-    memcpy(d.racket_off, c->racket_offset, sizeof(d.racket_off));
     d.state = b->ball_state; d.racket_state = b->racket_state; d.per_sim = b->ball_per_sim; d.hit_per_sim = b->racket_hit_per_sim; d.contact = b->ball_contact;
     d.rest_body = c->restitution_body; d.fric_body = c->friction_body; d.body_contacts = c->body_contacts ? 1 : 0;
     d.bounce_height = c->bounce_height; d.poll_hits = c->poll_racket_hits ? 1 : 0;
@@ -793,9 +794,38 @@ int v2p_env_attach_ball(v2p_env* e, const v2p_ball_cfg* c, const v2p_ball_buffer
         int rc = check_hip(hipMalloc((void**)&d.contact_part, sizeof(float) * (size_t)e->n * nsim * NB * 3), "hipMalloc(contact_part)");
         if (rc != V2P_OK) return rc;
     }
+    {   // every shape carries the cfg's racket until v2p_env_set_racket_shapes says otherwise
+        const std::vector<RacketDev> all((size_t)e->num_shapes, d.racket);
+        int rc = V2P_OK;
+        if (!d.rackets) rc = check_hip(hipMalloc((void**)&d.rackets, sizeof(RacketDev) * all.size()), "hipMalloc(rackets)");
+        if (rc == V2P_OK) rc = check_hip(hipMemcpy((void*)d.rackets, all.data(), sizeof(RacketDev) * all.size(), hipMemcpyHostToDevice), "hipMemcpy(rackets)");
+        if (rc != V2P_OK) return rc;
+    }
     if (e->pair_mix_default) e->pair_mix_permille = 0;
     if (e->job_mono_default) e->job_mono_permille = 250;
     return V2P_OK;
+}
+
+int v2p_env_set_racket_shapes(v2p_env* e, const v2p_racket_geom* per_shape, int32_t num_shapes) {
+    if (!e || !per_shape) { set_error("v2p_env_set_racket_shapes: null argument"); return V2P_ERR_INVALID; }
+    if (num_shapes != e->num_shapes) {
+        set_error("v2p_env_set_racket_shapes: %d rackets for a batch of %d body shapes", num_shapes, e->num_shapes);
+        return V2P_ERR_INVALID;
+    }
+    std::vector<RacketDev> all((size_t)num_shapes);
+    for (int32_t k = 0; k < num_shapes; ++k) {
+        const v2p_racket_geom& g = per_shape[k];
+        if (g.racket_link < 1 || g.racket_link >= NB || g.num_cylinders < 0 || g.num_cylinders > 2) {
+            set_error("v2p_env_set_racket_shapes: shape %d: racket_link %d (must be 1 .. %d) / num_cylinders %d (must be 0 .. 2)", k, g.racket_link, NB - 1, g.num_cylinders);
+            return V2P_ERR_INVALID;
+        }
+        all[k].racket_link = g.racket_link; all[k].ncyl = g.num_cylinders;
+        memcpy(all[k].cyl, g.cylinders, sizeof(all[k].cyl));
+        memcpy(all[k].racket_off, g.racket_offset, sizeof(all[k].racket_off));
+    }
+    if (!e->ball || !e->ball->rackets) { set_error("v2p_env_set_racket_shapes: no ball attached (call v2p_env_attach_ball first)"); return V2P_ERR_INVALID; }
+    DeviceGuard g(e->device);
+    return check_hip(hipMemcpy((void*)e->ball->rackets, all.data(), sizeof(RacketDev) * all.size(), hipMemcpyHostToDevice), "hipMemcpy(rackets)");
 }
 
 int v2p_env_check(v2p_env* e, void* stream) {

@@ -1,6 +1,8 @@
 // Declarations shared by the two physics kernels (physics.hip: one env per lane, LDS resident;
 // physics_ll.hip: one link per lane, register resident).
 #pragma once
+#include <stddef.h>
+
 #include "phys_math.hpp"
 #include "v2p_internal.hpp"
 
@@ -17,12 +19,20 @@ constexpr int LINK_SLOTS = 50;
 constexpr int WS_SLOTS = LINK_SLOTS * NB;
 
 
+// the racket of one body shape: the kernels read an env's racket through its shape (BallDev::rackets), like its hulls and joint ranges
+struct RacketDev {
+    int32_t racket_link, ncyl;
+    float cyl[2][8];       // centre 3, unit axis 3, half length, radius; in the racket link's frame
+    float racket_off[3];   // origin of the exported racket rigid body in the link's frame
+};
+typedef const RacketDev __attribute__((address_space(4))) ConstRacket;
+
 // racket + ball (v2p_env_attach_ball): parameters by value, buffers borrowed from the caller
 struct BallDev {
     float radius, mass, inv_mass, inv_inertia, rest_ground, fric_ground, rest_racket, fric_racket, bounce_thr, ang_damp, max_ang_vel, spin_scale;
-    int32_t racket_link, ncyl, sub_per_sim, enabled;
-    float cyl[2][8];       // centre 3, unit axis 3, half length, radius; in the racket link's frame
-    float racket_off[3];   // origin of the exported racket rigid body in the link's frame
+    RacketDev racket;         // v2p_ball_cfg's racket (host side): every shape's until v2p_env_set_racket_shapes
+    int32_t sub_per_sim;
+    const RacketDev* rackets; // [num_shapes] device: the racket of each body shape
     float* state;          // [N,13] ball root state (pos quat vel angvel), read at the start of a step, written at its end
     float* racket_state;   // [N,13] rigid-body state of the racket (rigid body 24 of the reference's tensor)
     float* per_sim;        // [N,nsim,13] ball state after each simulate() call
@@ -36,6 +46,9 @@ struct BallDev {
     float* contact_sum;    // [N,24,3] or NULL: net contact forces of the links summed over the simulate() calls of the control step
     float* contact_part;   // [N,nsim,24,3] engine-owned (with contact_sum): the net contact forces after each simulate() call, one slot per call
 };
+// (the size of PhysArgs, and with it the offsets of the hidden kernel arguments behind it that every instantiation reads, stays what it
+// was before the per-shape rackets: the kernels without a ball compile to the same code)
+static_assert(offsetof(BallDev, state) == 144, "BallDev layout");
 
 // post-physics fused into the physics launch (v2p_env_step, link-per-lane schedule): what env_post_kernel takes
 struct PostArgs {

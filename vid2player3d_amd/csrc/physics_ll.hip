@@ -638,6 +638,14 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
 
     if (valid && b != 0) park_put3(PARK_TAR, tar);  // constant for the whole launch (the columns of lanes 0 and 25 hold the wrench there)
     const BallDev& BP = a.ball;
+    // this env's racket, through its shape (BALL only).  (MULTI: the address is formed where it is used, from sid - live anyway - instead
+    // of being kept in a register pair across the substep loop: that pair cost the per-env-shape ball kernels 16 B of scratch per lane)
+    auto racket = [&]() -> ConstRacket* {
+        int s = sid;
+        if constexpr (MULTI) asm volatile("" : "+v"(s));
+        return (ConstRacket*)BP.rackets + s;
+    };
+    const bool racket_lane = BALL && lb == racket()->racket_link;  // this lane's link carries the env's racket
     const bool ball_lane = BALL && lb == NB;  // the first idle lane of the env carries the ball
     if (ball_lane) {
         // (JOBS: state and aerodynamic force - held over a simulate() call - come from the job of the substep before: chunks 50 .. 53)
@@ -709,7 +717,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         // more than its pose and velocity: further down, next to the link's inertia blocks, their temporaries did not fit)
         if (BALL) {
             // pose and (start-of-substep) velocity of the racket's link, handed to the ball lane of the same env
-            const int src = base + BP.racket_link;
+            const int src = base + racket()->racket_link;
             const Q4 wq = pull(q, src);
             const V3 wx = pull(x, src), ww = pull(w, src), wxd = pull(xd, src);
             if (ball_lane) {
@@ -761,13 +769,14 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 }
                 // ---- ball x the racket's solid cylinders: closest point, normal from the cylinder to the ball
                 const M3 Rw = q2mat(wq);
+                ConstRacket* const RS = racket();
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     lds_vfloat* rk = bl + BL_RK + 16 * j;
                     bool on = false;
-                    if (CONTACT && j < BP.ncyl) {
-                        const V3 cw = wx + mul(Rw, V3{BP.cyl[j][0], BP.cyl[j][1], BP.cyl[j][2]}), aw = mul(Rw, V3{BP.cyl[j][3], BP.cyl[j][4], BP.cyl[j][5]});
-                        const float hl = BP.cyl[j][6], rc = BP.cyl[j][7];
+                    if (CONTACT && j < RS->ncyl) {
+                        const V3 cw = wx + mul(Rw, V3{RS->cyl[j][0], RS->cyl[j][1], RS->cyl[j][2]}), aw = mul(Rw, V3{RS->cyl[j][3], RS->cyl[j][4], RS->cyl[j][5]});
+                        const float hl = RS->cyl[j][6], rc = RS->cyl[j][7];
                         const V3 d = bp - cw;
                         const float t = dot(d, aw);
                         const V3 qv = d - t * aw;
@@ -797,7 +806,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 bool near = false;
                 V3 cb{0.f, 0.f, 0.f};
                 const M3 R = q2mat(q);
-                if (valid && lb != BP.racket_link) {
+                if (valid && !racket_lane) {
                     cb = mulT(R, bp - x);  // ball centre, body frame
                     const V3 ac{S->aabb_c[bo][0], S->aabb_c[bo][1], S->aabb_c[bo][2]}, ae{S->aabb_e[bo][0], S->aabb_e[bo][1], S->aabb_e[bo][2]};
                     const V3 ex{fmaxf(fabsf(cb.x - ac.x) - ae.x, 0.f), fmaxf(fabsf(cb.y - ac.y) - ae.y, 0.f), fmaxf(fabsf(cb.z - ac.z) - ae.z, 0.f)};
@@ -1246,13 +1255,13 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             }
             // (with a ball: the racket's link joins the touched links while the ball is in contact with a cylinder)
             // (point j of the ball block belongs to this lane's link: j = 0, 1 the racket's cylinders, j = 2 .. 4 the hull points)
-            auto ball_rec_mine = [&](int j) -> bool { return j < 2 ? lb == BP.racket_link : lb == (int)bl[BL_RK + 16 * j + RK_LINK]; };
+            auto ball_rec_mine = [&](int j) -> bool { return j < 2 ? racket_lane : lb == (int)bl[BL_RK + 16 * j + RK_LINK]; };
             bool myhull = false;  // this link's hull carries a ball point
             if (BALL) {
 #pragma unroll
                 for (int j = 2; j < NBREC; ++j) myhull = myhull || (bl[BL_RK + 16 * j + RK_A] != 0.f && lb == (int)bl[BL_RK + 16 * j + RK_LINK]);
             }
-            const bool ballhit = BALL && valid && ((lb == BP.racket_link && (bl[BL_RK + RK_A] != 0.f || bl[BL_RK + 16 + RK_A] != 0.f)) || myhull);
+            const bool ballhit = BALL && valid && ((racket_lane && (bl[BL_RK + RK_A] != 0.f || bl[BL_RK + 16 + RK_A] != 0.f)) || myhull);
             const bool ballground = BALL && ball_lane && bl[BL_GA] != 0.f;
             const unsigned long long tb = __ballot(valid && (cnt > 0 || ballhit));
             const unsigned m0 = (unsigned)tb, m1 = (unsigned)(tb >> 32);
@@ -1899,7 +1908,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             }
         }
         if (BALL) {
-            auto ball_rec_mine_out = [&](int j) -> bool { return j < 2 ? lb == BP.racket_link : lb == (int)bl[BL_RK + 16 * j + RK_LINK]; };
+            auto ball_rec_mine_out = [&](int j) -> bool { return j < 2 ? racket_lane : lb == (int)bl[BL_RK + 16 * j + RK_LINK]; };
             // force on the ball in this substep from the racket (sum over the two cylinders) and from the hull points, world axes
             V3 frk{0.f, 0.f, 0.f}, fbd{0.f, 0.f, 0.f}, fmine{0.f, 0.f, 0.f};  // from the racket, from all hulls, from this lane's hull
             {
@@ -1958,7 +1967,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             }
             if ((last || (BP.contact_sum && sub % BP.sub_per_sim == BP.sub_per_sim - 1)) && valid && live_env && !frozen) {
                 // the reaction on the touched link enters its net contact force below
-                const V3 fr = mask(lb == BP.racket_link, frk) + fmine;
+                const V3 fr = mask(racket_lane, frk) + fmine;
                 park[PARK_W0 * 64] = fr.x; park[(PARK_W0 + 1) * 64] = fr.y; park[(PARK_W0 + 2) * 64] = fr.z;
             }
         }
@@ -2157,8 +2166,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
 #pragma unroll
             for (int k = 0; k < 13; ++k) BP.state[e * 13 + k] = bl[k];
         }
-        if (valid && lb == BP.racket_link) {  // rigid body 24 of the reference's tensor: the racket frame, welded to this link
-            const V3 off = mul(q2mat(q), V3{BP.racket_off[0], BP.racket_off[1], BP.racket_off[2]});
+        if (valid && racket_lane) {  // rigid body 24 of the reference's tensor: the racket frame, welded to this link
+            ConstRacket* const RS = racket();
+            const V3 off = mul(q2mat(q), V3{RS->racket_off[0], RS->racket_off[1], RS->racket_off[2]});
             const V3 rx = x + off, rv = xd + cross(w, off);
             float* o = BP.racket_state + e * 13;
             o[0] = rx.x; o[1] = rx.y; o[2] = rx.z; o[3] = q.x; o[4] = q.y; o[5] = q.z; o[6] = q.w;

@@ -24,6 +24,46 @@ from .humanoid_smpl_im import HumanoidSMPLIM
 BALL_R = racket.BALL["radius"]
 
 
+def pair_players(v2p, env):
+    """The two players of cfg_v2p `dual_mode: different` (names of racket.PLAYERS): `player: [p0, p1]`, or - names absent - `righthand:
+    [r0, r1]`, each entry djokovic (True) or nadal (False) like the single-player path.  Given both, they must agree."""
+    if int(env["numEnvs"]) % 2:
+        raise ValueError("dual_mode 'different' alternates the two players over the envs (env i = player i %% 2): numEnvs must be even, got %d" % int(env["numEnvs"]))
+    if "player" in env:
+        raise ValueError("cfg env.player selects ONE player; with dual_mode 'different' the pair comes from v2p.player / v2p.righthand")
+    names, hands = v2p.get("player"), v2p.get("righthand")
+    for key, val in (("player", names), ("righthand", hands)):
+        if val is not None and (isinstance(val, (str, bool)) or len(val) != 2):
+            raise ValueError("dual_mode 'different': v2p.%s must be a list of 2 entries (one per player), got %r" % (key, val))
+    if names is None:
+        if hands is None:
+            raise ValueError("dual_mode 'different' needs v2p.player = [p0, p1] or v2p.righthand = [r0, r1]")
+        names = ["djokovic" if bool(r) else "nadal" for r in hands]
+    names = [str(p) for p in names]
+    for p in names:
+        if p not in racket.PLAYERS:
+            raise ValueError("unknown player %r (known: %s)" % (p, ", ".join(sorted(racket.PLAYERS))))
+    if hands is not None:
+        for p, r in zip(names, hands):
+            if bool(r) != (racket.PLAYERS[p]["parent"] == "R_Wrist"):
+                raise ValueError("v2p.righthand %r disagrees with player %s" % (list(hands), p))
+    return names
+
+
+def _fill_racket(dst, g):
+    """cylinders / racket_offset / (racket_link, num_cylinders) of a racket geometry dict into a BallCfg or a RacketGeom."""
+    dst.racket_link, dst.num_cylinders = int(g["racket_link"]), len(g["cylinders"])
+    for k, cy in enumerate(g["cylinders"]):
+        dst.cylinders[k][:] = [float(x) for x in list(cy["center"]) + list(cy["axis"]) + [cy["half_len"], cy["radius"]]]
+    dst.racket_offset[:] = [float(x) for x in g["racket_offset"]]
+
+
+def racket_geom_struct(g):
+    r = _lib.RacketGeom()
+    _fill_racket(r, g)
+    return r
+
+
 class HumanoidSMPLIMRacketBall(HumanoidSMPLIM):
     def __init__(self, cfg, sim_params=None, physics_engine=None, device_type="cuda", device_id=0, headless=True):
         # (work on a copy: the caller's cfg stays what it was, a second task built from it starts from the plain body model again)
@@ -39,14 +79,31 @@ class HumanoidSMPLIMRacketBall(HumanoidSMPLIM):
         # like the reference (humanoid_smpl_im_mvae.py:73-78).  The exposed rigid-body order is the canonical one either way (racket =
         # rigid body 24: the reference permutes the left-handed asset's tensor into it, :67, 197-201).
         v2p = dict(cfg.get("v2p") or {})
-        player = env.get("player", "djokovic" if v2p.get("righthand", True) else "nadal")
-        if isinstance(base, (list, tuple)):
-            # one body shape per clip: the racket is the same object in every hand - welded at the same offset of the wrist frame - so
-            # every shape gets it folded in, and the ball's cylinders (given in the wrist frame) are shared
-            folded = [racket.with_racket(b, player=player) for b in base]
-            model, self.racket_geometry = [m for m, _ in folded], folded[0][1]
+        # two players (the match configs nadal_federer.yaml / federer_djokovic.yaml: dual_mode `different`): env i is player i % 2
+        # (humanoid_smpl_im_mvae.py:255-270, [::2] / [1::2]), each with its own asset - racket hand and arm ranges folded into one body
+        # shape per player; other dual_mode values share one asset in the reference and take the single-player path
+        self.racket_players = pair_players(v2p, env) if v2p.get("dual_mode") == "different" else None
+        if self.racket_players is not None:
+            if isinstance(base, (list, tuple)):
+                raise NotImplementedError("dual_mode 'different' with per-clip body shapes (a body_model list) is not built: give one BodyModel, "
+                                          "or v2p.player_body_models = [BodyModel, BodyModel] for the two players")
+            bases = v2p.get("player_body_models") or [base, base]
+            if len(bases) != 2:
+                raise ValueError("v2p.player_body_models must hold 2 body models (one per player), got %d" % len(bases))
+            # (two shapes even for two equal players: the batch runs the per-env-shape kernel either way)
+            folded = [racket.with_racket(b, player=p) for b, p in zip(bases, self.racket_players)]
+            model, self.racket_geometries = [m for m, _ in folded], [g for _, g in folded]
         else:
-            model, self.racket_geometry = racket.with_racket(base, player=player)
+            player = env.get("player", "djokovic" if v2p.get("righthand", True) else "nadal")
+            if isinstance(base, (list, tuple)):
+                # one body shape per clip: the racket is the same object in every hand - welded at the same offset of the wrist frame - so
+                # every shape gets it folded in, and the ball's cylinders (given in the wrist frame) are shared
+                folded = [racket.with_racket(b, player=player) for b in base]
+                model, self.racket_geometries = [m for m, _ in folded], [folded[0][1]]
+            else:
+                model, geom = racket.with_racket(base, player=player)
+                self.racket_geometries = [geom]
+        self.racket_geometry = self.racket_geometries[0]  # (player 0's)
         env["body_model"] = model
         # the player MJCF's racket-arm ranges (R_Wrist +-10 / +-45 / +-90 deg, R_Elbow_x <= 90 deg) are enforced like Isaac Gym does
         env.setdefault("joint_limits", True)
@@ -86,12 +143,9 @@ class HumanoidSMPLIMRacketBall(HumanoidSMPLIM):
                          restitution_ground=mat["rest_ground"], friction_ground=mat["fric_ground"], restitution_racket=mat["rest_racket"],
                          friction_racket=mat["fric_racket"], bounce_threshold_velocity=self.sim_params.physx.bounce_threshold_velocity,
                          angular_damping=mat["ang_damp"], max_angular_velocity=mat["max_ang_vel"], spin_scale=self.cfg_v2p.get("spin_scale", 1.0),
-                         racket_link=g["racket_link"], num_cylinders=len(g["cylinders"]),
                          restitution_body=mat["rest_body"], friction_body=mat["fric_body"], body_contacts=int(env.get("ball_body_contacts", True)),
                          bounce_height=BALL_R * (6 if self.sim_params.substeps > 2 else 4), poll_racket_hits=int(self.sim_params.substeps <= 2))
-        for k, cy in enumerate(g["cylinders"]):
-            c.cylinders[k][:] = [float(x) for x in list(cy["center"]) + list(cy["axis"]) + [cy["half_len"], cy["radius"]]]
-        c.racket_offset[:] = [float(x) for x in g["racket_offset"]]
+        _fill_racket(c, g)
         b = _lib.BallBuffers(ball_state=self._ball_root_states.data_ptr(), racket_state=self._racket_rb_state.data_ptr(),
                              ball_per_sim=self._ball_states_per_sim.data_ptr(), racket_hit_per_sim=self._racket_ball_contact_per_sim.data_ptr(),
                              ball_contact=self._ball_contact_forces.data_ptr(), ball_body_contact=self._ball_body_contact_force.data_ptr(),
@@ -99,7 +153,44 @@ class HumanoidSMPLIMRacketBall(HumanoidSMPLIM):
                              has_racket_contact=self._has_racket_ball_contact.data_ptr(), has_racket_contact_now=self._has_racket_ball_contact_now.data_ptr(),
                              contact_force_sum=None if self._contact_forces_sum is None else self._contact_forces_sum.data_ptr())
         _lib.check(self._lib.v2p_env_attach_ball(self._h_env, C.byref(c), C.byref(b)), "v2p_env_attach_ball")
+        if self.racket_players is not None:
+            geoms = (_lib.RacketGeom * 2)(*[racket_geom_struct(g) for g in self.racket_geometries])
+            _lib.check(self._lib.v2p_env_set_racket_shapes(self._h_env, geoms, 2), "v2p_env_set_racket_shapes")
+        # the reference's per-env racket attributes (humanoid_smpl_im_mvae.py:68-82): the link the racket is welded to, and which player of
+        # a pair is left-handed (-1: the single player is; None: no left hand)
+        links = [g["racket_link"] for g in self.racket_geometries]
+        if self.racket_players is None:
+            self._racket_wrist_body_id = links[0]
+            self._lefthand = -1 if racket.PLAYERS[self.racket_geometry["player"]]["parent"] == "L_Wrist" else None
+        else:
+            self._racket_wrist_body_id = torch.tensor(links, dtype=torch.long, device=dev).repeat(n // 2)
+            left = [racket.PLAYERS[p]["parent"] == "L_Wrist" for p in self.racket_players]
+            self._lefthand = left.index(True) if any(left) else None
         self.ball_material = mat
+
+    # ------------------------------------------------------------------ two players: shapes by env, not by clip
+    def _env_body_shapes(self, env):
+        if self.racket_players is None:
+            return super()._env_body_shapes(env)
+        return (np.arange(self.num_envs) % 2).astype(np.int32)
+
+    def _players_share_the_clips(self, fn, env):
+        # the motion library is built for (and checked against) player 0's skeleton, never clip by clip for the two player shapes
+        shapes, self.body_shapes = self.body_shapes, None
+        try:
+            return fn(env)
+        finally:
+            self.body_shapes = shapes
+
+    def _load_motion(self, env):
+        if self.racket_players is None:
+            return super()._load_motion(env)
+        return self._players_share_the_clips(super()._load_motion, env)
+
+    def _check_body_shapes(self, env):
+        if self.racket_players is None:
+            return super()._check_body_shapes(env)
+        return self._players_share_the_clips(super()._check_body_shapes, env)
 
     # ------------------------------------------------------------------ the reference's flag bookkeeping around the physics step
     def reset_balls(self, env_ids, launch_pos, launch_vel, launch_ang_vel):

@@ -287,13 +287,8 @@ class HumanoidSMPLIM:
         for val, bodies in env.get("body_pos_weights", dict()).items():
             for body in bodies:
                 self.body_pos_weights[self.body_names.index(body)] = val
-        # per-env shape (index into body_shapes) = shape of the env's clip
-        self._env_shape_ids = None
-        if self.body_shapes is not None and len(self.body_shapes) > 1:
-            m2s = np.asarray(env.get("motion_shape_ids", np.arange(self._motion_lib.num_motions())), dtype=np.int64)
-            if len(m2s) != self._motion_lib.num_motions() or m2s.min() < 0 or m2s.max() >= len(self.body_shapes):
-                raise ValueError("motion_shape_ids must map each of the %d clips to one of the %d body shapes" % (self._motion_lib.num_motions(), len(self.body_shapes)))
-            self._env_shape_ids = m2s[self._reset_ref_motion_ids.cpu().numpy()].astype(np.int32)
+        self._env_shape_ids = self._env_body_shapes(env)
+        if self._env_shape_ids is not None:
             self.humanoid_masses = np.array([self.body_shapes[k].total_mass for k in self._env_shape_ids])
         last = self.body_model if self._env_shape_ids is None else self.body_shapes[self._env_shape_ids[-1]]
         # (the reference keeps the gains of the LAST env it built, :382-383)
@@ -341,6 +336,15 @@ class HumanoidSMPLIM:
         self.actions = None
 
     # ------------------------------------------------------------------ construction helpers
+    def _env_body_shapes(self, env):
+        """Index into body_shapes of every env (int32 [num_envs]), None for a batch of one shape: the shape of the env's clip."""
+        if self.body_shapes is None or len(self.body_shapes) < 2:
+            return None
+        m2s = np.asarray(env.get("motion_shape_ids", np.arange(self._motion_lib.num_motions())), dtype=np.int64)
+        if len(m2s) != self._motion_lib.num_motions() or m2s.min() < 0 or m2s.max() >= len(self.body_shapes):
+            raise ValueError("motion_shape_ids must map each of the %d clips to one of the %d body shapes" % (self._motion_lib.num_motions(), len(self.body_shapes)))
+        return m2s[self._reset_ref_motion_ids.cpu().numpy()].astype(np.int32)
+
     def _check_body_shapes(self, env):
         """The reference builds one humanoid asset per sampled clip from the clip's betas (humanoid_smpl_im.py:247-296).  A library whose
         clips carry different betas, simulated with ONE body model, gives targets / observations / termination heights of per-beta
