@@ -1,14 +1,15 @@
 #!/bin/bash
 # For one physics_ll_kernel instantiation: every scratch STORE with the source line of the instruction that defined the stored register, and the
-# scratch LOADS by frame offset (which spilled value is reloaded how often, statically).  usage: tools/spill_defs.sh <8 template flags> [extra flags]
+# scratch LOADS by frame offset (which spilled value is reloaded how often, statically).  usage: tools/spill_defs.sh [--regs] <8 template flags> [extra flags]
+S=physics_ll.hip; if [ "$1" = "--regs" ]; then shift; S=physics_ll.hip:regs; fi
 T=$1; shift
-cd "$(dirname "$0")/../vid2player3d_amd/csrc"
+cd "$(dirname "$0")/.."; FLAGS=$(python -m vid2player3d_amd.build --print-flags $S); cd vid2player3d_amd/csrc
 M=$(echo $T | sed 's/./Lb&E/g')
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast-honor-pragmas -fno-vectorize -fno-slp-vectorize -fassociative-math -freciprocal-math -fno-signed-zeros -fno-trapping-math -fno-honor-nans -mllvm -sink-insts-to-avoid-spills=1 "$@" -gline-tables-only --cuda-device-only -S physics_ll.hip -o /tmp/spilld_$$.s 2>/dev/null
-python3 - /tmp/spilld_$$.s "_ZN3v2p17physics_ll_kernelI${M}EEvNS_8PhysArgsE" <<'PY'
+/opt/rocm/bin/hipcc $FLAGS "$@" -gline-tables-only --cuda-device-only -S physics_ll.hip -o /tmp/spilld_$$.s 2>/dev/null
+python3 - /tmp/spilld_$$.s "physics_ll_kernelI${M}EEvNS_8PhysArgsE" <<'PY'
 import re,sys,collections
 L=open(sys.argv[1]).read().split('\n'); name=sys.argv[2]
-s=next(i for i,l in enumerate(L) if l.startswith(name+':')); e=next(i for i in range(s,len(L)) if L[i].startswith('.Lfunc_end'))
+s=next(i for i,l in enumerate(L) if re.match(r'\w+'+name+':',l)); e=next(i for i in range(s,len(L)) if L[i].startswith('.Lfunc_end'))
 cur=None; lastdef={}; n=0; stores=[]; loads=collections.Counter(); pos=collections.defaultdict(list)
 for i in range(s,e):
     l=L[i]

@@ -7,6 +7,6 @@ IFS='|' read -ra GR <<< "${GROUPS_:-$DEF}"
 i=0
 for grp in "${GR[@]}"; do
 i=$((i+1)); rm -rf $O/pmc_valu_$i
-timeout 600 rocprofv3 --pmc $grp --kernel-trace -d $O/pmc_valu_$i -o pmc -- python $R/bench.py --full --steps 16 --warmup 0 --no-cpu-baseline ${VALU_ARGS:-} > $O/pmc_valu_$i.log 2>&1
+timeout 600 rocprofv3 --pmc $grp --kernel-trace -d $O/pmc_valu_$i -o pmc -- python $R/bench.py --full --steps 16 --warmup 0 --no-cpu-baseline ${VALU_ARGS:-} > $O/pmc_valu_$i.log 2>&1 || { echo "rocprofv3 pass failed (exit $?): see $O/pmc_valu_$i.log"; exit 1; }
 done
 python $R/tools/valu_summary.py $O > $O/${VALU_OUT:-valu_summary.json}; rm -rf $O/pmc_valu_*/; cat $O/${VALU_OUT:-valu_summary.json}

@@ -43,26 +43,11 @@ struct DeviceGuard {
 
 }  // namespace v2p
 
-// The link-per-lane physics kernel is built TWICE from the same source (build.py): the default object (168 VGPRs, three waves per SIMD,
-// contact records and phase-dead values parked in LDS) and `physics_ll_regs.o` (-Dv2p=v2p_regs -DV2P_LL_WPS=2 -DV2P_LL_PARK2=0
-// -DV2P_LL_PARK3=0: 256 VGPRs, two waves per SIMD, everything in registers).  Where a launch is as long as its heaviest env pair - up to
+// The link-per-lane physics kernel is in the library TWICE (physics_ll.hip): the default object (168 VGPRs, three waves per
+// SIMD, contact records and phase-dead values parked in LDS) behind launch_env_physics_ll, and the register build (256 VGPRs, two waves
+// per SIMD, everything in registers) behind launch_env_physics_ll_regs.  Where a launch is as long as its heaviest env pair - up to
 // ~5000 envs on one GPU - the register build is 7 - 12 % faster (no LDS round trips in the heaviest wave's chain; compiled for ILP), where
-// the wave slots are full the LDS build is 15 % faster (profiles/r04e_dual_build.txt).  The second object lives in its own
-// namespace; what it calls from this file is forwarded here.  (-Dv2p=v2p_regs renames the namespace in every header that object
-// includes as well: the types it sees inside `v2p_env` are `v2p_regs::` twins of this file's - same source, same layout, and only the
-// pointer crosses the boundary.)
-namespace v2p_regs {
-void set_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    v2p::set_error("%s", buf);
-}
-int check_hip(hipError_t e, const char* what) { return v2p::check_hip(e, what); }
-int launch_env_physics_ll(v2p_env* e, hipStream_t s, float* actions, int* fused_post);
-}  // namespace v2p_regs
+// the wave slots are full the LDS build is 15 % faster (profiles/r04e_dual_build.txt).
 
 using namespace v2p;
 
@@ -74,7 +59,6 @@ const char* debug_env(const char* name) {
     return (d && d[0] == '1' && d[1] == 0) ? getenv(name) : nullptr;
 }
 }  // namespace v2p
-namespace v2p_regs { const char* debug_env(const char* name) { return v2p::debug_env(name); } }
 
 // envs resident per device (live v2p_env batches of this process): what kernel_build = 0 decides by, launch by launch
 static std::atomic<int64_t> g_resident_envs[64];
@@ -741,7 +725,7 @@ static int physics_launch(v2p_env* e, hipStream_t s, float* actions, int* fused_
     choose_build(e);
     if (rec) (void)hipEventRecord(e->prof_ev[2 * e->prof_n], s);
     int rc = e->schedule != 0 ? launch_env_physics(e, s)
-                              : (e->ll_regs_build ? v2p_regs::launch_env_physics_ll(e, s, actions, fused_post) : launch_env_physics_ll(e, s, actions, fused_post));
+                              : (e->ll_regs_build ? launch_env_physics_ll_regs(e, s, actions, fused_post) : launch_env_physics_ll(e, s, actions, fused_post));
     if (rec) { (void)hipEventRecord(e->prof_ev[2 * e->prof_n + 1], s); ++e->prof_n; }
     return rc;
 }

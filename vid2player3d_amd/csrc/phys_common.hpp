@@ -1,5 +1,6 @@
 // Declarations shared by the two physics kernels (physics.hip: one env per lane, LDS resident;
-// physics_ll.hip: one link per lane, register resident).
+// physics_ll.hip: one link per lane, register resident - compiled twice, the default and the register build, both of
+// which see THESE types) and by physics_ll_host.hip (what of the link-per-lane schedule is compiled once).
 #pragma once
 #include <stddef.h>
 
@@ -112,7 +113,7 @@ struct PhysArgs {
 };
 
 
-// ---- pairing (see physics_ll.hip): slot of env e in the next launch = first slot of its load bin + its arrival index there
+// ---- pairing (see physics_ll_host.hip): slot of env e in the next launch = first slot of its load bin + its arrival index there
 constexpr int PAIR_BINS = 256;
 struct PairView {
     const int32_t* key;    // [N]

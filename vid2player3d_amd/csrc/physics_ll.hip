@@ -53,40 +53,24 @@
 #include "phys_common.hpp"
 #include "hull_gjk.hpp"
 
+// This file is compiled TWICE into libv2p_rollout.so (build.py): the default object (V2P_LL_WPS* = 3, V2P_LL_PARK2 / 3 = 1: 168 VGPRs,
+// three waves per SIMD, contact records and phase-dead values parked in LDS) and, with -DV2P_LL_REGS_BUILD and the knobs set to
+// 2 / 2 / 2 / 0 / 0, the register build (256 VGPRs, two waves per SIMD, everything in registers).  Only the kernel and its
+// launcher carry a per-build name; every shared type is namespace v2p's own, and what does not depend on the build
+// (env_pre_kernel, the pairing table, their launchers) is compiled once in physics_ll_host.hip.
+#if defined(V2P_LL_REGS_BUILD)
+#define V2P_LL_NS ll_regs
+#define V2P_LL_LAUNCHER launch_env_physics_ll_regs
+#else
+#define V2P_LL_NS ll_lds
+#define V2P_LL_LAUNCHER launch_env_physics_ll
+#endif
+
 namespace v2p {
 
-// Pre-physics (humanoid_smpl_im.py:125-157, 391-396) restates the reference's torch arithmetic: PD-target clamp, residual root wrench
-// rotated into the heading frame.  ONE implementation, compiled here with precise semantics and without contraction (the pragma
-// below; this file is built -ffp-contract=fast-honor-pragmas), serves both the stand-alone env_pre_kernel and the prologue of the
-// physics kernel, so the fused step equals the staged step bit for bit (tests).
-namespace strict {
-#pragma clang fp reassociate(off) reciprocal(off) contract(off)
-#include "v2p_math.inc"
-#include "motion_sample.inc"
-#include "post_ops.inc"
-// sum of 24 consecutive floats, ascending (the order env_post_kernel adds the bodies' reward terms in)
-__device__ __forceinline__ float sum_bodies(const float* p) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NB; ++i) s += p[i];
-    return s;
-}
-__device__ __forceinline__ float pd_clamp(float act, float q, float lim) { return fmaxf(fminf(act, q + lim), q - lim); }
-// root_rot: rigid-body rotation of the root (xyzw); a3: the three action components of the force (or torque) part
-__device__ __forceinline__ V3 residual_wrench(const float* root_rot, float a0, float a1, float a2, float scale) {
-    const Q4 hq = ref_heading_quat(ref_calc_heading(ref_remove_base_rot(Q4{root_rot[0], root_rot[1], root_rot[2], root_rot[3]})));
-    return ref_quat_rotate(hq, V3{a0 * scale, a1 * scale, a2 * scale});
-}
-// force and torque at once: one heading quaternion (the same functions of the same arguments: the same bits as two calls)
-__device__ __forceinline__ void residual_wrench2(const float* root_rot, const float* a6, float fscale, float tscale, V3& F, V3& T) {
-    const Q4 hq = ref_heading_quat(ref_calc_heading(ref_remove_base_rot(Q4{root_rot[0], root_rot[1], root_rot[2], root_rot[3]})));
-    F = ref_quat_rotate(hq, V3{a6[0] * fscale, a6[1] * fscale, a6[2] * fscale});
-    T = ref_quat_rotate(hq, V3{a6[3] * tscale, a6[4] * tscale, a6[5] * tscale});
-}
-}  // namespace strict
-#if !defined(V2P_LL_STRICT_MATH)
-#pragma clang fp reassociate(on) reciprocal(on) contract(fast)  // (a file-scope fp pragma stays in force past the namespace: switch back)
-#endif
+// namespace strict: the pre- / post-physics arithmetic that restates the reference, compiled precise and without contraction; shared
+// with the stand-alone env_pre_kernel (physics_ll_host.hip), so the fused step equals the staged step bit for bit (tests)
+#include "strict_ops.inc"
 
 typedef volatile __attribute__((address_space(3))) float lds_vfloat;  // a volatile float in LDS (ds_read / ds_write, 32-bit address + immediate offset)
 constexpr int LPE = 32;  // lanes per environment
@@ -203,6 +187,10 @@ __device__ __forceinline__ void grp_argmax(float& v, int& k) {
 #define LLSUB(k) do { if (DIAG && a.prof) { long long t_ = clock64(); if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t_ - tsub)); tsub = t_; } } while (0)
 #define LLPH(k) do { if (DIAG && a.prof) { long long t_ = clock64(); if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t_ - tprev)); tprev = t_; } } while (0)
 
+// Everything from here to the end of the kernel depends on the build (register budget, what is parked in LDS and with it the LDS
+// layout): it lives in a namespace of its own per build, which also keeps the two objects' kernels (and their host stubs) apart for
+// the linker and in a kernel trace.  Inline: the launcher below names them unqualified.
+inline namespace V2P_LL_NS {
 // (V2P_LL_WPB, waves per workgroup, is defined in v2p_internal.hpp: the host sizes the progress words with it)
 #ifndef V2P_LL_WPS
 #define V2P_LL_WPS 3   // waves per SIMD the register budget is set for (168 VGPRs; 2 = 256 VGPRs with everything in registers)
@@ -2236,72 +2224,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     }
     timeline();
 }
+}  // namespace V2P_LL_NS
 
-// ---- pairing: a wave costs the union of its two envs' contact structure, so envs are handed to waves in descending order of
-// their contact load (heavy waves first also keeps the tail of the launch short; the heaviest quarter each next to one of the lightest).
-// A counting sort without a sorting kernel: every env draws an arrival index in its load bin at the end of the physics kernel (atomics)
-// and appends itself to the bin's arrival list, the workgroup that finishes last scans the 256 bin counts, and the next launch looks
-// its envs up (prologue of physics_ll_kernel).  The order inside a bin depends on arrival, which is harmless: an env's arithmetic does
-// not depend on the env it shares a wave with (tests: bit-identical results).  The explicit slot -> env table below is built on
-// demand only (v2p_env_debug_pairing).
-__global__ void pair_scatter_kernel(PairView pv, int64_t n) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n) pair_scatter(pv, e);
-}
-
-// ---- stand-alone pre-physics (the staged API, v2p_env_pre_physics): one thread per action component
-__global__ void env_pre_kernel(PhysArgs a, PairView pv) {
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t e = tid / NACT;
-    const int c = (int)(tid - e * NACT);
-    if (e >= a.n) return;
-    if (c == 0 && pv.perm) pair_scatter(pv, e);
-    const bool dead = a.reset[e] == 1;
-    float act = a.actions[tid];
-    if (dead) { act = 0.f; a.actions[tid] = 0.f; }  // in place on the caller's tensor, like the reference
-    if (c < NDOF) {
-        const float tar = strict::pd_clamp(act, a.x_dof[(e * NDOF + c) * 2], a.p.pd_tar_lim);
-        a.pd_target[e * NDOF + c] = tar;
-        a.ctrl[CIDX(CT_PD + c)] = tar;
-    } else if (c == NDOF || c == NDOF + 3) {
-        const float a1 = dead ? 0.f : a.actions[tid + 1], a2 = dead ? 0.f : a.actions[tid + 2];
-        const strict::V3 w = strict::residual_wrench(a.x_rb + e * NB * 13 + 3, act, a1, a2, c == NDOF ? a.p.res_force_scale : a.p.res_torque_scale);
-        const int base = c == NDOF ? CT_FORCE : CT_TORQUE;
-        a.ctrl[CIDX(base + 0)] = w.x; a.ctrl[CIDX(base + 1)] = w.y; a.ctrl[CIDX(base + 2)] = w.z;
-    }
-}
-
-int launch_env_pre(v2p_env* env, float* actions, hipStream_t s) {
-    PhysArgs a = {};
-    a.ctrl = env->ctrl;
-    a.actions = actions;
-    a.reset = env->buf.reset;
-    a.pd_target = env->buf.pd_target;
-    a.x_dof = env->buf.dof_state;
-    a.x_rb = env->buf.rb_state;
-    a.n = env->n;
-    a.p = env->p;
-    PairView pv{nullptr, nullptr, nullptr, nullptr, 0, 0};  // (the physics kernel looks its envs up itself: nothing to scatter here)
-    const int64_t threads = env->n * NACT;
-    hipLaunchKernelGGL(env_pre_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a, pv);
-    return check_hip(hipGetLastError(), "env_pre_kernel");
-}
-
-bool env_pairing_on(const v2p_env* env) { return env->pair_period > 0 && env->schedule == 0 && env->p.enable_contact && env->n > 2; }
-
-PairView env_pair_view(const v2p_env* env) {
-    int mix = (int)(env->n * (int64_t)env->pair_mix_permille / 1000);
-    if (2 * mix > env->n) mix = (int)(env->n / 2);
-    return PairView{env->pair_key, env->pair_pos, env->pair_start, env->perm, (int32_t)env->n, mix};
-}
-
-int launch_env_pairing(v2p_env* env, hipStream_t s) {
-    // (v2p_env_debug_pairing only: the wave order the next launch will look up, as an explicit slot -> env table)
-    hipLaunchKernelGGL(pair_scatter_kernel, dim3((unsigned)((env->n + 255) / 256)), dim3(256), 0, s, env_pair_view(env), env->n);
-    return check_hip(hipGetLastError(), "pair_scatter_kernel");
-}
-
-int launch_env_physics_ll(v2p_env* env, hipStream_t s, float* actions, int* fused_post) {
+int V2P_LL_LAUNCHER(v2p_env* env, hipStream_t s, float* actions, int* fused_post) {
     if (fused_post) *fused_post = 0;
     const bool paired = env_pairing_on(env);
     PhysArgs a = {};

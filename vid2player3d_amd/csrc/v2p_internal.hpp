@@ -255,6 +255,8 @@ int launch_env_pre(v2p_env* e, float* actions, hipStream_t s);
 int launch_env_physics(v2p_env* e, hipStream_t s);
 // actions: fuse pre-physics into the kernel; fused_post (with actions): non-null = post-physics may be fused in as well, *fused_post says whether it was
 int launch_env_physics_ll(v2p_env* e, hipStream_t s, float* actions = nullptr, int* fused_post = nullptr);
+// the same kernel in the library's register build (physics_ll.hip compiled a second time: two waves per SIMD, nothing parked in LDS)
+int launch_env_physics_ll_regs(v2p_env* e, hipStream_t s, float* actions = nullptr, int* fused_post = nullptr);
 bool env_pairing_on(const v2p_env* e);
 struct PairView;
 PairView env_pair_view(const v2p_env* e);
