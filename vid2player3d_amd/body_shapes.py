@@ -24,7 +24,7 @@ import numpy as np
 from .model import BodyModel
 
 GEOM_DENSITY = 900.0  # smpl_mesh_humanoid_amass_v1.xml:50-... (every geom)
-MAX_HULL_VERTS = 64   # per body, the engine's limit (csrc/capi.hip v2p_model_create)
+MAX_HULL_VERTS = 64   # per body, the engine's limit (csrc/model_compile.hip, v2p_model_create)
 
 
 def convex_hull(points, eps_rel=1e-10):

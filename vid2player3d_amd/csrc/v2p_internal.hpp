@@ -1,7 +1,10 @@
 // Internal (non-ABI) declarations shared by the translation units of libv2p_rollout.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include <vector>
 
 #include "../../include/v2p_rollout.h"
 
@@ -80,12 +83,69 @@ struct CtxTransform {
     const float* draws;  // [N][W][24][5]: u_noise, z.xyz, u_drop
 };
 
+void set_error(const char* fmt, ...);
+int check_hip(hipError_t e, const char* what);
+
+// makes `dev` the calling thread's device for the length of a scope (capi.hip)
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev);
+    ~DeviceGuard();
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+// The ONE owner of what a batch (or a body model) allocates on its device: device buffers, pinned host memory, events (device_owner.hip).
+// Every call allocates, fills, records the pointer and returns the V2P_* code; a call that fails holds nothing and leaves *p as it was.
+// What the owner holds is released under its own DeviceGuard when it is destroyed: the typed pointer fields of v2p_env, v2p_model and
+// BallDev, which PhysArgs and the launchers read, only borrow.  `name` is what the error message calls the buffer: "hipMalloc(<name>): ...".
+class DeviceOwner {
+public:
+    enum Fill { NO_FILL, FILL_00, FILL_FF };
+    int device = 0;
+    DeviceOwner() = default;
+    ~DeviceOwner();
+    DeviceOwner(const DeviceOwner&) = delete;
+    DeviceOwner& operator=(const DeviceOwner&) = delete;
+    // `count` elements of device memory, every byte filled, or (host != NULL) copied from `count` elements of a host array
+    template <class T>
+    int alloc(T** p, size_t count, const char* name, Fill fill = NO_FILL, const void* host = nullptr) {
+        void* q = nullptr;
+        const int rc = device_bytes(&q, sizeof(T) * count, name, fill, host);
+        if (rc == V2P_OK) *p = (T*)q;
+        return rc;
+    }
+    template <class T>
+    int alloc_pinned(T** p, size_t count, const char* name) {  // zeroed pinned host memory
+        void* q = nullptr;
+        const int rc = pinned_bytes(&q, sizeof(T) * count, name);
+        if (rc == V2P_OK) *p = (T*)q;
+        return rc;
+    }
+    int events(hipEvent_t** ev, size_t count, unsigned flags, const char* name);  // a host array of `count` events (name NULL: "hipEventCreate")
+    void release(const void* p);  // one holding, ahead of the owner's end (NULL, or nothing the owner holds: no-op)
+
+private:
+    enum Kind { DEVICE, PINNED, EVENTS };
+    struct Item {
+        void* p;
+        size_t count;
+        Kind kind;
+    };
+    std::vector<Item> items;
+    int device_bytes(void** p, size_t bytes, const char* name, Fill fill, const void* host);
+    int pinned_bytes(void** p, size_t bytes, const char* name);
+    static void free_item(const Item& it);
+};
+
 }  // namespace v2p
 
 struct v2p_model {
-    v2p::DevModel host;
-    v2p::DevModel* dev;
-    int device;
+    v2p::DevModel host = {};
+    v2p::DevModel* dev = nullptr;
+    int device = 0;
+    v2p::DeviceOwner own;
 };
 
 struct v2p_mlib {
@@ -125,72 +185,74 @@ struct EnvParams {
 namespace v2p { struct BallDev; }
 
 struct v2p_env {
-    const v2p_model* model;   // shape 0 (the tree tables of every shape are identical)
-    int num_shapes;           // > 1: per-env body shapes
-    v2p::DevShape* shapes_dev;   // [num_shapes] (multi-shape only)
-    int32_t* env_shape_dev;      // [N]
-    float* shape_aug_dev;        // [num_shapes][24]
-    const v2p_mlib* mlib;
-    v2p::EnvParams p;
-    v2p_env_buffers buf;
-    int64_t n;
-    int device;
-    int cur_target;           // index of the current target buffer
-    int schedule;             // 0 = link per lane (physics_ll.hip), 1 = env per lane (physics.hip)
-    const int64_t* motion_id; // [N] device (borrowed)
-    float* state;             // [N][STATE_SLOTS]
-    float* ctrl;              // [N][CTRL_SLOTS]: pd target 69, wrench 6
-    float* out;               // [N][OUT_SLOTS]: physics outputs before export
-    float* ws;                // SoA [WS_SLOTS][N] physics workspace
-    int32_t* contact_ids;     // [N,24,4] debug
-    int32_t* contact_ids_sub; // [N,nsub,24,4] debug, every substep (v2p_sim_cfg.debug_substep_contacts), else NULL
-    long long* prof;          // [8] phase cycle counters when V2P_PHASE_TIMING is set (device), else NULL
-    long long* wave_times;    // [waves][4] per-wave wall-clock stamps of the last launch when V2P_WAVE_TIMES=<file> is set
+    const v2p_model* model = {};   // shape 0 (the tree tables of every shape are identical)
+    int num_shapes = {};           // > 1: per-env body shapes
+    v2p::DevShape* shapes_dev = {};   // [num_shapes] (multi-shape only)
+    int32_t* env_shape_dev = {};      // [N]
+    float* shape_aug_dev = {};        // [num_shapes][24]
+    const v2p_mlib* mlib = {};
+    v2p::EnvParams p = {};
+    v2p_env_buffers buf = {};
+    int64_t n = {};
+    int device = {};
+    int cur_target = {};           // index of the current target buffer
+    int schedule = {};             // 0 = link per lane (physics_ll.hip), 1 = env per lane (physics.hip)
+    const int64_t* motion_id = {}; // [N] device (borrowed)
+    float* state = {};             // [N][STATE_SLOTS]
+    float* ctrl = {};              // [N][CTRL_SLOTS]: pd target 69, wrench 6
+    float* out = {};               // [N][OUT_SLOTS]: physics outputs before export
+    float* ws = {};                // SoA [WS_SLOTS][N] physics workspace
+    int32_t* contact_ids = {};     // [N,24,4] debug
+    int32_t* contact_ids_sub = {}; // [N,nsub,24,4] debug, every substep (v2p_sim_cfg.debug_substep_contacts), else NULL
+    long long* prof = {};          // [8] phase cycle counters when V2P_PHASE_TIMING is set (device), else NULL
+    long long* wave_times = {};    // [waves][4] per-wave wall-clock stamps of the last launch when V2P_WAVE_TIMES=<file> is set
     // pairing (physics_ll.hip): envs are handed to waves in descending order of their contact load
-    int32_t* pair_key;        // [N] load key of each env after the last physics launch (0..255)
-    int32_t* pair_pos;        // [N] arrival index inside its load bin
-    int32_t* pair_hist;       // [256] + pair_start [256] + pair_done [1] (one allocation)
-    int32_t* pair_start;
-    int32_t* pair_done;
-    int32_t* perm;            // [N] wave slot -> env of the next physics launch, materialised for v2p_env_debug_pairing only
-    int32_t* pair_list[2];    // [256][N] envs of each load bin in arrival order: what the NEXT launch looks its envs up in (double
-    int32_t* pair_starts[2];  // [256]    first rank of each bin                  buffered: a launch reads one set and fills the other)
-    int pair_buf;             // the set the next launch reads
-    int job_mono_default;     // job_mono_permille was left at its default (v2p_env_attach_ball moves it)
-    int32_t* pair_slot_env;   // [N] env of each wave slot of the running launch: looked up by the job of the first substep, read by the later ones
-    int pair_period;          // 0 = pairing off (v2p_sim_cfg.pair_envs_by_load = 0), else on
-    int substeps_per_sim;     // substeps of one simulate() call
-    int substep_jobs;         // v2p_sim_cfg.substep_jobs: the physics launch is cut into (substep, env pair) jobs
-    int job_min_blocks;       // ... when it has more env pairs than this (0: always)
-    int32_t* job_progress;    // [waves + 1] progress word per wave slot, last = error flag
-    float* job_hand;          // [nsub - 1][N][HAND_FLOATS] the state as one substep job hands it to the next (16-byte chunks), a slot per substep
-    long job_timeout_spins;   // see PhysArgs
-    int job_interleave;
-    int job_len;              // substeps per job; 0 = the engine decides (2 for launches of >= job_len2_blocks env pairs, else 1)
-    int job_len2_blocks;
-    int ll_regs_build;        // 1: this batch runs the register build of the link-per-lane kernel (two waves per SIMD)
-    int kernel_build;         // v2p_sim_cfg.kernel_build (0: ll_regs_build follows the envs resident on the device)
-    int build_latched;        // kernel_build 0: the choice is taken at the first launch after creation / after a whole-batch reset and holds until the next one
-    int counted_resident;     // this batch is in the device's resident-env count
-    int job_lead;             // substeps of the FIRST job of a cut pair (0 = like the others, -1 = the engine decides)
-    int64_t job_recoveries;   // jobs that gave up waiting and recomputed, as last fetched (v2p_env_check / _check_async)
-    int64_t jobs_skipped;     // late jobs that found their pair's step complete and did not run (their per-call records are missing for that step)
-    int64_t jobs_skipped_reported;
-    int job_epoch;
-    int pair_mix_permille;    // share of the envs (the heaviest) that are paired with the lightest ones instead of with each other
-    int pair_mix_default;     // pair_mix_permille was left to the engine (-1)
-    int job_mono_permille;    // share of the env pairs (the heaviest) whose substeps stay in one workgroup
-    v2p::BallDev* ball;       // racket + ball attached (v2p_env_attach_ball), else NULL
-    int32_t* err_host;        // pinned copy of the substep jobs' error word (v2p_env_check_async), lazily allocated
-    hipEvent_t err_event;
-    int err_pending;
-    hipEvent_t* prof_ev;      // 2 events per measured physics launch (v2p_env_profile_begin), else NULL
-    int64_t prof_cap, prof_n;
-    int64_t prof_seen;        // physics launches since v2p_env_profile_begin
-    int32_t prof_stride, prof_period;  // which of them are bracketed (v2p_env_profile_begin_sampled)
-    int pair_have;            // the last physics launch left (key, pos, start) that have not been scattered into perm yet
-    v2p::CtxTransform ctx;    // context frame width + transform (v2p_env_set_context_transform)
-    int context_built;        // a reset / context call has written frames: the width is fixed from now on
+    int32_t* pair_key = {};        // [N] load key of each env after the last physics launch (0..255)
+    int32_t* pair_pos = {};        // [N] arrival index inside its load bin
+    int32_t* pair_hist = {};       // [256] + pair_start [256] + pair_done [1] (one allocation)
+    int32_t* pair_start = {};
+    int32_t* pair_done = {};
+    int32_t* perm = {};            // [N] wave slot -> env of the next physics launch, materialised for v2p_env_debug_pairing only
+    int32_t* pair_list[2] = {};    // [256][N] envs of each load bin in arrival order: what the NEXT launch looks its envs up in (double
+    int32_t* pair_starts[2] = {};  // [256]    first rank of each bin                  buffered: a launch reads one set and fills the other)
+    int pair_buf = {};             // the set the next launch reads
+    int job_mono_default = {};     // job_mono_permille was left at its default (v2p_env_attach_ball moves it)
+    int32_t* pair_slot_env = {};   // [N] env of each wave slot of the running launch: looked up by the job of the first substep, read by the later ones
+    int pair_period = {};          // 0 = pairing off (v2p_sim_cfg.pair_envs_by_load = 0), else on
+    int substeps_per_sim = {};     // substeps of one simulate() call
+    int substep_jobs = {};         // v2p_sim_cfg.substep_jobs: the physics launch is cut into (substep, env pair) jobs
+    int job_min_blocks = {};       // ... when it has more env pairs than this (0: always)
+    int32_t* job_progress = {};    // [waves + 1] progress word per wave slot, last = error flag
+    float* job_hand = {};          // [nsub - 1][N][HAND_FLOATS] the state as one substep job hands it to the next (16-byte chunks), a slot per substep
+    long job_timeout_spins = {};   // see PhysArgs
+    int job_interleave = {};
+    int job_len = {};              // substeps per job; 0 = the engine decides (2 for launches of >= job_len2_blocks env pairs, else 1)
+    int job_len2_blocks = {};
+    int ll_regs_build = {};        // 1: this batch runs the register build of the link-per-lane kernel (two waves per SIMD)
+    int kernel_build = {};         // v2p_sim_cfg.kernel_build (0: ll_regs_build follows the envs resident on the device)
+    int build_latched = {};        // kernel_build 0: the choice is taken at the first launch after creation / after a whole-batch reset and holds until the next one
+    int counted_resident = {};     // this batch is in the device's resident-env count
+    int job_lead = {};             // substeps of the FIRST job of a cut pair (0 = like the others, -1 = the engine decides)
+    int64_t job_recoveries = {};   // jobs that gave up waiting and recomputed, as last fetched (v2p_env_check / _check_async)
+    int64_t jobs_skipped = {};     // late jobs that found their pair's step complete and did not run (their per-call records are missing for that step)
+    int64_t jobs_skipped_reported = {};
+    int job_epoch = {};
+    int pair_mix_permille = {};    // share of the envs (the heaviest) that are paired with the lightest ones instead of with each other
+    int pair_mix_default = {};     // pair_mix_permille was left to the engine (-1)
+    int job_mono_permille = {};    // share of the env pairs (the heaviest) whose substeps stay in one workgroup
+    v2p::BallDev* ball = {};       // racket + ball attached (v2p_env_attach_ball), else NULL
+    int32_t* err_host = {};        // pinned copy of the substep jobs' error word (v2p_env_check_async), lazily allocated
+    hipEvent_t* err_event = {};    // [1] recorded behind the copy into err_host
+    int err_pending = {};
+    hipEvent_t* prof_ev = {};      // 2 events per measured physics launch (v2p_env_profile_begin), else NULL
+    int64_t prof_cap = {}, prof_n = {};
+    int64_t prof_seen = {};        // physics launches since v2p_env_profile_begin
+    int32_t prof_stride = {}, prof_period = {};  // which of them are bracketed (v2p_env_profile_begin_sampled)
+    int pair_have = {};            // the last physics launch left (key, pos, start) that have not been scattered into perm yet
+    v2p::CtxTransform ctx = {};    // context frame width + transform (v2p_env_set_context_transform)
+    int context_built = {};        // a reset / context call has written frames: the width is fixed from now on
+    v2p::DeviceOwner own;          // owns every engine-side allocation the pointers above name (the ball's contact_part / rackets too)
+    ~v2p_env();                    // (env.hip: the host-side BallDev)
 };
 
 #ifndef V2P_LL_WPB
@@ -216,9 +278,7 @@ constexpr int OUT_RB = 0, OUT_DOF_POS = NB * 13, OUT_CONTACT = OUT_DOF_POS + NDO
 #define CIDX(slot) ((int64_t)e * v2p::CTRL_SLOTS + (slot))
 #define OIDX(slot) ((int64_t)e * v2p::OUT_SLOTS + (slot))
 
-void set_error(const char* fmt, ...);
 const char* debug_env(const char* name);  // getenv in a process that sets V2P_DEBUG=1, else NULL (profiling switches only)
-int check_hip(hipError_t e, const char* what);
 
 // launchers (each in its own translation unit)
 int launch_motion_state(const v2p_motion_tables& t, const int64_t* ids, const float* times, int64_t q, int adjust_height, float ground_tol,
@@ -262,7 +322,11 @@ struct PairView;
 PairView env_pair_view(const v2p_env* e);
 int launch_env_pairing(v2p_env* e, hipStream_t s);  // scatter (key, pos, start) -> perm when env_pre_kernel has not done it
 int launch_env_export(v2p_env* e, hipStream_t s);
+
+// host side (no kernels): model_compile.hip, env.hip
+int compile_model(const v2p_model_desc& d, DevModel* out);  // the body model as the kernels read it; validates, no GPU calls
 int ensure_env_per_lane_buffers(v2p_env* e);  // the env-per-lane schedule's global workspace, allocated on first use
+int env_physics_launch(v2p_env* e, hipStream_t s, float* actions, int* fused_post = nullptr);  // either schedule, in the build of choice
 int launch_env_post(v2p_env* e, hipStream_t s);
 int launch_env_push_state(v2p_env* e, const int64_t* env_ids, int64_t n, int with_rb, hipStream_t s);
 int physics_ws_slots();
