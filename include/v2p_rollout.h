@@ -500,6 +500,49 @@ typedef struct {
 } v2p_racket_geom;
 int v2p_env_set_racket_shapes(v2p_env* e, const v2p_racket_geom* per_shape, int32_t num_shapes);
 
+/* ---- free balls on their own (vid2player/utils/tennis_ball.py:113-218 `simulate`, tennis_ball_out_estimator.py:21-121
+ * `simulate_without_bounce`): n balls, one per lane, each simulated alone for num_frames control steps of control_freq_inv simulate()
+ * calls of `substeps` substeps, in one launch.  The ball is the engine's own (the ball of v2p_env_attach_ball without racket and
+ * humanoid: gravity, drag + Magnus force re-evaluated before every call, the ball x ground rows under either solver, angular damping
+ * and cap), so that the pool of incoming launches and the estimator tables the reference makes offline with Isaac Gym describe the
+ * ball a racket + ball batch really simulates.  Added to `simulate`'s side of it: the SIGN of the launch spin (the spin fed to the
+ * lift is sign x |w| / 2 pi until the call that detects the bounce, + afterwards, :163-176, 190-195; launch angular velocity =
+ * vspin x 2 pi x normalize(launch_vel x (0,0,-1)), :135-136), and the bookkeeping at the start of every call (:167-187).
+ * No handle, no state between calls; asynchronous on `stream` on the CURRENT device. */
+typedef struct {
+    float radius, mass, inertia;                     /* 0.032, 0.057, 4e-5 (tennis_ball.urdf) */
+    float restitution_ground, friction_ground;       /* ball x plane, already combined */
+    float bounce_threshold_velocity;
+    float angular_damping, max_angular_velocity;     /* 0.5, 64 */
+    float spin_scale;
+    float sim_dt;                                    /* length of one simulate() call */
+    int32_t substeps, control_freq_inv, num_iterations, solver_type; /* all >= 1; solver_type 0 PGS, 1 TGS */
+    float gravity_z, contact_offset, erp, max_depenetration_velocity;
+    int32_t enable_ground;                           /* 0: no ground rows (the outgoing tables) */
+    int32_t num_frames;                              /* control steps recorded */
+    float net_height;                                /* pass_net: height the ball must exceed at the first call that sees y < 0 */
+    float bounce_height;                             /* height at the start of a call at or below which the ball "has bounced" */
+    int32_t resample;                                /* 1: no trajectory; the positions at the start of all (num_frames + 1) x control_freq_inv
+                                                      * calls are resampled online onto the two grids below (needs enable_ground = 0) */
+    double grid_x[3];                                /* (lo, hi, step) of the horizontal distance y: int((hi - lo) / step) cells, cell k at lo + k step */
+    double grid_y[3];                                /* (lo, hi, step) of the drop below the launch height */
+} v2p_ball_sim;
+typedef struct {                 /* DEVICE buffers, each nullable */
+    float* traj;                 /* [n,num_frames,3] position at the start of control step t (resample = 0) */
+    float* bounce_pos;           /* [n,3] position at the start of the call that saw z <= bounce_height first, else 0 */
+    int64_t* bounce_idx;         /* [n] frame of that call, else num_frames - 1 */
+    uint8_t* pass_net;           /* [n] at the first call that saw y < 0: not yet bounced and z > net_height */
+    float* peak_after_bounce;    /* [n] largest recorded height over frames bounce_idx .. num_frames - 1 (resample = 0) */
+    float* final_state;          /* [n,13] pos quat vel angvel after the last call */
+    float* traj_x;               /* [n,nx] resample: height relative to the launch height at every distance of grid_x */
+    float* traj_y;               /* [n,ny,2] resample: (distance, time in seconds) at every drop of grid_y */
+} v2p_ball_rollout_out;
+/* Refused before any HIP call (V2P_ERR_INVALID, a message that names the call): NULL cfg / out; NULL launch arrays with n > 0; n < 0;
+ * substeps, control_freq_inv, num_iterations or num_frames < 1; solver_type outside 0 / 1; mass, inertia or radius <= 0; resample
+ * with enable_ground, without both grids (a grid with no cell), or with a non-positive step.  n = 0 is a no-op. */
+int v2p_ball_rollout(const v2p_ball_sim* cfg, int64_t n, const float* launch_pos /*[n,3]*/, const float* launch_vel /*[n,3]*/,
+                     const float* launch_vspin /*[n] revolutions per second, signed*/, const v2p_ball_rollout_out* out, void* stream);
+
 /* measurement: HIP events around every launch of the physics kernel (the dominant kernel of the step), recorded on the launch stream
  * by v2p_env_step / v2p_env_physics between _begin and _end (at most max_launches of them).  _end synchronises the events and returns
  * the summed kernel time in milliseconds and the number of launches measured.  bench.py's roofline.kernel_ms comes from here, from

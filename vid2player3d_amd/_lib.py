@@ -75,6 +75,21 @@ class RacketGeom(C.Structure):
     _fields_ = [("racket_link", C.c_int32), ("num_cylinders", C.c_int32), ("cylinders", (C.c_float * 8) * 2), ("racket_offset", C.c_float * 3)]
 
 
+class BallSim(C.Structure):
+    """v2p_ball_sim: a free ball on its own (v2p_ball_rollout)."""
+    _fields_ = [("radius", C.c_float), ("mass", C.c_float), ("inertia", C.c_float), ("restitution_ground", C.c_float), ("friction_ground", C.c_float),
+                ("bounce_threshold_velocity", C.c_float), ("angular_damping", C.c_float), ("max_angular_velocity", C.c_float), ("spin_scale", C.c_float),
+                ("sim_dt", C.c_float), ("substeps", C.c_int32), ("control_freq_inv", C.c_int32), ("num_iterations", C.c_int32), ("solver_type", C.c_int32),
+                ("gravity_z", C.c_float), ("contact_offset", C.c_float), ("erp", C.c_float), ("max_depenetration_velocity", C.c_float),
+                ("enable_ground", C.c_int32), ("num_frames", C.c_int32), ("net_height", C.c_float), ("bounce_height", C.c_float), ("resample", C.c_int32),
+                ("grid_x", C.c_double * 3), ("grid_y", C.c_double * 3)]
+
+
+class BallRolloutOut(C.Structure):
+    _fields_ = [("traj", vp), ("bounce_pos", vp), ("bounce_idx", vp), ("pass_net", vp), ("peak_after_bounce", vp), ("final_state", vp),
+                ("traj_x", vp), ("traj_y", vp)]
+
+
 class ContextTransform(C.Structure):
     _fields_ = [("num_ops", C.c_int32), ("ops", C.c_int32 * 3), ("mask_joints", C.c_uint32), ("noise_prob", C.c_float), ("noise_std", C.c_float),
                 ("conf_std", C.c_float), ("min_conf", C.c_float), ("drop_prob", C.c_float)]
@@ -142,6 +157,7 @@ def load():
         "v2p_env_jobs_skipped": [vp, C.POINTER(C.c_int64)],
         "v2p_env_attach_ball": [vp, C.POINTER(BallCfg), C.POINTER(BallBuffers)],
         "v2p_env_set_racket_shapes": [vp, C.POINTER(RacketGeom), C.c_int32],
+        "v2p_ball_rollout": [C.POINTER(BallSim), C.c_int64, vp, vp, vp, C.POINTER(BallRolloutOut), vp],
         "v2p_env_profile_begin": [vp, C.c_int64],
         "v2p_env_profile_begin_sampled": [vp, C.c_int64, C.c_int32, C.c_int32],
         "v2p_env_profile_end": [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)],
@@ -161,7 +177,7 @@ def load():
 EXPORTED_SYMBOLS = (
     "v2p_model_create", "v2p_model_destroy", "v2p_mlib_create", "v2p_mlib_destroy", "v2p_motion_state", "v2p_reward", "v2p_reset_flags",
     "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_obs_imitation_packed_w", "v2p_policy_head_w", "v2p_policy_head_record_w", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_set_context_transform", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
-    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_last_error", "v2p_abi_version",
+    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_last_error", "v2p_abi_version",
 )
 
 

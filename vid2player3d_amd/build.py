@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libv2p_rollout.so")
-SOURCES = ["capi.hip", "device_owner.hip", "model_compile.hip", "env.hip", "motion_state.hip", "task_ops.hip", "shape_compile.hip", "motion_build.hip", "physics.hip", "physics_ll.hip", "physics_ll_host.hip"]
+SOURCES = ["capi.hip", "device_owner.hip", "model_compile.hip", "env.hip", "motion_state.hip", "task_ops.hip", "shape_compile.hip", "motion_build.hip", "physics.hip", "physics_ll.hip", "physics_ll_host.hip", "ball_rollout.hip"]
 HEADERS = ["v2p_internal.hpp", "v2p_dev.hpp", "v2p_math.inc", "phys_math.hpp", "phys_common.hpp", "motion_sample.inc", "hull_gjk.hpp", "post_ops.inc", "strict_ops.inc", os.path.join("..", "..", "include", "v2p_rollout.h")]
 ARCH = "gfx950"
 
@@ -78,8 +78,9 @@ def compile_flags(source, regs=False):
         # the task-side kernels restate torch elementwise code: no FMA contraction, so that ill-conditioned spots of the
         # reference itself (acos of a dot product next to 1 in slerp / angle-axis) round the way torch rounds them
         fl = [f if f != "-ffp-contract=fast" else "-ffp-contract=off" for f in fl]
-    if source in ("physics_ll.hip", "physics_ll_host.hip"):
-        # the link-per-lane physics kernel (and the stand-alone pre-physics kernel that shares namespace strict with it): relaxed fp32
+    if source in ("physics_ll.hip", "physics_ll_host.hip", "ball_rollout.hip"):
+        # the link-per-lane physics kernel (and the stand-alone pre-physics kernel that shares namespace strict with it; and the free-ball
+        # kernel, which restates the ball lane of the former and is meant to round like it): relaxed fp32
         # arithmetic for the code of this file, precise device libraries (see the head of physics_ll.hip for why the flags are spelled
         # out instead of -ffast-math); V2P_LL_STRICT_MATH=1 builds it precise (A/B, bisecting)
         fl = [f if f != "-ffp-contract=fast" else "-ffp-contract=fast-honor-pragmas" for f in fl]

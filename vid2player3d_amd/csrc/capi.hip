@@ -219,6 +219,33 @@ int v2p_shapes_compile(int32_t num_jobs, const double* points, const int32_t* jo
                                 num_verts, vert_ids, verts, status, (hipStream_t)stream);
 }
 
+int v2p_ball_rollout(const v2p_ball_sim* c, int64_t n, const float* launch_pos, const float* launch_vel, const float* launch_vspin,
+                     const v2p_ball_rollout_out* out, void* stream) {
+    // every refusal comes before the first HIP call
+    if (!c || !out) { set_error("v2p_ball_rollout: null cfg / out"); return V2P_ERR_INVALID; }
+    if (n < 0) { set_error("v2p_ball_rollout: n %lld < 0", (long long)n); return V2P_ERR_INVALID; }
+    if (n > 0 && (!launch_pos || !launch_vel || !launch_vspin)) { set_error("v2p_ball_rollout: null launch array"); return V2P_ERR_INVALID; }
+    if (c->substeps < 1 || c->control_freq_inv < 1 || c->num_iterations < 1 || c->num_frames < 1) {
+        set_error("v2p_ball_rollout: substeps %d, control_freq_inv %d, num_iterations %d and num_frames %d must all be >= 1", c->substeps, c->control_freq_inv,
+                  c->num_iterations, c->num_frames);
+        return V2P_ERR_INVALID;
+    }
+    if (c->solver_type != 0 && c->solver_type != 1) { set_error("v2p_ball_rollout: solver_type %d is neither 0 (PGS) nor 1 (TGS)", c->solver_type); return V2P_ERR_INVALID; }
+    if (!(c->mass > 0.f) || !(c->inertia > 0.f) || !(c->radius > 0.f)) {
+        set_error("v2p_ball_rollout: mass %g, inertia %g and radius %g must be > 0", (double)c->mass, (double)c->inertia, (double)c->radius);
+        return V2P_ERR_INVALID;
+    }
+    if (!(c->sim_dt > 0.f)) { set_error("v2p_ball_rollout: sim_dt %g <= 0", (double)c->sim_dt); return V2P_ERR_INVALID; }
+    if (c->resample) {
+        if (c->enable_ground) { set_error("v2p_ball_rollout: resample needs enable_ground = 0 (the outgoing tables are flights without a bounce)"); return V2P_ERR_INVALID; }
+        if (!(c->grid_x[2] > 0.0) || !(c->grid_y[2] > 0.0)) { set_error("v2p_ball_rollout: resample with a non-positive grid step"); return V2P_ERR_INVALID; }
+        if (ball_grid_cells(c->grid_x) < 1 || ball_grid_cells(c->grid_y) < 1) { set_error("v2p_ball_rollout: resample needs both grids (lo < hi, at most 1e6 cells)"); return V2P_ERR_INVALID; }
+        if (n > 0 && (!out->traj_x || !out->traj_y)) { set_error("v2p_ball_rollout: resample needs traj_x and traj_y"); return V2P_ERR_INVALID; }
+    }
+    if (n == 0) return V2P_OK;
+    return launch_ball_rollout(*c, n, launch_pos, launch_vel, launch_vspin, *out, (hipStream_t)stream);
+}
+
 int v2p_env_reset(v2p_env* e, const int64_t* env_ids, int64_t n, const float* motion_times, void* stream) {
     if (!e || !motion_times || n < 0 || n > e->n) { set_error("v2p_env_reset: bad argument"); return V2P_ERR_INVALID; }
     DeviceGuard g(e->device);

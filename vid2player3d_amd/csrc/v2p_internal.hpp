@@ -309,6 +309,10 @@ int launch_value_record(int64_t n, const float* x, const double* mean, const dou
 int launch_rollout_record(int64_t n, const float* obs, int64_t obs_dim, const float* rew, const int64_t* reset, const int64_t* terminate, const float* sub_rewards,
                           float* next_obs_row, float* rewards_row, float* dones_row, float* dones, float* terminated, float* prev_dones, float* cur_rewards,
                           float* cur_lengths, double* acc, double* sub_acc, hipStream_t s);
+// free balls on their own (ball_rollout.hip); ball_grid_cells: cells of a (lo, hi, step) grid, 0 = not a grid
+int launch_ball_rollout(const v2p_ball_sim& c, int64_t n, const float* launch_pos, const float* launch_vel, const float* launch_vspin,
+                        const v2p_ball_rollout_out& out, hipStream_t s);
+int ball_grid_cells(const double g[3]);
 int launch_env_reset(v2p_env* e, const int64_t* env_ids, int64_t n, const float* motion_times, hipStream_t s);
 int launch_env_context(v2p_env* e, const int64_t* env_ids, int64_t n, const float* motion_times, hipStream_t s);
 int launch_env_pre(v2p_env* e, float* actions, hipStream_t s);

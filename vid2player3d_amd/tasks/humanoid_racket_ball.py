@@ -167,6 +167,18 @@ class HumanoidSMPLIMRacketBall(HumanoidSMPLIM):
             left = [racket.PLAYERS[p]["parent"] == "L_Wrist" for p in self.racket_players]
             self._lefthand = left.index(True) if any(left) else None
         self.ball_material = mat
+        # the ball generator (humanoid_smpl_im_mvae.py:121-130), opt-in: a pool file under cfg_v2p.ball_traj_file (ball_traj_file_test when
+        # neither training nor test_mode 'random'), or a generator object under cfg_v2p.ball_generator; without either key reset_balls
+        # takes the launch state from the caller as before.  Two departures from :121-130: the reference reads the task's own _is_train, here
+        # it is a key of its own, cfg_v2p.is_train (default true); and the reference builds no generator under dual_mode, here a
+        # two-player task that names a pool file gets one too
+        self._ball_generator = self.cfg_v2p.get("ball_generator")
+        if self._ball_generator is None and "ball_traj_file" in self.cfg_v2p:
+            from ..ball_traj import TennisBallGeneratorOffline
+
+            random_rows = bool(self.cfg_v2p.get("is_train", True)) or self.cfg_v2p.get("test_mode", "random") == "random"
+            self._ball_generator = TennisBallGeneratorOffline(self.cfg_v2p["ball_traj_file" if random_rows else "ball_traj_file_test"], sample_random=random_rows,
+                                                              num_envs=n, device=dev)
 
     # ------------------------------------------------------------------ two players: shapes by env, not by clip
     def _env_body_shapes(self, env):
@@ -193,9 +205,21 @@ class HumanoidSMPLIMRacketBall(HumanoidSMPLIM):
         return self._players_share_the_clips(super()._check_body_shapes, env)
 
     # ------------------------------------------------------------------ the reference's flag bookkeeping around the physics step
-    def reset_balls(self, env_ids, launch_pos, launch_vel, launch_ang_vel):
-        """`_reset_balls` (:503-522) with the launch state given by the caller (the reference draws it from its trajectory generator)."""
+    def reset_balls(self, env_ids, launch_pos=None, launch_vel=None, launch_ang_vel=None):
+        """`_reset_balls` (:503-524).  With a launch state given by the caller it is written as it is; without one it is drawn from the
+        task's ball generator (cfg_v2p.ball_traj_file / ball_generator) as the reference does - `generate(len(env_ids),
+        need_init_state=True, start_pos=ball positions, env_ids=env_ids)`, spin axis from the launch velocity (:508-509) - and the drawn
+        trajectories [len(env_ids),frames,3] are returned."""
         ids = torch.as_tensor(env_ids, device=self.device, dtype=torch.long)
+        traj = None
+        if launch_pos is None:
+            if self._ball_generator is None:
+                raise RuntimeError("reset_balls without a launch state needs cfg_v2p.ball_traj_file or cfg_v2p.ball_generator")
+            from ..ball_traj import launch_ang_vel as spin_axis
+
+            traj, launch_pos, launch_vel, vspin = self._ball_generator.generate(len(ids), need_init_state=True, start_pos=self._ball_root_states[ids, 0:3], env_ids=ids)
+            launch_pos, launch_vel = launch_pos.to(self.device), launch_vel.to(self.device)
+            launch_ang_vel = spin_axis(launch_vel, vspin.to(self.device))
         self._ball_root_states[ids, 0:3] = launch_pos
         self._ball_root_states[ids, 3:7] = torch.tensor([0.0, 0.0, 0.0, 1.0], device=self.device)
         self._ball_root_states[ids, 7:10] = launch_vel
@@ -203,6 +227,7 @@ class HumanoidSMPLIMRacketBall(HumanoidSMPLIM):
         self._has_bounce[ids] = False
         self._bounce_pos[ids] = 0
         self._has_racket_ball_contact[ids] = False
+        return traj
 
     # The reference's flag bookkeeping around every simulate() call - the bounce test on the ball height at the START of the call
     # (apply_external_force_to_ball, :731-737: threshold 4 ball radii, 6 with more than 2 substeps) and the contact-force poll after it
