@@ -543,6 +543,92 @@ typedef struct {                 /* DEVICE buffers, each nullable */
 int v2p_ball_rollout(const v2p_ball_sim* cfg, int64_t n, const float* launch_pos /*[n,3]*/, const float* launch_vel /*[n,3]*/,
                      const float* launch_vspin /*[n] revolutions per second, signed*/, const v2p_ball_rollout_out* out, void* stream);
 
+/* ---- the tennis controller's task step (vid2player/env/tasks/physics_mvae_controller.py: PhysicsMVAEController) on top of a racket +
+ * ball batch: everything the controller does after the physics of a control step - racket hit, true and estimated bounce bookkeeping
+ * (_update_state, :271-314), one of the three reward laws (:368-406, 492-602), the actor + task observation (:316-360), the reaction /
+ * recovery / termination flags (_compute_reset, :408-436) and the roll of the ball-trajectory window (physics_step, :365-366) - for all
+ * envs in ONE launch without a host synchronisation (the reference has two: has_contact_now.sum() > 0, has_valid_contact.sum() > 0).
+ * One wavefront per env: lanes stride the columns of the observation row.  Stateless like v2p_reward: every buffer is the caller's. */
+enum { V2P_TENNIS_REWARD_REACH = 0, V2P_TENNIS_REWARD_RETURN = 1, V2P_TENNIS_REWARD_RETURN_W_ESTIMATE = 2 };
+#define V2P_TENNIS_ACTOR_OBS 225   /* root_pos3 root_vel3 (bodies 1..24 - root)72 rot6d(bodies 0..23)144 racket_normal3 (:333-342) */
+#define V2P_TENNIS_TRAJ_FRAMES 100 /* frames of an env's ball trajectory (`_ball_traj`, :64) */
+typedef struct {
+    int32_t reward_type;            /* V2P_TENNIS_REWARD_* (cfg_v2p reward_type) */
+    int32_t obs_ball_traj_length;   /* L, 1..100: the task observation holds 3 L columns */
+    int32_t use_history_ball_obs;   /* 1: the window is the rolled history of ball positions, 0: frames cursor .. cursor + L - 1 of ball_traj */
+    int32_t use_random_ball_target; /* 1: two more columns, target xy - root xy */
+    int32_t contact_by_velocity;    /* 1 (sim.substeps > 2): the racket hit is read from the ball's velocity change
+                                     * (humanoid_smpl_im_mvae.py:800-808) and WRITTEN to has_racket_contact(_now); 0: the flags are read */
+    int32_t enable_early_termination;
+    int64_t max_episode_length;     /* episodeLength */
+    float grip_normal[3];           /* racket normal in the wrist frame: eastern (0,1,0), semi_western (0,1/sqrt2,1/sqrt2) (:835-838) */
+    float court_min[2], court_max[2]; /* cfg_v2p court_min / court_max: the player leaves the court outside them (:482-490) */
+    float scale_pos, scale_phase, scale_bounce_pos, scale_bounce_time; /* reward_scales: 5, 10, 0.05, 0.1 */
+    float weight_pos, weight_ball_pos; /* reward_weights `pos` (default 1 for reach, 0 else) and `ball_pos` (0) */
+    /* the out-estimator (utils/tennis_ball_out_estimator.py:13-18, 124-205): grids as (lo, hi, step) in the order VEL_X, VEL_Y, VSPIN,
+     * TRAJ_X, TRAJ_Y, and the shape of the two tables */
+    double grid[5][3];
+    int64_t table_rows;             /* B */
+    int32_t table_nx, table_ny;     /* cells of a row of traj_out_x / traj_out_y */
+} v2p_tennis_cfg;
+typedef struct {                    /* DEVICE buffers; bool tensors are bytes */
+    /* read only: the racket + ball batch's tensors */
+    const float* rb_state;          /* [N,24,13] */
+    const float* root_states;       /* [N,13] */
+    const float* racket_state;      /* [N,13] rigid body 24 */
+    const float* ball_state;        /* [N,13] */
+    const int64_t* wrist_link;      /* [N] the link the env's racket is welded to */
+    const uint8_t* has_bounce;      /* [N] */
+    const uint8_t* has_bounce_now;  /* [N] */
+    const float* bounce_pos;        /* [N,3] */
+    /* read only: what the motion generator supplies */
+    const float* phase_pred;        /* [N] */
+    const int64_t* swing_type;      /* [N] (reach, return) */
+    const int64_t* swing_type_cycle; /* [N] (return_w_estimate) */
+    /* read only: the outgoing tables */
+    const float* traj_out_x;        /* [B,nx] */
+    const float* traj_out_y;        /* [B,ny,2] */
+    /* read only: the controller's targets */
+    const int64_t* tar_time_total;  /* [N] */
+    const int64_t* tar_action;      /* [N] 1 swing, 0 recovery */
+    const float* target_bounce_pos; /* [N,3] */
+    const float* ball_traj;         /* [N,100,3] (nullable with use_history_ball_obs) */
+    /* read and written */
+    uint8_t* has_racket_contact;    /* [N] written with contact_by_velocity only */
+    uint8_t* has_racket_contact_now; /* [N] */
+    int64_t* tar_time;              /* [N] */
+    int64_t* progress;              /* [N] */
+    float* prev_ball_vy;            /* [N] the ball's vy at the previous task step (`_ball_vel[:, 1]` before its update) */
+    int32_t* traj_cursor;           /* [N] first frame of the env's window inside ball_traj; frames past 100 read as zero */
+    float* ball_obs;                /* [N,L,3] history of ball positions, rolled by every observation (nullable without use_history_ball_obs) */
+    uint8_t* bounce_in;             /* [N] */
+    float* est_bounce_pos;          /* [N,3] */
+    float* est_bounce_time;         /* [N] */
+    float* est_max_height;          /* [N] */
+    uint8_t* est_bounce_in;         /* [N] */
+    float* distance;                /* [N] */
+    int64_t* vel_x_overflow;        /* [1] 'velocity X overflow' counter (tennis_ball_out_estimator.py:180) */
+    /* written */
+    float* racket_pos;              /* [N,3] */
+    float* racket_normal;           /* [N,3] */
+    float* obs;                     /* [N, 225 + 3 L (+ 2)] */
+    float* rew;                     /* [N] */
+    float* sub_rewards;             /* [N,1] reach, [N,2] else */
+    int64_t* reset;                 /* [N] */
+    int64_t* terminate;             /* [N] */
+    uint8_t* reset_reaction;        /* [N] */
+    uint8_t* reset_recovery;        /* [N] */
+} v2p_tennis_buffers;
+/* One control step of the task for envs 0 .. n-1, in the reference's order: tar_time / progress += 1; racket hit; _update_state; reward;
+ * observation; _compute_reset; the window advances one frame.  sub_rewards_names (HOST, nullable) receives the reward law's names string.
+ * Refused before any HIP call (V2P_ERR_INVALID, a message that names the call): n < 0, a null required pointer, L outside 1..100, an
+ * unknown reward type, tables without cells.  n = 0 is a no-op. */
+int v2p_tennis_task_step(const v2p_tennis_cfg* cfg, int64_t n, const v2p_tennis_buffers* buffers, const char** sub_rewards_names, void* stream);
+/* `_compute_observations(env_ids)` alone (:198-199, at reset time), the history roll of those envs included: racket_pos, racket_normal,
+ * ball_obs and obs rows of env_ids [n_ids] (device; ids outside 0 .. num_envs-1 are skipped) are written, nothing else. */
+int v2p_tennis_task_obs(const v2p_tennis_cfg* cfg, int64_t num_envs, const v2p_tennis_buffers* buffers, const int64_t* env_ids, int64_t n_ids,
+                        void* stream);
+
 /* measurement: HIP events around every launch of the physics kernel (the dominant kernel of the step), recorded on the launch stream
  * by v2p_env_step / v2p_env_physics between _begin and _end (at most max_launches of them).  _end synchronises the events and returns
  * the summed kernel time in milliseconds and the number of launches measured.  bench.py's roofline.kernel_ms comes from here, from

@@ -90,6 +90,26 @@ class BallRolloutOut(C.Structure):
                 ("traj_x", vp), ("traj_y", vp)]
 
 
+class TennisCfg(C.Structure):
+    """v2p_tennis_cfg: settings of the tennis controller's task step (v2p_tennis_task_step / _obs)."""
+    _fields_ = [("reward_type", C.c_int32), ("obs_ball_traj_length", C.c_int32), ("use_history_ball_obs", C.c_int32), ("use_random_ball_target", C.c_int32),
+                ("contact_by_velocity", C.c_int32), ("enable_early_termination", C.c_int32), ("max_episode_length", C.c_int64), ("grip_normal", C.c_float * 3),
+                ("court_min", C.c_float * 2), ("court_max", C.c_float * 2), ("scale_pos", C.c_float), ("scale_phase", C.c_float), ("scale_bounce_pos", C.c_float),
+                ("scale_bounce_time", C.c_float), ("weight_pos", C.c_float), ("weight_ball_pos", C.c_float), ("grid", (C.c_double * 3) * 5),
+                ("table_rows", C.c_int64), ("table_nx", C.c_int32), ("table_ny", C.c_int32)]
+
+
+TENNIS_BUFFER_NAMES = ("rb_state", "root_states", "racket_state", "ball_state", "wrist_link", "has_bounce", "has_bounce_now", "bounce_pos", "phase_pred", "swing_type",
+                       "swing_type_cycle", "traj_out_x", "traj_out_y", "tar_time_total", "tar_action", "target_bounce_pos", "ball_traj", "has_racket_contact",
+                       "has_racket_contact_now", "tar_time", "progress", "prev_ball_vy", "traj_cursor", "ball_obs", "bounce_in", "est_bounce_pos", "est_bounce_time",
+                       "est_max_height", "est_bounce_in", "distance", "vel_x_overflow", "racket_pos", "racket_normal", "obs", "rew", "sub_rewards", "reset", "terminate",
+                       "reset_reaction", "reset_recovery")
+
+
+class TennisBuffers(C.Structure):
+    _fields_ = [(k, vp) for k in TENNIS_BUFFER_NAMES]
+
+
 class ContextTransform(C.Structure):
     _fields_ = [("num_ops", C.c_int32), ("ops", C.c_int32 * 3), ("mask_joints", C.c_uint32), ("noise_prob", C.c_float), ("noise_std", C.c_float),
                 ("conf_std", C.c_float), ("min_conf", C.c_float), ("drop_prob", C.c_float)]
@@ -158,6 +178,8 @@ def load():
         "v2p_env_attach_ball": [vp, C.POINTER(BallCfg), C.POINTER(BallBuffers)],
         "v2p_env_set_racket_shapes": [vp, C.POINTER(RacketGeom), C.c_int32],
         "v2p_ball_rollout": [C.POINTER(BallSim), C.c_int64, vp, vp, vp, C.POINTER(BallRolloutOut), vp],
+        "v2p_tennis_task_step": [C.POINTER(TennisCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(C.c_char_p), vp],
+        "v2p_tennis_task_obs": [C.POINTER(TennisCfg), C.c_int64, C.POINTER(TennisBuffers), vp, C.c_int64, vp],
         "v2p_env_profile_begin": [vp, C.c_int64],
         "v2p_env_profile_begin_sampled": [vp, C.c_int64, C.c_int32, C.c_int32],
         "v2p_env_profile_end": [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)],
@@ -177,7 +199,7 @@ def load():
 EXPORTED_SYMBOLS = (
     "v2p_model_create", "v2p_model_destroy", "v2p_mlib_create", "v2p_mlib_destroy", "v2p_motion_state", "v2p_reward", "v2p_reset_flags",
     "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_obs_imitation_packed_w", "v2p_policy_head_w", "v2p_policy_head_record_w", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_set_context_transform", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
-    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_last_error", "v2p_abi_version",
+    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_last_error", "v2p_abi_version",
 )
 
 

@@ -7,6 +7,7 @@
 
 #include <new>
 
+#include "tennis_task.hpp"
 #include "v2p_internal.hpp"
 
 namespace v2p {
@@ -244,6 +245,54 @@ int v2p_ball_rollout(const v2p_ball_sim* c, int64_t n, const float* launch_pos, 
     }
     if (n == 0) return V2P_OK;
     return launch_ball_rollout(*c, n, launch_pos, launch_vel, launch_vspin, *out, (hipStream_t)stream);
+}
+
+// what both tennis entry points refuse; `step`: the buffers only the whole step touches are required too
+static int tennis_check(const char* fn, const v2p_tennis_cfg* c, int64_t n, const v2p_tennis_buffers* b, bool step) {
+    if (!c || !b) { set_error("%s: null cfg / buffers", fn); return V2P_ERR_INVALID; }
+    if (n < 0) { set_error("%s: n %lld < 0", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (c->obs_ball_traj_length < 1 || c->obs_ball_traj_length > V2P_TENNIS_TRAJ_FRAMES) {
+        set_error("%s: obs_ball_traj_length %d outside 1..%d", fn, c->obs_ball_traj_length, V2P_TENNIS_TRAJ_FRAMES);
+        return V2P_ERR_INVALID;
+    }
+    if (c->reward_type < V2P_TENNIS_REWARD_REACH || c->reward_type > V2P_TENNIS_REWARD_RETURN_W_ESTIMATE) {
+        set_error("%s: unknown reward type %d", fn, c->reward_type);
+        return V2P_ERR_INVALID;
+    }
+    if (n == 0) return V2P_OK;
+    bool ok = b->rb_state && b->root_states && b->racket_state && b->ball_state && b->wrist_link && b->obs && b->racket_pos && b->racket_normal;
+    ok = ok && (c->use_history_ball_obs ? b->ball_obs != nullptr : (b->ball_traj && b->traj_cursor));
+    ok = ok && (!c->use_random_ball_target || b->target_bounce_pos);
+    if (step) {
+        ok = ok && b->has_bounce && b->has_bounce_now && b->bounce_pos && b->phase_pred && b->traj_out_x && b->traj_out_y && b->tar_time_total &&
+             b->tar_action && b->target_bounce_pos && b->has_racket_contact && b->has_racket_contact_now && b->tar_time && b->progress && b->prev_ball_vy &&
+             b->bounce_in && b->est_bounce_pos && b->est_bounce_time && b->est_max_height && b->est_bounce_in && b->distance && b->vel_x_overflow &&
+             b->rew && b->sub_rewards && b->reset && b->terminate && b->reset_reaction && b->reset_recovery;
+        ok = ok && (c->reward_type == V2P_TENNIS_REWARD_RETURN_W_ESTIMATE ? b->swing_type_cycle != nullptr : b->swing_type != nullptr);
+    }
+    if (!ok) { set_error("%s: null buffer", fn); return V2P_ERR_INVALID; }
+    if (step) {
+        if (c->table_rows < 1 || c->table_nx < 1 || c->table_ny < 1) { set_error("%s: the estimator tables have no cells", fn); return V2P_ERR_INVALID; }
+        for (int g = 0; g < 5; ++g)
+            if (!(c->grid[g][2] > 0.0) || !(c->grid[g][1] > c->grid[g][0])) { set_error("%s: grid %d is not (lo < hi, step > 0)", fn, g); return V2P_ERR_INVALID; }
+    }
+    return V2P_OK;
+}
+
+int v2p_tennis_task_step(const v2p_tennis_cfg* c, int64_t n, const v2p_tennis_buffers* b, const char** names, void* stream) {
+    const int rc = tennis_check("v2p_tennis_task_step", c, n, b, true);
+    if (rc != V2P_OK) return rc;
+    if (names) *names = c->reward_type == V2P_TENNIS_REWARD_REACH ? "pos_reward" : "pos_reward,ball_pos_reward";
+    if (n == 0) return V2P_OK;
+    return launch_tennis_task_step(*c, n, *b, (hipStream_t)stream);
+}
+
+int v2p_tennis_task_obs(const v2p_tennis_cfg* c, int64_t num_envs, const v2p_tennis_buffers* b, const int64_t* env_ids, int64_t n_ids, void* stream) {
+    const int rc = tennis_check("v2p_tennis_task_obs", c, n_ids, b, false);
+    if (rc != V2P_OK) return rc;
+    if (num_envs < 0 || (n_ids > 0 && !env_ids)) { set_error("v2p_tennis_task_obs: num_envs %lld < 0 or null env_ids", (long long)num_envs); return V2P_ERR_INVALID; }
+    if (n_ids == 0 || num_envs == 0) return V2P_OK;
+    return launch_tennis_task_obs(*c, num_envs, *b, env_ids, n_ids, (hipStream_t)stream);
 }
 
 int v2p_env_reset(v2p_env* e, const int64_t* env_ids, int64_t n, const float* motion_times, void* stream) {

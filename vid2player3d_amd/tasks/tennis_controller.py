@@ -1,0 +1,453 @@
+"""The tennis controller's task step on the device (vid2player/env/tasks/physics_mvae_controller.py, `PhysicsMVAEController`).
+
+What consumes the racket + ball batch (`HumanoidSMPLIMRacketBall`), the pool of incoming launches and the outgoing estimator tables
+(`ball_traj.py`): the actor and task observations (:316-360), the three reward laws (:368-406, 492-602), the true and estimated bounce
+bookkeeping (:271-314), the reaction / recovery / termination logic (:408-436) and the ball-trajectory window (:362-366).  One control
+step of it is ONE kernel launch, `v2p_tennis_task_step` (csrc/tennis_task.hip), without a host synchronisation; the observation of
+freshly reset envs is `v2p_tennis_task_obs`.  The racket hit at more than 2 substeps - read from the ball's velocity change
+(humanoid_smpl_im_mvae.py:800-808), which the racket task itself does not do - is part of that step.
+
+The MVAE motion generator is not here: what the controller needs from it, the swing phase and the swing type, comes in as tensors from
+whoever drives the step (`post_physics_step(phase_pred, swing_type, swing_type_cycle)`).
+
+`task_step_reference` is a numpy statement of the same step on arrays - the checker of the tests, as `ball_traj.resample_reference`
+and `body_shapes` have theirs; the product never calls it.  There is no CPU path: a CPU device or a missing library is a RuntimeError.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..ball_traj import NET_HEIGHT, traj_out_params
+
+NUM_ACTOR_OBS = 3 + 3 + 24 * 3 + 24 * 6 + 3  # physics_mvae_controller.py:148
+TRAJ_FRAMES = 100
+REWARD_TYPES = {"reach": 0, "return": 1, "return_w_estimate": 2}
+SUB_REWARD_NAMES = {"reach": "pos_reward", "return": "pos_reward,ball_pos_reward", "return_w_estimate": "pos_reward,ball_pos_reward"}
+GRIP_NORMALS = {"eastern": (0.0, 1.0, 0.0), "semi_western": (0.0, 1.0 / math.sqrt(2), 1.0 / math.sqrt(2))}  # humanoid_smpl_im_mvae.py:835-838
+COURT = (-4.11, 4.11, 0.0, 11.89)  # the bounce tests' court (:285-286): x0, x1, y0, y1
+
+
+def grids_of(params=traj_out_params):
+    """The five (lo, hi, step) ranges of the out-estimator in the order of v2p_tennis_cfg.grid."""
+    return np.array([params.VEL_X_RANGE, params.VEL_Y_RANGE, params.VSPIN_RANGE, params.TRAJ_X_RANGE, params.TRAJ_Y_RANGE], dtype=np.float64)
+
+
+def task_settings(reward_type="return", obs_ball_traj_length=100, use_history_ball_obs=False, use_random_ball_target=False, contact_by_velocity=False,
+                  enable_early_termination=False, max_episode_length=300, grip="eastern", court_min=(-20.0, -40.0), court_max=(20.0, 0.0),
+                  reward_scales=None, reward_weights=None, grids=None):
+    """The settings of one task step as a plain dict (what both the kernel's v2p_tennis_cfg and task_step_reference are made from);
+    defaults of scales and weights are the reference's (:512-516, 529, 543-544, 594-595)."""
+    if reward_type not in REWARD_TYPES:
+        raise ValueError("reward_type %r is none of %s" % (reward_type, sorted(REWARD_TYPES)))
+    L = int(obs_ball_traj_length)
+    if not 1 <= L <= TRAJ_FRAMES:
+        raise ValueError("obs_ball_traj_length %d outside 1..%d" % (L, TRAJ_FRAMES))
+    sc, w = dict(reward_scales or {}), dict(reward_weights or {})
+    return dict(reward_type=reward_type, L=L, use_history=bool(use_history_ball_obs), use_target=bool(use_random_ball_target),
+                contact_by_velocity=bool(contact_by_velocity), early_termination=bool(enable_early_termination), max_episode_length=int(max_episode_length),
+                grip_normal=tuple(float(x) for x in (GRIP_NORMALS[grip] if isinstance(grip, str) else grip)),
+                court_min=tuple(float(x) for x in court_min[:2]), court_max=tuple(float(x) for x in court_max[:2]),
+                scale_pos=float(sc.get("pos", 5.0)), scale_phase=float(sc.get("phase", 10.0)), scale_bounce_pos=float(sc.get("bounce_pos", 0.05)),
+                scale_bounce_time=float(sc.get("bounce_time", 0.1)), weight_pos=float(w.get("pos", 1.0 if reward_type == "reach" else 0.0)),
+                weight_ball_pos=float(w.get("ball_pos", 0.0)), grids=np.asarray(grids_of() if grids is None else grids, dtype=np.float64))
+
+
+def obs_width(st):
+    return NUM_ACTOR_OBS + 3 * st["L"] + (2 if st["use_target"] else 0)
+
+
+def num_sub_rewards(st):
+    return 1 if st["reward_type"] == "reach" else 2
+
+
+def cfg_struct(st, table_shape_x, table_shape_y):
+    """v2p_tennis_cfg of a settings dict and the shapes of the two tables ([B,nx], [B,ny,2])."""
+    c = _lib.TennisCfg(reward_type=REWARD_TYPES[st["reward_type"]], obs_ball_traj_length=st["L"], use_history_ball_obs=int(st["use_history"]),
+                       use_random_ball_target=int(st["use_target"]), contact_by_velocity=int(st["contact_by_velocity"]),
+                       enable_early_termination=int(st["early_termination"]), max_episode_length=st["max_episode_length"],
+                       scale_pos=st["scale_pos"], scale_phase=st["scale_phase"], scale_bounce_pos=st["scale_bounce_pos"], scale_bounce_time=st["scale_bounce_time"],
+                       weight_pos=st["weight_pos"], weight_ball_pos=st["weight_ball_pos"], table_rows=int(table_shape_x[0]), table_nx=int(table_shape_x[1]),
+                       table_ny=int(table_shape_y[1]))
+    c.grip_normal[:] = st["grip_normal"]
+    c.court_min[:] = st["court_min"]
+    c.court_max[:] = st["court_max"]
+    for g in range(5):
+        c.grid[g][:] = [float(x) for x in st["grids"][g]]
+    return c
+
+
+def buffers_struct(tensors):
+    """v2p_tennis_buffers of a dict name -> device tensor (names of _lib.TENNIS_BUFFER_NAMES; absent or None = NULL)."""
+    unknown = set(tensors) - set(_lib.TENNIS_BUFFER_NAMES)
+    if unknown:
+        raise ValueError("not buffers of v2p_tennis_buffers: %s" % sorted(unknown))
+    for k, t in tensors.items():
+        if t is not None and (not t.is_cuda or not t.is_contiguous()):
+            raise RuntimeError("tennis task step: buffer %s must be a contiguous GPU tensor (there is no CPU path)" % k)
+    return _lib.TennisBuffers(**{k: t.data_ptr() for k, t in tensors.items() if t is not None})
+
+
+def launch_step(st, tensors, n):
+    """v2p_tennis_task_step on a dict of device tensors; returns the names string of the reward law."""
+    lib = _lib.load()
+    c = cfg_struct(st, tensors["traj_out_x"].shape, tensors["traj_out_y"].shape)
+    b = buffers_struct(tensors)
+    names = C.c_char_p()
+    dev = tensors["obs"].device
+    with torch.cuda.device(dev):
+        _lib.check(lib.v2p_tennis_task_step(C.byref(c), int(n), C.byref(b), C.byref(names), _lib.current_stream(dev)), "v2p_tennis_task_step")
+    return names.value.decode()
+
+
+def launch_obs(st, tensors, num_envs, env_ids):
+    """v2p_tennis_task_obs for env_ids (int64 device tensor)."""
+    lib = _lib.load()
+    tx, ty = tensors.get("traj_out_x"), tensors.get("traj_out_y")
+    c = cfg_struct(st, (1, 1) if tx is None else tx.shape, (1, 1, 2) if ty is None else ty.shape)
+    b = buffers_struct(tensors)
+    dev = tensors["obs"].device
+    ids = env_ids.to(device=dev, dtype=torch.long).contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(lib.v2p_tennis_task_obs(C.byref(c), int(num_envs), C.byref(b), _lib.ptr(ids), int(ids.numel()), _lib.current_stream(dev)), "v2p_tennis_task_obs")
+
+
+# ------------------------------------------------------------------------------------------------------------------ the checker
+_f = np.float32
+
+
+def _rotmat_rows(w, x, y, z):
+    """quaternion_to_rotation_matrix (utils/konia_transform.py:474-549) of already unpacked numbers, float32: the 9 entries, row-major."""
+    n = np.maximum(np.sqrt(w * w + x * x + y * y + z * z), _f(1e-12))
+    w, x, y, z = w / n, x / n, y / n, z / n
+    tx, ty, tz = _f(2) * x, _f(2) * y, _f(2) * z
+    one = _f(1)
+    return [one - (ty * y + tz * z), ty * x - tz * w, tz * x + ty * w, ty * x + tz * w, one - (tx * x + tz * z), tz * y - tx * w, tz * x - ty * w, tz * y + tx * w,
+            one - (tx * x + ty * y)]
+
+
+def _index(v, r):
+    """round((clamp(v, lo, hi - step) - lo) / step) on float32 with the scalars rounded to float32 (ball_traj._index_f32)."""
+    lo, top, step = _f(r[0]), _f(r[1] - r[2]), _f(r[2])
+    return np.rint((np.clip(v, lo, top) - lo) / step)
+
+
+def _in_court(x, y):
+    return (x > _f(COURT[0])) & (x < _f(COURT[1])) & (y > _f(COURT[2])) & (y < _f(COURT[3]))
+
+
+def observation_reference(st, s, env_ids=None):
+    """`_compute_observations(env_ids)` (:316-360) in numpy float32 on a dict of arrays named like v2p_tennis_buffers.  Returns
+    (obs rows [len(env_ids), W], ball_obs after the roll or None, racket_pos, racket_normal) for those envs."""
+    ids = np.arange(len(s["ball_state"])) if env_ids is None else np.asarray(env_ids, dtype=np.int64)
+    rb = np.asarray(s["rb_state"], dtype=_f).reshape(-1, 24, 13)[ids]
+    rk = np.asarray(s["racket_state"], dtype=_f)[ids]
+    root, rvel = rb[:, 0, 0:3], np.asarray(s["root_states"], dtype=_f)[ids, 7:10]
+    rpos = rk[:, 0:3]
+    L = st["L"]
+    # racket normal: the wrist link's rotation, converted xyzw -> wxyz properly (humanoid_smpl_im_mvae.py:831-845)
+    q = rb[np.arange(len(ids)), np.asarray(s["wrist_link"], dtype=np.int64)[ids], 3:7]
+    m = _rotmat_rows(q[:, 3], q[:, 0], q[:, 1], q[:, 2])
+    g = [_f(x) for x in st["grip_normal"]]
+    rnorm = np.stack([m[3 * i] * g[0] + m[3 * i + 1] * g[1] + m[3 * i + 2] * g[2] for i in range(3)], -1)
+    # quat_to_rot6d on the (x, y, z, w) numbers read as (w, x, y, z): columns 0 and 1 of that matrix
+    q = rb[:, :, 3:7]
+    m = _rotmat_rows(q[..., 0], q[..., 1], q[..., 2], q[..., 3])
+    rot6d = np.stack([m[0], m[3], m[6], m[1], m[4], m[7]], -1).reshape(len(ids), 144)
+    rel = (np.concatenate([rb[:, 1:, 0:3], rpos[:, None]], 1) - root[:, None]).reshape(len(ids), 72)
+    hist = None
+    if s.get("ball_obs") is not None:
+        old = np.asarray(s["ball_obs"], dtype=_f).reshape(-1, L, 3)[ids]
+        hist = np.concatenate([old[:, 1:], np.asarray(s["ball_state"], dtype=_f)[ids, None, 0:3]], 1)
+    if st["use_history"]:
+        window = hist
+    else:
+        traj = np.concatenate([np.asarray(s["ball_traj"], dtype=_f).reshape(-1, TRAJ_FRAMES, 3)[ids], np.zeros((len(ids), TRAJ_FRAMES + L, 3), _f)], 1)
+        cur = np.clip(np.asarray(s["traj_cursor"], dtype=np.int64)[ids], 0, TRAJ_FRAMES)
+        window = traj[np.arange(len(ids))[:, None], cur[:, None] + np.arange(L)[None]]
+    cols = [root, rvel, rel, rot6d, rnorm, (window - rpos[:, None]).reshape(len(ids), 3 * L)]
+    if st["use_target"]:
+        cols.append(np.asarray(s["target_bounce_pos"], dtype=_f)[ids, 0:2] - root[:, 0:2])
+    with np.errstate(invalid="ignore"):
+        return np.concatenate(cols, 1).astype(_f), hist, rpos.copy(), rnorm.astype(_f)
+
+
+def task_step_reference(st, s):
+    """One control step of the task on arrays (post_physics_step :441-452 + the roll of physics_step :365-366), numpy float32.
+    `st`: task_settings(...); `s`: arrays named like v2p_tennis_buffers (inputs and state before the step).  Returns a dict with every
+    array the step writes: the updated state and the outputs.  Nothing in `s` is modified."""
+    n = len(s["ball_state"])
+    A = lambda k, dt=None: np.array(s[k], dtype=dt)
+    o = {}
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        tar_time, progress, tar_action = A("tar_time", np.int64) + 1, A("progress", np.int64) + 1, A("tar_action", np.int64)
+        ball = A("ball_state", _f)
+        rb = A("rb_state", _f).reshape(n, 24, 13)
+        root, rvel = rb[:, 0, 0:3], A("root_states", _f)[:, 7:10]
+        hit, now = A("has_racket_contact").astype(bool), A("has_racket_contact_now").astype(bool)
+        vy = ball[:, 8]
+        if st["contact_by_velocity"]:
+            now = ~hit & (vy > 0) & ((vy - A("prev_ball_vy", _f)) > _f(10))
+            hit = hit | now
+        # ---- _update_state
+        bp = A("bounce_pos", _f)
+        upd = (tar_action == 0) & A("has_bounce_now").astype(bool)
+        bounce_in = np.where(upd, _in_court(bp[:, 0], bp[:, 1]), A("bounce_in").astype(bool))
+        est, est_time, est_peak, est_in = A("est_bounce_pos", _f), A("est_bounce_time", _f), A("est_max_height", _f), A("est_bounce_in").astype(bool)
+        G = st["grids"]
+        VX, VY, VS, TX, TY = G
+        tx, ty = np.asarray(s["traj_out_x"], dtype=_f), np.asarray(s["traj_out_y"], dtype=_f)
+        valid = now & (ball[:, 8] > _f(VX[0])) & (ball[:, 9] > _f(VY[0])) & (ball[:, 9] < _f(VY[1])) & (ball[:, 2] < _f(TY[1]))
+        x_net = ball[:, 0] + ball[:, 7] * np.abs(ball[:, 1] / ball[:, 8])
+        valid &= (x_net > _f(-4)) & (x_net < _f(4))
+        overflow = 0
+        for e in np.nonzero(valid)[0]:  # TennisBallOutEstimator.estimate (tennis_ball_out_estimator.py:164-205), ball by ball
+            b = ball[e]
+            vel_x = np.sqrt(b[7] * b[7] + b[8] * b[8])
+            overflow += int(vel_x >= _f(VX[1]))
+            vspin = np.sqrt(b[10] * b[10] + b[11] * b[11] + b[12] * b[12]) / _f(math.pi * 2)
+            dim1, dim2 = _f((VY[1] - VY[0]) / VY[2]), _f((VS[1] - VS[0]) / VS[2])
+            ti = int(np.clip(int(_index(vel_x, VX) * dim1 * dim2 + _index(b[9], VY) * dim2 + _index(vspin, VS)), 0, len(tx) - 1))
+            hi = int(np.clip(int(_index(b[2], TY)), 0, ty.shape[1] - 1))
+            bx, by, bt = b[0] + ty[ti, hi, 0] * b[7] / vel_x, b[1] + ty[ti, hi, 0] * b[8] / vel_x, ty[ti, hi, 1]
+            ni = int(np.clip(int(_index(-b[1] / b[8] * vel_x, TX)), 0, tx.shape[1] - 1))
+            if tx[ti, ni] + b[2] < _f(NET_HEIGHT):
+                bx = by = bt = _f(0)
+            est[e, 0], est[e, 1], est_time[e], est_peak[e] = bx, by, bt, b[2] + tx[ti].max()
+            est_in[e] = bool(_in_court(_f(bx), _f(by)))
+        # ---- the reward
+        rpos, bpos = A("racket_state", _f)[:, 0:3], ball[:, 0:3]
+        d = bpos - rpos
+        pos_err = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+        phase = A("phase_pred", _f)
+        rt = st["reward_type"]
+        swing = A("swing_type_cycle" if rt == "return_w_estimate" else "swing_type", np.int64)
+        early = (swing == -1) if rt == "reach" else (swing >= 2)
+        pd = phase - np.where(early, _f(3), _f(math.pi))
+        near = np.exp(-_f(st["scale_pos"]) * pos_err) * np.exp(-_f(st["scale_phase"]) * (pd * pd))
+        tg = A("target_bounce_pos", _f)
+        sq = lambda u: u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1] + u[:, 2] * u[:, 2]
+        if rt == "reach":
+            sub = ((tar_action == 1).astype(_f) * near)[:, None]
+            rew = sub[:, 0] * _f(st["weight_pos"])
+        else:
+            sub0 = (~hit).astype(_f) * near + hit.astype(_f)
+            if rt == "return":
+                err = np.where(A("has_bounce").astype(bool), sq(bp - tg), sq(bpos - tg))
+                sub1 = hit.astype(_f) * np.clip((_f(400) - err) / _f(400), _f(0), _f(1))
+            else:
+                sub1 = est_in.astype(_f) * np.exp(-_f(st["scale_bounce_pos"]) * sq(est - tg)) * np.exp(-_f(st["scale_bounce_time"]) * est_time)
+            sub = np.stack([sub0, sub1], -1)
+            rew = _f(st["weight_pos"]) * sub0 + _f(st["weight_ball_pos"]) * sub1
+        # ---- the observation
+        obs, hist, _, rnorm = observation_reference(st, s)
+        # ---- _compute_reset
+        cmin, cmax = [_f(x) for x in st["court_min"]], [_f(x) for x in st["court_max"]]
+        terminated = (root[:, 0] < cmin[0]) | (root[:, 1] < cmin[1]) | (root[:, 0] > cmax[0]) | (root[:, 1] > cmax[1])
+        terminated |= np.isnan(obs).any(axis=1)
+        reset = np.where(progress >= st["max_episode_length"] - 1, True, terminated)
+        reaction = tar_time == A("tar_time_total", np.int64)
+        behind = bpos[:, 1] < root[:, 1] - _f(1)
+        recovery = (tar_action == 1) & (hit | behind)
+        distance = A("distance", _f) + np.sqrt(rvel[:, 0] * rvel[:, 0] + rvel[:, 1] * rvel[:, 1])
+        terminate = terminated.copy()
+        if st["early_termination"]:
+            terminate |= (recovery & ~hit) | behind
+            if rt.startswith("return_w_estimate"):
+                terminate |= hit & ~est_in
+        terminated = terminated | terminate
+        reset = reset | terminate
+        recovery = recovery & ~terminate
+        reaction = reaction | reset
+    o.update(tar_time=tar_time, progress=progress, has_racket_contact=hit, has_racket_contact_now=now, prev_ball_vy=vy.copy(), bounce_in=bounce_in,
+             est_bounce_pos=est, est_bounce_time=est_time, est_max_height=est_peak, est_bounce_in=est_in, distance=distance.astype(_f),
+             vel_x_overflow=np.int64(np.asarray(s.get("vel_x_overflow", 0)).reshape(-1)[0] + overflow), racket_pos=rpos.copy(), racket_normal=rnorm, obs=obs,
+             rew=rew.astype(_f), sub_rewards=sub.astype(_f), reset=reset.astype(np.int64), terminate=terminated.astype(np.int64), reset_reaction=reaction,
+             reset_recovery=recovery, sub_rewards_names=SUB_REWARD_NAMES[rt])
+    if hist is not None:
+        o["ball_obs"] = hist
+    if not st["use_history"]:
+        o["traj_cursor"] = np.minimum(np.clip(A("traj_cursor", np.int64), 0, TRAJ_FRAMES) + 1, TRAJ_FRAMES).astype(np.int32)
+    return o
+
+
+# ------------------------------------------------------------------------------------------------------------------ the task
+class TennisControllerTask:
+    """`PhysicsMVAEController` without the MVAE player, on top of a single-player `HumanoidSMPLIMRacketBall`.  Attribute names are the
+    reference's.  cfg: `cfg["env"]` (episodeLength, enableEarlyTermination) and `cfg["v2p"]` (reward_type / _weights / _scales, court_min /
+    _max, obs_ball_traj_length, use_history_ball_obs, use_random_ball_target, reset_reaction_nframes, grip, ball_traj_out_x_file / _y_file -
+    file names or arrays).  `_ball_traj` [N,100,3] holds every env's drawn trajectory as it was drawn; `_ball_traj_cursor` [N] is the
+    first frame of its window (the reference rolls the tensor instead, :365-366): `ball_traj_window()` gives the rolled view."""
+
+    def __init__(self, task, cfg, params=traj_out_params):
+        env, v2p = dict(cfg.get("env") or {}), dict(cfg.get("v2p") or {})
+        if v2p.get("dual_mode") or getattr(task, "racket_players", None) is not None:
+            raise NotImplementedError("TennisControllerTask: dual_mode (the two-player controller and its ball hand-over) is not built")
+        if not hasattr(task, "_ball_root_states"):
+            raise TypeError("TennisControllerTask wraps a HumanoidSMPLIMRacketBall")
+        dev = torch.device(task.device)
+        if dev.type != "cuda":
+            raise RuntimeError("TennisControllerTask: the task step is a HIP kernel - the wrapped task must live on a GPU (no CPU fallback)")
+        _lib.load()
+        for key in ("court_min", "court_max", "reset_reaction_nframes"):
+            if key not in v2p:
+                raise ValueError("TennisControllerTask: cfg v2p.%s is required" % key)
+        self.task, self.cfg, self.cfg_v2p, self.device, self.num_envs = task, cfg, v2p, dev, task.num_envs
+        self._max_episode_length = int(env["episodeLength"])
+        self._enable_early_termination = bool(env.get("enableEarlyTermination", False))
+        self.settings = task_settings(reward_type=v2p.get("reward_type", "return"), obs_ball_traj_length=v2p.get("obs_ball_traj_length", 100),
+                                      use_history_ball_obs=v2p.get("use_history_ball_obs", False), use_random_ball_target=v2p.get("use_random_ball_target", False),
+                                      contact_by_velocity=task.sim_params.substeps > 2, enable_early_termination=self._enable_early_termination,
+                                      max_episode_length=self._max_episode_length, grip=v2p.get("grip", "eastern"), court_min=v2p["court_min"], court_max=v2p["court_max"],
+                                      reward_scales=v2p.get("reward_scales"), reward_weights=v2p.get("reward_weights"), grids=grids_of(params))
+        st = self.settings
+        self._obs_ball_traj_length = st["L"]
+        n = self.num_envs
+        f, i64, bl = dict(dtype=torch.float32, device=dev), dict(dtype=torch.long, device=dev), dict(dtype=torch.bool, device=dev)
+        load = lambda t: torch.from_numpy(np.load(t) if isinstance(t, str) else np.ascontiguousarray(t)).to(**f).contiguous()
+        self._ball_traj_out_x = load(v2p.get("ball_traj_out_x_file", "vid2player/data/ball_traj_out_x_v0.npy"))
+        self._ball_traj_out_y = load(v2p.get("ball_traj_out_y_file", "vid2player/data/ball_traj_out_y_v0.npy"))
+        if self._ball_traj_out_x.dim() != 2 or self._ball_traj_out_y.dim() != 3 or len(self._ball_traj_out_x) != len(self._ball_traj_out_y):
+            raise ValueError("the outgoing tables must be [B,nx] and [B,ny,2]")
+        self.num_obs = obs_width(st)
+        self.obs_buf = torch.zeros((n, self.num_obs), **f)
+        self.rew_buf = torch.zeros(n, **f)
+        self.reset_buf = torch.ones(n, **i64)
+        self.progress_buf = torch.zeros(n, **i64)
+        self._terminate_buf = torch.ones(n, **i64)
+        self.extras = {}
+        self._sub_rewards = torch.zeros((n, num_sub_rewards(st)), **f)
+        self._sub_rewards_names = SUB_REWARD_NAMES[st["reward_type"]]
+        self._racket_pos, self._racket_normal = torch.zeros((n, 3), **f), torch.zeros((n, 3), **f)
+        self._ball_traj = torch.zeros((n, TRAJ_FRAMES, 3), **f)
+        self._ball_traj_cursor = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._ball_obs = torch.zeros((n, st["L"], 3), **f)
+        self._bounce_in = torch.zeros(n, **bl)
+        self._est_bounce_pos, self._est_bounce_time = torch.zeros((n, 3), **f), torch.zeros(n, **f)
+        self._est_bounce_in, self._est_max_height = torch.zeros(n, **bl), torch.zeros(n, **f)
+        self._tar_time, self._tar_time_total, self._tar_action = torch.zeros(n, **i64), torch.zeros(n, **i64), torch.zeros(n, **i64)
+        self._target_bounce_pos = torch.zeros((n, 3), **f)
+        self._target_bounce_pos[:] = torch.tensor([0.0, 10.0, 0.0], **f)
+        self._target_bounce_min, self._target_bounce_max = torch.tensor([-3.0, 9.0, 0.0], **f), torch.tensor([3.0, 11.0, 0.0], **f)
+        self._reset_reaction_buf, self._reset_recovery_buf = torch.ones(n, **bl), torch.zeros(n, **bl)  # all envs start with a reaction task
+        self._num_reset_reaction, self._num_reset = torch.zeros(n, **i64), torch.zeros(n, **i64)
+        self._distance = torch.zeros(n, **f)
+        self._prev_ball_vy = torch.zeros(n, **f)
+        self.vel_x_overflow = torch.zeros(1, **i64)
+        self._phase_pred, self._swing_type, self._swing_type_cycle = torch.zeros(n, **f), torch.zeros(n, **i64), torch.full((n,), -1, **i64)
+        wl = task._racket_wrist_body_id
+        self._wrist_link = (wl.to(**i64) if torch.is_tensor(wl) else torch.full((n,), int(wl), **i64)).contiguous()
+        self._has_init = False
+
+    # ------------------------------------------------------------------ sizes
+    def get_actor_obs_size(self):
+        return NUM_ACTOR_OBS
+
+    def get_task_obs_size(self):
+        return 3 * self.settings["L"] + (2 if self.settings["use_target"] else 0)
+
+    def ball_traj_window(self):
+        """The reference's rolled `_ball_traj`: frame k of the view is frame cursor + k of the drawn trajectory, zeros past its end."""
+        idx = self._ball_traj_cursor.long().view(-1, 1) + torch.arange(TRAJ_FRAMES, device=self.device).view(1, -1)
+        padded = torch.cat([self._ball_traj, torch.zeros_like(self._ball_traj)], 1)
+        return padded[torch.arange(self.num_envs, device=self.device).view(-1, 1), idx.clamp(max=2 * TRAJ_FRAMES - 1)]
+
+    def _tensors(self):
+        t, rb = self.task, self.task._rigid_body_state
+        return dict(rb_state=rb, root_states=t._humanoid_root_states, racket_state=t._racket_rb_state, ball_state=t._ball_root_states, wrist_link=self._wrist_link,
+                    has_bounce=t._has_bounce, has_bounce_now=t._has_bounce_now, bounce_pos=t._bounce_pos, phase_pred=self._phase_pred, swing_type=self._swing_type,
+                    swing_type_cycle=self._swing_type_cycle, traj_out_x=self._ball_traj_out_x, traj_out_y=self._ball_traj_out_y, tar_time_total=self._tar_time_total,
+                    tar_action=self._tar_action, target_bounce_pos=self._target_bounce_pos, ball_traj=self._ball_traj, has_racket_contact=t._has_racket_ball_contact,
+                    has_racket_contact_now=t._has_racket_ball_contact_now, tar_time=self._tar_time, progress=self.progress_buf, prev_ball_vy=self._prev_ball_vy,
+                    traj_cursor=self._ball_traj_cursor, ball_obs=self._ball_obs, bounce_in=self._bounce_in, est_bounce_pos=self._est_bounce_pos,
+                    est_bounce_time=self._est_bounce_time, est_max_height=self._est_max_height, est_bounce_in=self._est_bounce_in, distance=self._distance,
+                    vel_x_overflow=self.vel_x_overflow, racket_pos=self._racket_pos, racket_normal=self._racket_normal, obs=self.obs_buf, rew=self.rew_buf,
+                    sub_rewards=self._sub_rewards, reset=self.reset_buf, terminate=self._terminate_buf, reset_reaction=self._reset_reaction_buf,
+                    reset_recovery=self._reset_recovery_buf)
+
+    def state_arrays(self):
+        """Every tensor of the step as a numpy array, named like v2p_tennis_buffers (what task_step_reference takes)."""
+        return {k: v.detach().cpu().numpy().copy() for k, v in self._tensors().items()}
+
+    # ------------------------------------------------------------------ reset (:167-242, without the MVAE call)
+    def reset(self, env_ids=None):
+        if env_ids is None:
+            if self._has_init and self.num_envs > 1:
+                return
+            env_ids = torch.arange(self.num_envs, device=self.device, dtype=torch.long)
+        self._reset_envs(torch.as_tensor(env_ids, device=self.device, dtype=torch.long))
+
+    def _reset_envs(self, env_ids):
+        reaction_ids = self._reset_reaction_buf.nonzero(as_tuple=False).flatten()  # (include env_ids)
+        recovery_ids = self._reset_recovery_buf.nonzero(as_tuple=False).flatten()
+        all_ids = (self._reset_reaction_buf | self._reset_recovery_buf).nonzero(as_tuple=False).flatten()
+        if len(env_ids) > 0:
+            self._reset_env_tensors(env_ids)
+            self._num_reset[env_ids] += 1
+        if len(reaction_ids) > 0:
+            new_traj = self.task.reset_balls(reaction_ids)
+            frames = min(new_traj.shape[1], TRAJ_FRAMES)
+            self._ball_traj[reaction_ids] = 0
+            self._ball_traj[reaction_ids, :frames] = new_traj[:, :frames].to(self.device)
+            self._ball_traj_cursor[reaction_ids] = 0
+            # (`_reset_balls` refreshes `_ball_vel` with the launch velocity, humanoid_smpl_im_mvae.py:522: the velocity rule's previous vy)
+            self._prev_ball_vy[reaction_ids] = self.task._ball_root_states[reaction_ids, 8]
+        if len(recovery_ids) > 0:
+            self._reset_recovery_tasks(recovery_ids)
+        if len(reaction_ids) > 0:
+            self._reset_reaction_tasks(reaction_ids)
+        if len(all_ids) > 0:
+            launch_obs(self.settings, self._tensors(), self.num_envs, all_ids)
+        self._has_init = True
+
+    def _reset_env_tensors(self, env_ids):
+        self.progress_buf[env_ids] = 0
+        self.reset_buf[env_ids] = 0
+        self._terminate_buf[env_ids] = 0
+        self._reset_reaction_buf[env_ids] = False
+        self._reset_recovery_buf[env_ids] = False
+        self._num_reset_reaction[env_ids] = 0
+        self._distance[env_ids] = 0
+
+    def _reset_reaction_tasks(self, env_ids):
+        if self.settings["use_history"]:
+            self._ball_obs[env_ids] = self.task._ball_root_states[env_ids, 0:3].view(-1, 1, 3).repeat(1, self._obs_ball_traj_length, 1)
+        self._tar_time[env_ids] = 0
+        self._tar_action[env_ids] = 1
+        self._num_reset_reaction[env_ids] += 1
+        self._bounce_in[env_ids] = False
+        self._est_bounce_pos[env_ids, :] = 0
+        self._est_bounce_time[env_ids] = 0
+        self._est_bounce_in[env_ids] = False
+        self._est_max_height[env_ids] = 0
+        self._swing_type_cycle[env_ids] = -1
+        self._tar_time_total[env_ids] = int(self.cfg_v2p["reset_reaction_nframes"]) + torch.randint(-5, 5, (len(env_ids),), device=self.device)
+        target = self.cfg_v2p.get("use_random_ball_target")
+        if target:
+            if target == "continuous":  # (the same target for the envs to be reset)
+                self._target_bounce_pos[env_ids] = torch.rand((3,), device=self.device) * (self._target_bounce_max - self._target_bounce_min) + self._target_bounce_min
+            else:
+                seed = torch.rand((len(env_ids),), device=self.device)
+                x = torch.where(seed < 0.33, -3.0, torch.where(seed > 0.67, 3.0, 0.0))
+                self._target_bounce_pos[env_ids] = torch.stack([x, torch.full_like(x, 10.0), torch.zeros_like(x)], -1)
+
+    def _reset_recovery_tasks(self, env_ids):
+        self._tar_action[env_ids] = 0
+        self.task._has_bounce[env_ids] = False
+        self.task._bounce_pos[env_ids] = 0
+
+    # ------------------------------------------------------------------ the step
+    def post_physics_step(self, phase_pred, swing_type, swing_type_cycle=None):
+        """post_physics_step (:441-452) and the roll of physics_step (:365-366) after the wrapped task has stepped its physics: one kernel
+        launch.  phase_pred [N] float, swing_type [N] int: what the motion generator predicts for this step; swing_type_cycle [N] (the
+        reaction resets put -1 into the kept copy) is needed by `return_w_estimate` only."""
+        self._phase_pred.copy_(phase_pred)
+        self._swing_type.copy_(swing_type)
+        if swing_type_cycle is not None:
+            self._swing_type_cycle.copy_(swing_type_cycle)
+        self._sub_rewards_names = launch_step(self.settings, self._tensors(), self.num_envs)
+        self.extras["terminate"] = self._terminate_buf
+        self.extras["sub_rewards"] = self._sub_rewards
+        self.extras["sub_rewards_names"] = self._sub_rewards_names
