@@ -298,7 +298,7 @@ int v2p_tennis_task_obs(const v2p_tennis_cfg* c, int64_t num_envs, const v2p_ten
 int v2p_env_reset(v2p_env* e, const int64_t* env_ids, int64_t n, const float* motion_times, void* stream) {
     if (!e || !motion_times || n < 0 || n > e->n) { set_error("v2p_env_reset: bad argument"); return V2P_ERR_INVALID; }
     DeviceGuard g(e->device);
-    if (!env_ids || n == e->n) e->build_latched = 0;  // an epoch boundary: the next launch may choose its build anew (kernel_build 0)
+    if (!env_ids || n == e->n) e->sched.build_latched = 0;  // an epoch boundary: the next launch may choose its build anew (kernel_build 0)
     if (e->buf.context_feat) e->context_built = 1;
     return launch_env_reset(e, env_ids, env_ids ? n : e->n, motion_times, (hipStream_t)stream);
 }
@@ -441,9 +441,9 @@ int v2p_env_debug_pairing(v2p_env* e, int32_t* perm, int32_t* key, void* stream)
     if (!e || !perm || !key) { set_error("v2p_env_debug_pairing: bad argument"); return V2P_ERR_INVALID; }
     DeviceGuard g(e->device);
     int rc = V2P_OK;
-    if (env_pairing_on(e) && e->pair_have) rc = launch_env_pairing(e, (hipStream_t)stream);
-    if (rc == V2P_OK) rc = check_hip(hipMemcpyAsync(perm, e->perm, sizeof(int32_t) * (size_t)e->n, hipMemcpyDeviceToDevice, (hipStream_t)stream), "hipMemcpyAsync(perm)");
-    if (rc == V2P_OK) rc = check_hip(hipMemcpyAsync(key, e->pair_key, sizeof(int32_t) * (size_t)e->n, hipMemcpyDeviceToDevice, (hipStream_t)stream), "hipMemcpyAsync(pair_key)");
+    if (env_pairing_on(e) && e->sched.pair_have) rc = launch_env_pairing(e, (hipStream_t)stream);
+    if (rc == V2P_OK) rc = check_hip(hipMemcpyAsync(perm, e->sched.perm, sizeof(int32_t) * (size_t)e->n, hipMemcpyDeviceToDevice, (hipStream_t)stream), "hipMemcpyAsync(perm)");
+    if (rc == V2P_OK) rc = check_hip(hipMemcpyAsync(key, e->sched.pair_key, sizeof(int32_t) * (size_t)e->n, hipMemcpyDeviceToDevice, (hipStream_t)stream), "hipMemcpyAsync(pair_key)");
     return rc;
 }
 

@@ -1,10 +1,9 @@
-// The life of a batch (v2p_env), host code only: create and destroy, the engine's schedule defaults, the launch-by-launch choice of kernel
-// build, ball and racket attachment, the substep jobs' counters and the profiling events.  Every allocation goes through the batch's
-// DeviceOwner (e->own): nothing here frees by hand.
+// The life of a batch (v2p_env), host code only: create and destroy, ball and racket attachment, the substep jobs' counters and the
+// profiling events.  How a physics launch is scheduled is not decided here: ll_schedule.hpp, applied by physics_ll_host.hip.  Every
+// allocation goes through the batch's DeviceOwner (e->own): nothing here frees by hand.
 #include <stdio.h>
 #include <string.h>
 
-#include <atomic>
 #include <memory>
 #include <new>
 #include <vector>
@@ -12,57 +11,9 @@
 #include "v2p_internal.hpp"
 #include "phys_common.hpp"
 
-// The link-per-lane physics kernel is in the library TWICE (physics_ll.hip): the default object (168 VGPRs, three waves per
-// SIMD, contact records and phase-dead values parked in LDS) behind launch_env_physics_ll, and the register build (256 VGPRs, two waves
-// per SIMD, everything in registers) behind launch_env_physics_ll_regs.  Where a launch is as long as its heaviest env pair - up to
-// ~5000 envs on one GPU - the register build is 7 - 12 % faster (no LDS round trips in the heaviest wave's chain; compiled for ILP), where
-// the wave slots are full the LDS build is 15 % faster (profiles/r04e_dual_build.txt).
-
 using namespace v2p;
 
-// envs resident per device (live v2p_env batches of this process): what kernel_build = 0 decides by, launch by launch
-static std::atomic<int64_t> g_resident_envs[64];
-static int64_t resident_envs(int device) { return (device >= 0 && device < 64) ? g_resident_envs[device].load(std::memory_order_relaxed) : 0; }
-static constexpr int64_t REGS_BUILD_MAX_ENVS = 5120;  // measured crossover of the two builds (profiles/r04e_dual_build.txt)
-
 v2p_env::~v2p_env() { delete ball; }
-
-// ---------------------------------------------------------------------------- the engine's schedule defaults
-// What the engine takes where v2p_sim_cfg leaves a schedule field to it - the ONE statement of that policy: batch creation, the build
-// choice of a launch and ball attachment all ask here.
-struct EngineDefaults {
-    int pair_mix_permille, job_mono_permille;
-    int job_len, job_lead;  // 0 / -1: decided launch by launch (see launch_env_physics_ll)
-    long job_timeout_spins;
-};
-static EngineDefaults engine_defaults(int64_t n, bool joint_limits, bool regs_build, bool ball) {
-    EngineDefaults d;
-    // (mixing trades total work for a shorter critical path: it pays while the launch is as long as its heaviest pair, i.e. up to
-    // ~4 env pairs per wave slot; beyond that the launch is throughput bound and pairs of equals are cheaper)
-    // (the kernels with joint-limit rows or a ball run 2 waves per SIMD: there pairs of equals measured best, profiles/r02g_racket_ball_sweep.txt)
-    const bool mix = n <= 12288 && !joint_limits && !ball;
-    // defaults: measured best.  Round 2 (profiles/r02_job_mono_sweep.txt): 250 / 250; re-swept on the round-4 kernel (profiles/r04_mono_mix_sweep.txt:
-    // 5 x 4 grid at 8192 envs, then across TGS / djokovic / per-clip shapes / 4096 and 12288 envs): 60 / 150 is +1 .. 2 % everywhere - with the
-    // walk the heaviest chains are shorter, fewer pairs need to keep their substeps in one workgroup
-    // (the register build runs where a launch is as long as its heaviest wave: there every heavy env takes a light partner, 500 - +1.3 % at 1024
-    // and 4096 envs against 150, profiles/r04e_dual_build.txt)
-    d.pair_mix_permille = mix ? (regs_build ? 500 : 150) : 0;
-    // (above 12288 envs, with joint limits or with a ball - where the heavy x light mix is off - 250 stays 0.2 .. 1 % better)
-    d.job_mono_permille = mix ? 60 : 250;
-    // substeps per job: 1 while the launch is short of jobs, 2 once there are plenty (>= CUs x 32 env pairs: measured crossover at
-    // 16384 envs - a job's prologue / hand-over is ~8 % of a one-substep job); v2p_sim_cfg.job_len: A/B switch
-    d.job_len = 0;
-    d.job_lead = -1;
-    d.job_timeout_spins = 50000l;  // ~20 ms: far beyond the longest chain of substeps of a launch
-    return d;
-}
-// ... applied to the fields of a batch that were left to the engine
-static EngineDefaults apply_engine_defaults(v2p_env* e) {
-    const EngineDefaults d = engine_defaults(e->n, e->p.joint_limits != 0, e->ll_regs_build != 0, e->ball != nullptr);
-    if (e->pair_mix_default) e->pair_mix_permille = d.pair_mix_permille;
-    if (e->job_mono_default) e->job_mono_permille = d.job_mono_permille;
-    return d;
-}
 
 // ---------------------------------------------------------------------------- create
 // 1. check: pure host code.  Arguments first, then buffers, then sim parameters, then the enumerated config fields.
@@ -149,31 +100,6 @@ static void fill_env_params(const v2p_sim_cfg* c, const DevShape& shape, EnvPara
     joint_augmentation(shape, p.h, p.aug);
 }
 
-// 3. the schedule of the batch: what the cfg says, the engine's defaults where it leaves a field to the engine
-static void fill_env_schedule(v2p_env* e, const v2p_sim_cfg* c) {
-    e->schedule = e->num_shapes > 1 ? 0 : c->schedule;  // the env-per-lane cross-check kernel is single-shape
-    e->substeps_per_sim = c->substeps;
-    e->pair_period = c->pair_envs_by_load ? 1 : 0;
-    e->substep_jobs = c->substep_jobs ? 1 : 0;
-    e->job_interleave = c->job_no_interleave ? 0 : 1;  // (A/B switch)
-    // which build of the link-per-lane kernel this batch runs (see the head of this file): v2p_sim_cfg.kernel_build, 0 = by the number of
-    // envs RESIDENT on the device - the batches of a process that share a GPU (rollout groups) are bound by instruction issue together,
-    // whatever the size of each - re-evaluated launch by launch (choose_build); the value here is the one a lone batch would get
-    e->kernel_build = c->kernel_build;
-    e->ll_regs_build = c->kernel_build ? (c->kernel_build == 2) : (resident_envs(e->device) + e->n <= REGS_BUILD_MAX_ENVS);
-    e->pair_mix_default = c->pair_mix_permille < 0 ? 1 : 0;
-    e->pair_mix_permille = c->pair_mix_permille;
-    e->job_mono_default = c->job_mono_permille < 0 ? 1 : 0;
-    e->job_mono_permille = c->job_mono_permille;
-    const EngineDefaults d = apply_engine_defaults(e);
-    if (e->substep_jobs) {
-        // (job_timeout_spins < 0: tests force the recovery path)
-        e->job_timeout_spins = c->job_timeout_spins == 0 ? d.job_timeout_spins : (c->job_timeout_spins < 0 ? 0l : (long)c->job_timeout_spins);
-        e->job_len = c->job_len > 0 ? c->job_len : d.job_len;
-        e->job_lead = c->job_lead == 0 ? d.job_lead : (c->job_lead < 0 ? 0 : c->job_lead);
-    }
-}
-
 namespace v2p {
 // out[N][525] + ws: only the env-per-lane cross-check schedule stages through global memory.  Both or neither.
 int ensure_env_per_lane_buffers(v2p_env* e) {
@@ -216,24 +142,23 @@ static int alloc_env(v2p_env* e, const v2p_model* const* shapes, const int32_t* 
         if (rc == V2P_OK) rc = own.alloc(&e->shape_aug_dev, aug.size(), "shape_aug", NONE, aug.data());
         if (rc == V2P_OK) rc = own.alloc(&e->env_shape_dev, N, "env_shape", NONE, env_shape_id);
     }
-    if (rc == V2P_OK && e->substep_jobs) {
-        rc = own.alloc(&e->job_progress, (size_t)job_wave_slots(e->n) + 2, "job_progress", Z);
+    if (rc == V2P_OK && e->sched.job.on) {
+        rc = own.alloc(&e->sched.job_progress, (size_t)job_wave_slots(e->n) + 2, "job_progress", Z);
         // the state as the jobs hand it over: 50 16-byte chunks per env (see physics_ll.hip)
-        if (rc == V2P_OK) rc = own.alloc(&e->job_hand, HAND_FLOATS * N * (nsub > 1 ? nsub - 1 : 1), "job_hand");
+        if (rc == V2P_OK) rc = own.alloc(&e->sched.job_hand, HAND_FLOATS * N * (nsub > 1 ? nsub - 1 : 1), "job_hand");
     }
     std::vector<int32_t> iota(N);
     for (size_t i = 0; i < N; ++i) iota[i] = (int32_t)i;
-    if (rc == V2P_OK) rc = own.alloc(&e->pair_key, N, "pair_key", Z);
-    if (rc == V2P_OK) rc = own.alloc(&e->pair_pos, N, "pair_pos", NONE, iota.data());
-    if (rc == V2P_OK) rc = own.alloc(&e->perm, N, "perm", NONE, iota.data());
-    if (rc == V2P_OK) rc = own.alloc(&e->pair_hist, (size_t)(4 * PAIR_BINS + 1), "pair_hist", Z);
-    for (int k = 0; k < 2 && rc == V2P_OK; ++k) rc = own.alloc(&e->pair_list[k], PAIR_BINS * N, "pair_list");
-    if (rc == V2P_OK) rc = own.alloc(&e->pair_slot_env, N, "pair_slot_env");
+    if (rc == V2P_OK) rc = own.alloc(&e->sched.pair_key, N, "pair_key", Z);
+    if (rc == V2P_OK) rc = own.alloc(&e->sched.pair_pos, N, "pair_pos", NONE, iota.data());
+    if (rc == V2P_OK) rc = own.alloc(&e->sched.perm, N, "perm", NONE, iota.data());
+    if (rc == V2P_OK) rc = own.alloc(&e->sched.pair_hist, (size_t)(4 * PAIR_BINS + 1), "pair_hist", Z);
+    for (int k = 0; k < 2 && rc == V2P_OK; ++k) rc = own.alloc(&e->sched.pair_list[k], PAIR_BINS * N, "pair_list");
+    if (rc == V2P_OK) rc = own.alloc(&e->sched.pair_slot_env, N, "pair_slot_env");
     if (rc == V2P_OK) {
-        e->pair_starts[0] = e->pair_hist + PAIR_BINS;
-        e->pair_starts[1] = e->pair_hist + 2 * PAIR_BINS;
-        e->pair_start = e->pair_starts[0];
-        e->pair_done = e->pair_hist + 4 * PAIR_BINS;
+        e->sched.pair_starts[0] = e->sched.pair_hist + PAIR_BINS;
+        e->sched.pair_starts[1] = e->sched.pair_hist + 2 * PAIR_BINS;
+        e->sched.pair_done = e->sched.pair_hist + 4 * PAIR_BINS;
         rc = check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize(env_create)");
     }
     // (one record per wave; per JOB in a V2P_LL_TIMELINE build: up to nsub per wave)
@@ -257,37 +182,14 @@ static int env_create_impl(const v2p_model* const* shapes, int32_t num_shapes, c
     e->device = e->own.device = device;
     e->motion_id = env_motion_id;
     fill_env_params(c, shapes[0]->host.shape, e->p);
-    fill_env_schedule(e.get(), c);
     DeviceGuard g(device);
     if (!g.ok) { set_error("v2p_env_create: cannot select device %d", device); return V2P_ERR_HIP; }
-    {   // 1 = the engine decides launch by launch: cutting pays once the env pairs no longer fit the GPU's wave slots in one round
-        // (CUs x 4 SIMDs x 3 waves; measured: at <= 2/3 of the slots whole control steps per workgroup are 0.3 ... 8 % faster); 2 = always
-        hipDeviceProp_t prop;
-        const bool have = hipGetDeviceProperties(&prop, device) == hipSuccess;
-        e->job_min_blocks = (c->substep_jobs == 1 && have) ? prop.multiProcessorCount * 8 : 0;
-        e->job_len2_blocks = have ? prop.multiProcessorCount * 32 : 8192;
-    }
+    fill_env_schedule(e.get(), c);  // 3. the schedule of the batch (physics_ll_host.hip)
     rc = alloc_env(e.get(), shapes, env_shape_id, c);
     if (rc != V2P_OK) return rc;
-    if (device >= 0 && device < 64) { g_resident_envs[device] += n; e->counted_resident = 1; }
+    count_resident_envs(e.get(), true);
     *out = e.release();
     return V2P_OK;
-}
-
-// ---------------------------------------------------------------------------- the build of a launch
-// kernel_build = 0: the build follows the envs resident on the device (a second rollout group created after this batch moves both to the
-// three-wave build); the heavy x light pairing share follows the build where it was left to the engine.  The choice is LATCHED: taken at
-// the first launch after the batch was created or reset as a whole (an epoch boundary: every env restarts from a reference state) and
-// kept until the next such reset - the two builds agree to rounding only, so a live batch must not change build in the middle of an
-// epoch because an unrelated batch (an eval task next to training) came or went (advisor r5).
-static int build_wanted(const v2p_env* e) { return resident_envs(e->device) <= REGS_BUILD_MAX_ENVS ? 1 : 0; }
-static void choose_build(v2p_env* e) {
-    if (e->kernel_build != 0 || e->build_latched) return;
-    e->build_latched = 1;
-    const int regs = build_wanted(e);
-    if (regs == e->ll_regs_build) return;
-    e->ll_regs_build = regs;
-    apply_engine_defaults(e);
 }
 
 namespace v2p {
@@ -303,7 +205,7 @@ int env_physics_launch(v2p_env* e, hipStream_t s, float* actions, int* fused_pos
     choose_build(e);
     if (rec) (void)hipEventRecord(e->prof_ev[2 * e->prof_n], s);
     int rc = e->schedule != 0 ? launch_env_physics(e, s)
-                              : (e->ll_regs_build ? launch_env_physics_ll_regs(e, s, actions, fused_post) : launch_env_physics_ll(e, s, actions, fused_post));
+                              : (e->sched.ll_regs_build ? launch_env_physics_ll_regs(e, s, actions, fused_post) : launch_env_physics_ll(e, s, actions, fused_post));
     if (rec) { (void)hipEventRecord(e->prof_ev[2 * e->prof_n + 1], s); ++e->prof_n; }
     return rc;
 }
@@ -329,7 +231,7 @@ int v2p_env_create_shapes(const v2p_model* const* shapes, int32_t num_shapes, co
 
 void v2p_env_destroy(v2p_env* e) {
     if (!e) return;
-    if (e->counted_resident) g_resident_envs[e->device] -= e->n;
+    count_resident_envs(e, false);
     DeviceGuard g(e->device);
     if (e->wave_times) {
         const size_t nw = ((size_t)e->n / 2 + 1) * (size_t)e->p.nsub;  // (records that were never written stay zero and are skipped)
@@ -435,9 +337,9 @@ int v2p_env_check(v2p_env* e, void* stream) {
     if (!e) { set_error("v2p_env_check: bad argument"); return V2P_ERR_INVALID; }
     DeviceGuard g(e->device);
     int rc = check_hip(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
-    if (rc != V2P_OK || !e->job_progress) return rc;
+    if (rc != V2P_OK || !e->sched.job_progress) return rc;
     int32_t count[2] = {0, 0};
-    rc = check_hip(hipMemcpy(count, e->job_progress + v2p::job_wave_slots(e->n), sizeof(count), hipMemcpyDeviceToHost), "hipMemcpy(job recovery counters)");
+    rc = check_hip(hipMemcpy(count, e->sched.job_progress + v2p::job_wave_slots(e->n), sizeof(count), hipMemcpyDeviceToHost), "hipMemcpy(job recovery counters)");
     if (rc == V2P_OK) { e->job_recoveries = count[0]; e->jobs_skipped = count[1]; }
     if (rc == V2P_OK && e->jobs_skipped > e->jobs_skipped_reported) {
         // a late job of a cut pair found its step complete and did not run: its substeps were replayed by its successors (results are the
@@ -453,7 +355,7 @@ int v2p_env_check(v2p_env* e, void* stream) {
 
 int v2p_env_check_async(v2p_env* e, void* stream) {
     if (!e) { set_error("v2p_env_check_async: bad argument"); return V2P_ERR_INVALID; }
-    if (!e->job_progress) return V2P_OK;
+    if (!e->sched.job_progress) return V2P_OK;
     DeviceGuard g(e->device);
     int rc = V2P_OK;
     if (!e->err_host) {
@@ -468,7 +370,7 @@ int v2p_env_check_async(v2p_env* e, void* stream) {
         e->jobs_skipped = e->err_host[1];
     }
     if (!e->err_pending) {  // fetch the counter as it stands behind everything enqueued so far; looked at by the next call
-        rc = check_hip(hipMemcpyAsync(e->err_host, e->job_progress + v2p::job_wave_slots(e->n), 2 * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream),
+        rc = check_hip(hipMemcpyAsync(e->err_host, e->sched.job_progress + v2p::job_wave_slots(e->n), 2 * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream),
                        "hipMemcpyAsync(job recovery counter)");
         if (rc == V2P_OK) rc = check_hip(hipEventRecord(e->err_event[0], (hipStream_t)stream), "hipEventRecord(job recovery counter)");
         if (rc == V2P_OK) e->err_pending = 1;
@@ -523,8 +425,7 @@ int v2p_env_profile_end(v2p_env* e, double* physics_ms_total, int64_t* launches)
 
 int v2p_env_kernel_build(const v2p_env* e) {  // (the build the NEXT launch of the batch runs)
     if (!e) return V2P_ERR_INVALID;
-    if (e->kernel_build == 0 && !e->build_latched) return build_wanted(e) ? 2 : 1;  // (read-only: what choose_build would take now)
-    return e->ll_regs_build ? 2 : 1;
+    return next_kernel_build(e);
 }
 
 }  // extern "C"

@@ -112,6 +112,17 @@ struct PhysArgs {
     PostArgs post;
 };
 
+// What both launchers of physics_ll_kernel share (physics_ll_host.hip).  ll_launch_prepare: everything of a launch that does not depend
+// on the build - the refusals, PhysArgs from the batch, the job plan, the progress epoch, fused post-physics.  blocks: env pairs of the
+// launch; diag: the build would take its instrumented instantiation, which exists for the headline configuration only and keeps whole
+// control steps per workgroup - L.diag says whether this launch is one.  ll_launch_done: behind the launch, flips the pairing tables.
+struct LlLaunch {
+    PhysArgs a;
+    unsigned grid;  // workgroups
+    bool diag;
+};
+int ll_launch_prepare(v2p_env* env, hipStream_t s, float* actions, int* fused_post, unsigned blocks, bool diag, LlLaunch& L);
+void ll_launch_done(v2p_env* env);
 
 // ---- pairing (see physics_ll_host.hip): slot of env e in the next launch = first slot of its load bin + its arrival index there
 constexpr int PAIR_BINS = 256;

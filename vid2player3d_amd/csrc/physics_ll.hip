@@ -2227,129 +2227,35 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
 }  // namespace V2P_LL_NS
 
 int V2P_LL_LAUNCHER(v2p_env* env, hipStream_t s, float* actions, int* fused_post) {
-    if (fused_post) *fused_post = 0;
-    const bool paired = env_pairing_on(env);
-    PhysArgs a = {};
-    const int buf = env->pair_buf;
-    a.pl_start = (paired && env->pair_have) ? env->pair_starts[buf] : nullptr;
-    a.pl_list = env->pair_list[buf];
-    a.pl_list_next = env->pair_list[1 - buf];
-    a.pl_mix = env_pair_view(env).mix;
-    a.pl_slot_env = env->pair_slot_env;
-    a.pair_key = env->pair_key;
-    a.pair_pos = env->pair_pos;
-    a.pair_hist = paired ? env->pair_hist : nullptr;
-    a.pair_start = env->pair_starts[1 - buf];
-    a.pair_done = env->pair_done;
-    a.model = env->model->dev;
-    a.state = env->state;
-    a.ctrl = env->ctrl;
-    a.actions = actions;  // non-null: pre-physics runs in this kernel's prologue
-    a.par_pack[0] = a.par_pack[1] = 0ull;
-    for (int i = 0; i < NB; ++i) {
-        const int par = env->model->host.parents[i] < 0 ? 0 : env->model->host.parents[i];
-        a.par_pack[i / 12] |= (unsigned long long)par << (5 * (i % 12));
-    }
-    a.reset = env->buf.reset;
-    a.pd_target = env->buf.pd_target;
-    a.out = env->out;
-    a.ws = env->ws;
-    a.contact_ids = env->contact_ids;
-    a.contact_ids_sub = env->contact_ids_sub;
-    a.x_root = env->buf.root_states;
-    a.x_dof = env->buf.dof_state;
-    a.x_rb = env->buf.rb_state;
-    a.x_contact = env->buf.contact_force;
-    a.x_dof_force = env->buf.dof_force;
-    a.prof = env->prof;
-    a.prof_heavy = debug_env("V2P_PHASE_HEAVY") ? 1 : 0;  // diagnostics: sample the 8 heaviest waves instead of every 64th
-    a.wave_times = env->wave_times;
-    a.n = env->n;
-    a.p = env->p;
-    unsigned blocks = (unsigned)((env->n + 2 * LL_WPB - 1) / (2 * LL_WPB));
-    a.shapes = env->shapes_dev;
-    a.env_shape = env->env_shape_dev;
-    a.shape_aug = env->shape_aug_dev;
-    const bool multi = env->num_shapes > 1;  // per-env shapes: hull vertices come from the shape tables instead of the LDS copy
-    const dim3 grid(blocks), block(64 * LL_WPB);
+    const unsigned blocks = (unsigned)((env->n + 2 * LL_WPB - 1) / (2 * LL_WPB));
+    const dim3 block(64 * LL_WPB);
     const size_t lds = sizeof(float) * LDS_FLOATS_PER_WAVE * LL_WPB;
-    const bool tgs = env->p.solver_type == 1;
 #if defined(V2P_LL_TIMELINE)
-    const bool diag = a.prof != nullptr;
+    const bool diag = env->prof != nullptr;
 #else
-    const bool diag = a.prof || a.wave_times;
+    const bool diag = env->prof || env->wave_times;
 #endif
-    if (env->ball) a.ball = *env->ball;
+    // everything of the launch that is the same in both builds: the refusals, the kernel's arguments, the job plan (physics_ll_host.hip)
+    LlLaunch launch;
+    const int rc = ll_launch_prepare(env, s, actions, fused_post, blocks, diag, launch);
+    if (rc != V2P_OK) return rc;
+    const PhysArgs& a = launch.a;
+    const dim3 grid(launch.grid);
     // ONE instantiation whether the launch is cut into substep jobs or not (job_mono = every pair: whole control steps per workgroup,
     // nothing handed over): "substep jobs are invisible" holds by construction - two instantiations of the template are two
     // compilations, and under -fassociative-math nothing makes them round alike
-    a.job_blocks = (int)blocks;
-    a.job_progress = env->job_progress;
-    a.job_hand = env->job_hand;
-    a.job_timeout_spins = env->job_timeout_spins;
-    a.job_interleave = env->job_interleave;
-    a.job_len = 1;
-    a.job_lead = 1;
-    a.job_mono = (int)blocks;
-    auto job_grid = [&](int& rc) -> dim3 {
-        rc = V2P_OK;
-        const bool cut = env->substep_jobs && env->job_progress && blocks > 1 && (int)blocks > env->job_min_blocks;
-        if (cut) {
-            // substep jobs: one launch of job_mono + nsub x (blocks - job_mono) workgroups, substep-major
-            a.job_epoch = ++env->job_epoch;
-            if (env->job_epoch > (1 << 30) / (env->p.nsub + 1) - 2) env->job_epoch = 0;  // (wraps before the progress words overflow; a wrap needs them cleared)
-            if (env->job_epoch == 0) {
-                rc = check_hip(hipMemsetAsync(env->job_progress, 0, sizeof(int) * (size_t)job_wave_slots(env->n), s), "hipMemsetAsync(job_progress)");  // (not the error word behind them)
-                a.job_epoch = env->job_epoch = 1;
-            }
-            a.job_mono = (int)(blocks * (unsigned)env->job_mono_permille / 1000u);
-        }
-        a.job_len = !cut ? 1 : (env->job_len >= 1 ? env->job_len : (((int)blocks >= env->job_len2_blocks && env->p.nsub % 2 == 0) ? 2 : 1));
-        // (job_lead: substeps of the first job of a cut pair; 0 / out of range = job_len, i.e. jobs of equal length; -1 = the engine's
-        // choice: with one-substep jobs the first job takes two substeps - one hand-over less per pair (a third of the hand-over traffic
-        // at four substeps) while the jobs that END a launch stay one substep long; measured +0.3 % at 8192 envs, +1.3 % at 12288, three
-        // substeps in the first job -4.7 %: profiles/r04_job_lead.txt)
-        // (not with a ball: 12.68 vs 12.79 M)
-        const int lead_req = env->job_lead >= 0 ? env->job_lead : ((a.job_len == 1 && env->p.nsub >= 4 && !env->ball) ? 2 : 0);
-        a.job_lead = (cut && lead_req >= 1 && lead_req < env->p.nsub) ? lead_req : a.job_len;
-        const unsigned njobs = 1u + (unsigned)((env->p.nsub - a.job_lead + a.job_len - 1) / a.job_len);
-        return dim3((unsigned)a.job_mono + (blocks - (unsigned)a.job_mono) * njobs);
-    };
-    // every production instantiation is cut into substep jobs and runs post-physics in the epilogue of an env's last job (v2p_env_step);
-    // the instrumented build (DIAG) exists for the headline configuration only and keeps whole control steps per workgroup
-    auto with_post = [&]() {
-        if (fused_post && actions && env->mlib) {
-            a.post.b = env->buf;
-            a.post.t = env->mlib->t;
-            a.post.motion_id = env->motion_id;
-            a.post.cur = env->cur_target;
-            a.post.on = 1;
-            *fused_post = 1;
-        }
-    };
-    if (env->p.joint_limits && !env->p.enable_contact) {
-        set_error("physics: joint limits run with contacts on");
-        return V2P_ERR_UNSUPPORTED;
-    }
-    if (env->ball && !env->p.enable_contact) {
-        set_error("physics: racket + ball runs with contacts on");
-        return V2P_ERR_UNSUPPORTED;
-    }
-    if (diag && env->p.enable_contact && !tgs && !multi && !env->ball && !env->p.joint_limits && env->p.friction_frame == 0) {
+    if (launch.diag) {
         hipLaunchKernelGGL((physics_ll_kernel<true, false, false, true, false, false, false>), grid, block, lds, s, a);
     } else {
-        int rc0;
-        const dim3 jgrid = job_grid(rc0);
-        if (rc0 != V2P_OK) return rc0;
-        with_post();
-        const bool lim = env->p.joint_limits != 0, ball = env->ball != nullptr, con = env->p.enable_contact != 0;
+        const bool multi = env->num_shapes > 1;  // per-env shapes: hull vertices come from the shape tables instead of the LDS copy
+        const bool tgs = env->p.solver_type == 1, lim = env->p.joint_limits != 0, ball = env->ball != nullptr, con = env->p.enable_contact != 0;
         const bool vfric = env->p.friction_frame == 1 && con;
 #define V2P_LL_LAUNCH(C, T, B, L) do { \
             if (vfric && C) { \
-                if (multi) hipLaunchKernelGGL((physics_ll_kernel<C, true, T, false, B, true, L, C>), jgrid, block, lds, s, a); \
-                else hipLaunchKernelGGL((physics_ll_kernel<C, false, T, false, B, true, L, C>), jgrid, block, lds, s, a); \
-            } else if (multi) hipLaunchKernelGGL((physics_ll_kernel<C, true, T, false, B, true, L>), jgrid, block, lds, s, a); \
-            else hipLaunchKernelGGL((physics_ll_kernel<C, false, T, false, B, true, L>), jgrid, block, lds, s, a); } while (0)
+                if (multi) hipLaunchKernelGGL((physics_ll_kernel<C, true, T, false, B, true, L, C>), grid, block, lds, s, a); \
+                else hipLaunchKernelGGL((physics_ll_kernel<C, false, T, false, B, true, L, C>), grid, block, lds, s, a); \
+            } else if (multi) hipLaunchKernelGGL((physics_ll_kernel<C, true, T, false, B, true, L>), grid, block, lds, s, a); \
+            else hipLaunchKernelGGL((physics_ll_kernel<C, false, T, false, B, true, L>), grid, block, lds, s, a); } while (0)
         if (lim && ball && tgs) V2P_LL_LAUNCH(true, true, true, true);
         else if (lim && ball) V2P_LL_LAUNCH(true, false, true, true);
         else if (lim && tgs) V2P_LL_LAUNCH(true, true, false, true);
@@ -2361,11 +2267,7 @@ int V2P_LL_LAUNCHER(v2p_env* env, hipStream_t s, float* actions, int* fused_post
         else V2P_LL_LAUNCH(false, false, false, false);
 #undef V2P_LL_LAUNCH
     }
-    if (paired) {  // the tables this launch has filled are what the next one reads
-        env->pair_buf = 1 - buf;
-        env->pair_start = env->pair_starts[env->pair_buf];
-        env->pair_have = 1;
-    }
+    ll_launch_done(env);
     return check_hip(hipGetLastError(), "physics_ll_kernel");
 }
 

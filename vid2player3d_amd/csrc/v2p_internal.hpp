@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/v2p_rollout.h"
+#include "ll_schedule.hpp"
 
 namespace v2p {
 
@@ -206,40 +207,11 @@ struct v2p_env {
     int32_t* contact_ids_sub = {}; // [N,nsub,24,4] debug, every substep (v2p_sim_cfg.debug_substep_contacts), else NULL
     long long* prof = {};          // [8] phase cycle counters when V2P_PHASE_TIMING is set (device), else NULL
     long long* wave_times = {};    // [waves][4] per-wave wall-clock stamps of the last launch when V2P_WAVE_TIMES=<file> is set
-    // pairing (physics_ll.hip): envs are handed to waves in descending order of their contact load
-    int32_t* pair_key = {};        // [N] load key of each env after the last physics launch (0..255)
-    int32_t* pair_pos = {};        // [N] arrival index inside its load bin
-    int32_t* pair_hist = {};       // [256] + pair_start [256] + pair_done [1] (one allocation)
-    int32_t* pair_start = {};
-    int32_t* pair_done = {};
-    int32_t* perm = {};            // [N] wave slot -> env of the next physics launch, materialised for v2p_env_debug_pairing only
-    int32_t* pair_list[2] = {};    // [256][N] envs of each load bin in arrival order: what the NEXT launch looks its envs up in (double
-    int32_t* pair_starts[2] = {};  // [256]    first rank of each bin                  buffered: a launch reads one set and fills the other)
-    int pair_buf = {};             // the set the next launch reads
-    int job_mono_default = {};     // job_mono_permille was left at its default (v2p_env_attach_ball moves it)
-    int32_t* pair_slot_env = {};   // [N] env of each wave slot of the running launch: looked up by the job of the first substep, read by the later ones
-    int pair_period = {};          // 0 = pairing off (v2p_sim_cfg.pair_envs_by_load = 0), else on
+    v2p::LlSchedule sched = {};    // pairing, substep jobs, kernel build: the launch policy of the link-per-lane schedule (ll_schedule.hpp)
     int substeps_per_sim = {};     // substeps of one simulate() call
-    int substep_jobs = {};         // v2p_sim_cfg.substep_jobs: the physics launch is cut into (substep, env pair) jobs
-    int job_min_blocks = {};       // ... when it has more env pairs than this (0: always)
-    int32_t* job_progress = {};    // [waves + 1] progress word per wave slot, last = error flag
-    float* job_hand = {};          // [nsub - 1][N][HAND_FLOATS] the state as one substep job hands it to the next (16-byte chunks), a slot per substep
-    long job_timeout_spins = {};   // see PhysArgs
-    int job_interleave = {};
-    int job_len = {};              // substeps per job; 0 = the engine decides (2 for launches of >= job_len2_blocks env pairs, else 1)
-    int job_len2_blocks = {};
-    int ll_regs_build = {};        // 1: this batch runs the register build of the link-per-lane kernel (two waves per SIMD)
-    int kernel_build = {};         // v2p_sim_cfg.kernel_build (0: ll_regs_build follows the envs resident on the device)
-    int build_latched = {};        // kernel_build 0: the choice is taken at the first launch after creation / after a whole-batch reset and holds until the next one
-    int counted_resident = {};     // this batch is in the device's resident-env count
-    int job_lead = {};             // substeps of the FIRST job of a cut pair (0 = like the others, -1 = the engine decides)
     int64_t job_recoveries = {};   // jobs that gave up waiting and recomputed, as last fetched (v2p_env_check / _check_async)
     int64_t jobs_skipped = {};     // late jobs that found their pair's step complete and did not run (their per-call records are missing for that step)
     int64_t jobs_skipped_reported = {};
-    int job_epoch = {};
-    int pair_mix_permille = {};    // share of the envs (the heaviest) that are paired with the lightest ones instead of with each other
-    int pair_mix_default = {};     // pair_mix_permille was left to the engine (-1)
-    int job_mono_permille = {};    // share of the env pairs (the heaviest) whose substeps stay in one workgroup
     v2p::BallDev* ball = {};       // racket + ball attached (v2p_env_attach_ball), else NULL
     int32_t* err_host = {};        // pinned copy of the substep jobs' error word (v2p_env_check_async), lazily allocated
     hipEvent_t* err_event = {};    // [1] recorded behind the copy into err_host
@@ -248,7 +220,6 @@ struct v2p_env {
     int64_t prof_cap = {}, prof_n = {};
     int64_t prof_seen = {};        // physics launches since v2p_env_profile_begin
     int32_t prof_stride = {}, prof_period = {};  // which of them are bracketed (v2p_env_profile_begin_sampled)
-    int pair_have = {};            // the last physics launch left (key, pos, start) that have not been scattered into perm yet
     v2p::CtxTransform ctx = {};    // context frame width + transform (v2p_env_set_context_transform)
     int context_built = {};        // a reset / context call has written frames: the width is fixed from now on
     v2p::DeviceOwner own;          // owns every engine-side allocation the pointers above name (the ball's contact_part / rackets too)
@@ -321,6 +292,12 @@ int launch_env_physics(v2p_env* e, hipStream_t s);
 int launch_env_physics_ll(v2p_env* e, hipStream_t s, float* actions = nullptr, int* fused_post = nullptr);
 // the same kernel in the library's register build (physics_ll.hip compiled a second time: two waves per SIMD, nothing parked in LDS)
 int launch_env_physics_ll_regs(v2p_env* e, hipStream_t s, float* actions = nullptr, int* fused_post = nullptr);
+// the launch policy applied to a batch (physics_ll_host.hip; the decisions themselves: ll_schedule.hpp)
+void fill_env_schedule(v2p_env* e, const v2p_sim_cfg* c);  // what the cfg says, the engine's defaults where it leaves a field to the engine
+EngineDefaults apply_engine_defaults(v2p_env* e);          // ... again, after what they depend on has changed (ball attached, build chosen)
+void count_resident_envs(v2p_env* e, bool live);           // the batch enters / leaves the count of envs resident on its device
+void choose_build(v2p_env* e);                             // kernel_build 0: latches the build at the first launch of an epoch
+int next_kernel_build(const v2p_env* e);                   // 1 / 2: the build the next launch of the batch runs
 bool env_pairing_on(const v2p_env* e);
 struct PairView;
 PairView env_pair_view(const v2p_env* e);
