@@ -183,6 +183,36 @@ __device__ __forceinline__ void grp_argmin(float& v, int& k) {
 __device__ __forceinline__ void grp_argmax(float& v, int& k) {
     grp_arg_step<true>(v, k, grp_xor1); grp_arg_step<true>(v, k, grp_xor2); grp_arg_step<true>(v, k, grp_mirror);
 }
+// ... in two reductions of ONE value each instead of a (value, index) pair under a three-way comparison: the extreme itself
+// (v_min / v_max on the DPP network), then the lowest index among the lanes that hold it.  The same winner: a lane's own index is the
+// first of its slots that attains the lane's extreme, and an empty lane (index -1) takes no part.  A third of the instructions of
+// grp_argmin / grp_argmax; it needs two registers more while it runs, which the racket + ball and joint-limit instantiations do not
+// have (their scratch grew by 8 - 20 B per lane with it; in the register build the TGS kernels' too), so those keep the pairwise
+// form (FAST = false).
+__device__ __forceinline__ float grp_fmin(float v) {
+    v = fminf(v, __uint_as_float(grp_xor1(__float_as_uint(v)))); v = fminf(v, __uint_as_float(grp_xor2(__float_as_uint(v)))); v = fminf(v, __uint_as_float(grp_mirror(__float_as_uint(v))));
+    return v;
+}
+__device__ __forceinline__ float grp_fmax(float v) {
+    v = fmaxf(v, __uint_as_float(grp_xor1(__float_as_uint(v)))); v = fmaxf(v, __uint_as_float(grp_xor2(__float_as_uint(v)))); v = fmaxf(v, __uint_as_float(grp_mirror(__float_as_uint(v))));
+    return v;
+}
+__device__ __forceinline__ unsigned grp_umin(unsigned v) {
+    unsigned o = grp_xor1(v); v = o < v ? o : v; o = grp_xor2(v); v = o < v ? o : v; o = grp_mirror(v); v = o < v ? o : v;
+    return v;
+}
+template <bool MAX, bool FAST>
+__device__ __forceinline__ void grp_arg(float& v, int& k) {
+    if (!FAST) {
+        if (MAX) grp_argmax(v, k); else grp_argmin(v, k);
+        return;
+    }
+    const float m = k < 0 ? (MAX ? -3.0e38f : 3.0e38f) : v;
+    const float g = MAX ? grp_fmax(m) : grp_fmin(m);
+    const unsigned c = grp_umin((k >= 0 && m == g) ? (unsigned)k : 0x7fffffffu);
+    k = c == 0x7fffffffu ? -1 : (int)c;
+    v = g;
+}
 
 #define LLSUB(k) do { if (DIAG && a.prof) { long long t_ = clock64(); if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t_ - tsub)); tsub = t_; } } while (0)
 #define LLPH(k) do { if (DIAG && a.prof) { long long t_ = clock64(); if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t_ - tprev)); tprev = t_; } } while (0)
@@ -1092,6 +1122,11 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 const int rounds = (ntot + 7) >> 3;
                 const int myk = (half ? nr0 : 0) + __popc(nm & ((1u << lb) - 1u));  // rank of this link among the near links of the wave
                 const int grp = lane >> 3, gl = lane & 7;
+#ifdef V2P_LL_REGS_BUILD
+                constexpr bool FASTARG = !BALL && !LIMITS && !TGS && !DIAG;  // (see grp_arg; the register build spills in its TGS kernels with it)
+#else
+                constexpr bool FASTARG = !BALL && !LIMITS;
+#endif
                 int* const scr = (int*)(park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + PARK_SCR * 64);  // k-th near link -> its lane
                 if (near) scr[myk] = lane;
                 if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[13], (unsigned long long)rounds);
@@ -1139,7 +1174,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     clo |= grp_xor1(clo); chi |= grp_xor1(chi);
                     clo |= grp_xor2(clo); chi |= grp_xor2(chi);
                     clo |= grp_mirror(clo); chi |= grp_mirror(chi);
-                    grp_argmin(zmin, k0);
+                    grp_arg<false, FASTARG>(zmin, k0);
                     const unsigned long long cm = ((unsigned long long)chi << 32) | clo;
                     const int cntg = __popc(clo) + __popc(chi);
                     unsigned long long t = cm;
@@ -1169,7 +1204,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             best = take ? d2 : best;
                             k1 = take ? 8 * k + gl : k1;
                         }
-                        grp_argmax(best, k1);
+                        grp_arg<true, FASTARG>(best, k1);
                         const int k1s = k1 < 0 ? 0 : k1;
                         const float4 u1 = hullv(v0L + k1s);
                         const float ex = xx + r0 * u1.x + r1 * u1.y + r2 * u1.z - p0x;
@@ -1188,8 +1223,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             amax = up ? area : amax; k2 = up ? 8 * k + gl : k2;
                             amin = dn ? area : amin; k3 = dn ? 8 * k + gl : k3;
                         }
-                        grp_argmax(amax, k2);
-                        grp_argmin(amin, k3);
+                        grp_arg<true, FASTARG>(amax, k2);
+                        grp_arg<false, FASTARG>(amin, k3);
                         if (big) {
                             s0 = k0; s1 = k1;
                             s2 = k2 >= 0 ? k2 : k3;
