@@ -954,13 +954,24 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
 #pragma unroll
         for (int i = 0; i < 9; ++i) E.m[i] = 0.f;
         V3 u{0.f, 0.f, 0.f};
-        for (int d = maxd; d >= 1; --d) {
-            Sym3 cA{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, cC{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            M3 cB;
+        // A level's contributions are written by the lanes at that depth only and stay in their registers (no zero-fill per level: the
+        // other lanes keep what they last wrote).  The receiving adds run under an EXEC mask instead: the parents of the level - and,
+        // with them, every lane at depth >= d.  Those have to stay switched on, because a DPP shift or a ds_bpermute returns 0 for a
+        // source lane that EXEC has switched off, and they are the sources; what they add onto their own A, B, C, pn, pf in passing is
+        // never read: a link's own level is the last to read them (only the root's are read after the loop, and the root, depth 0, is
+        // never among these lanes).  Links are in depth-first order: the lane after a parent with a first child is that child, at
+        // depth d.  The sums of the values that are used are the same adds as with zero-filled contributions and selects.
+        Sym3 cA{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, cC{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        M3 cB;
 #pragma unroll
-            for (int i = 0; i < 9; ++i) cB.m[i] = 0.f;
-            V3 cn{0.f, 0.f, 0.f}, cf{0.f, 0.f, 0.f};
-            if (dep == d) {
+        for (int i = 0; i < 9; ++i) cB.m[i] = 0.f;
+        V3 cn{0.f, 0.f, 0.f}, cf{0.f, 0.f, 0.f};
+        for (int d = maxd; d >= 1; --d) {
+            // (the comparisons below read an opaque scalar copy of the level: comparing `dep` with the loop counter itself lets value
+            // numbering put the per-lane `dep` in the counter's place, and the loop then runs with its counter in a VGPR and per-lane exits)
+            int dl = d;
+            asm volatile("" : "+s"(dl));
+            if (dep == dl) {
                 Sym3 D{A.xx + aug, A.xy, A.xz, A.yy + aug, A.yz, A.zz + aug};
                 Di = inv(D);
                 E = mul(Di, B);
@@ -990,18 +1001,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 cn = pan + cross(r, paf);
                 cf = paf;
             }
-            // parents (depth d-1) pull their children's contributions; contributions of lanes that are not at depth d are zero
-            if ((nonchain >> d) & 1) {
-                A = A + mask(has0, from_next(cA));
-                C = C + mask(has0, from_next(cC));
-                M3 t = from_next(cB);
-#pragma unroll
-                for (int i = 0; i < 9; ++i) B.m[i] += has0 ? t.m[i] : 0.f;
-                pn = pn + mask(has0, from_next(cn));
-                pf = pf + mask(has0, from_next(cf));
-            } else {
-                // every link of this level directly follows its parent: whatever the next lane contributes is this lane's child's
-                // (lanes at other depths contribute zeros), so the shifted values are added unmasked (DPP operand of the add)
+            if (dep >= dl || (dep == dl - 1 && has0)) {
                 A = A + from_next(cA);
                 C = C + from_next(cC);
                 M3 t = from_next(cB);
@@ -1015,13 +1015,15 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 for (int sl = 1; sl <= 2; ++sl) {  // one extra child at a time keeps the register peak down
                     const int cl = sl == 1 ? cl1 : cl2;
                     const bool hs = sl == 1 ? has1 : has2;
-                    A = A + mask(hs, pull(cA, cl));
-                    C = C + mask(hs, pull(cC, cl));
-                    M3 t1 = pull(cB, cl);
+                    if (dep >= dl || (dep == dl - 1 && hs)) {
+                        A = A + pull(cA, cl);
+                        C = C + pull(cC, cl);
+                        M3 t1 = pull(cB, cl);
 #pragma unroll
-                    for (int i = 0; i < 9; ++i) B.m[i] += hs ? t1.m[i] : 0.f;
-                    pn = pn + mask(hs, pull(cn, cl));
-                    pf = pf + mask(hs, pull(cf, cl));
+                        for (int i = 0; i < 9; ++i) B.m[i] += t1.m[i];
+                        pn = pn + pull(cn, cl);
+                        pf = pf + pull(cf, cl);
+                    }
                 }
             }
         }
