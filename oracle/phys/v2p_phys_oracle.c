@@ -693,7 +693,7 @@ static int substep_impl(const v2p_omodel *m, const v2p_oparams *p, v2p_ostate *s
          * (PhysX: one per overlapping pair; the MAXH nearest are kept), found at the start of the substep; activation and bias exactly
          * like a racket point; the rows of a link's point are solved right after that link's ground points.  A ball centre INSIDE a hull (more than a radius deep:
          * not reachable through the speculative rows unless it is placed there) is pushed out along the direction from the centre of
-         * the hull's body-frame bounding box. */
+         * the hull's body-frame bounding box, along the body's +z within 1e-5 m of that centre. */
         g_hull_rows = 0;
 #define MAXH 3 /* hull points kept per ball: the nearest links (the engine's LDS block holds three next to the cylinders' two) */
         int nhull = 0, hull_link[MAXH];
@@ -712,7 +712,9 @@ static int substep_impl(const v2p_omodel *m, const v2p_oparams *p, v2p_ostate *s
                     for (int q = 0; q < nv; ++q) for (int i = 0; i < 3; ++i) { double x = m->hull_verts[3 * (v0 + q) + i]; lo[i] = fmin(lo[i], x); hi[i] = fmax(hi[i], x); }
                     for (int i = 0; i < 3; ++i) e[i] = cb[i] - 0.5 * (lo[i] + hi[i]);
                     double l = sqrt(dot3(e, e));
-                    if (l > 1e-9) for (int i = 0; i < 3; ++i) n[i] = e[i] / l; else { n[0] = 0; n[1] = 0; n[2] = 1; }
+                    /* (1e-5 m: above what float32 resolves at a few metres from the origin - closer to the box centre than that, the
+                     * direction of e is rounding noise in the engine's arithmetic) */
+                    if (l > 1e-5) for (int i = 0; i < 3; ++i) n[i] = e[i] / l; else { n[0] = 0; n[1] = 0; n[2] = 1; }
                     dist = 0.0;
                     memcpy(pb, cb, sizeof(pb));
                 }

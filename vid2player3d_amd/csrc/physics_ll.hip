@@ -802,8 +802,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         const float tc = fminf(fmaxf(t, -hl), hl), kq = rho > rc ? rc * PHYS_RCP(rho) : 1.f;
                         const V3 pt = cw + tc * aw + kq * qv;
                         const V3 ev = bp - pt;
-                        const float dist = PHYS_SQRT(dot(ev, ev));
-                        const V3 n = dist > 1e-9f ? PHYS_RCP(dist) * ev : (t >= 0.f ? aw : -aw);
+                        // (centre inside the solid: pt is bp up to rounding and the direction of ev is noise - out through the nearer cap)
+                        const float dist = (fabsf(t) <= hl && rho <= rc) ? 0.f : PHYS_SQRT(dot(ev, ev));
+                        const V3 n = dist > 1e-6f ? PHYS_RCP(dist) * ev : (t >= 0.f ? aw : -aw);
                         const V3 rl = pt - wx;
                         const float vrel = dot(bv - wxd - cross(ww, rl), n);
                         const float gap = dist - BP.radius;
@@ -846,7 +847,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         else {  // centre inside the hull: out along the direction from the centre of the bounding box
                             const V3 ev = cb - V3{S->aabb_c[bo][0], S->aabb_c[bo][1], S->aabb_c[bo][2]};
                             const float l = PHYS_SQRT(dot(ev, ev));
-                            nb = l > 1e-9f ? PHYS_RCP(l) * ev : V3{0.f, 0.f, 1.f};
+                            nb = l > 1e-5f ? PHYS_RCP(l) * ev : V3{0.f, 0.f, 1.f};  // (closer than float32 resolves: +z, like the oracle)
                             dist = 0.f;
                             pb = cb;
                         }
