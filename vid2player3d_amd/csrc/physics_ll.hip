@@ -1438,8 +1438,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 }
                 // touched links whose parent is the touched link right before them (ascending).  Nothing reads these masks any more (the
                 // per-group sweep that did is gone), but without this loop the compiler lowers the control flow of the sweep differently:
-                // 3 more scalar instructions in the headline instantiation, 0.5 % slower in an A/B.  It goes with the next change that
-                // moves the sweep's code anyway.
+                // 0.5 % slower in an A/B then; measured again on top of the way up without fills and copies (docs/NOTES.md B, 2026-10-19):
+                // 21.24 / 21.29 / 21.27 M env-steps/s without it against 21.50 / 21.52 / 21.49 with it (-1.1 %).  It stays.
                 [[maybe_unused]] unsigned chain0 = 0u, chain1 = 0u;
                 {
                     int prev = -1;
@@ -1503,6 +1503,10 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         p1 = b1;
                     }
                 }
+                // whether walk_to runs the way up in its masked form.  The joint-limit and TGS kernels keep the earlier form: with the masked
+                // one the joint-limit kernels of the register build need 4 .. 16 B more scratch per lane, and two TGS tests of the racket + ball
+                // kernels missed their bounds by 1 % and 5 % - cause not found, see docs/NOTES.md B 2026-10-19
+                constexpr bool UPMASK = !LIMITS && !TGS;
                 // one move of both walks: env h goes from cur_h to its next link when mv_h (info_h = the move, see minfo), else it rests
                 auto walk_to = [&](int nx0, int nx1, int info0, int info1, bool mv0, bool mv1) {
                     long long tsub = DIAG && a.prof ? clock64() : 0;
@@ -1529,50 +1533,112 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     const int updep = (onc && dep > myul) ? dep : -1, dndep = (onn && dep > mydl) ? dep : -1;
                     const int turndep = (onc && dep == myul) ? dep : -2;  // the LCA itself: where this env's move turns
                     const int ulmin = ul0 < ul1 ? ul0 : ul1, dlmin = dl0 < dl1 ? dl0 : dl1;
-                    // levels (bit d = the links at depth d hand over) that need the long form: a walk turns at their parent, or a path link
-                    // is not the first child of its parent (it does not sit in the lane next to it)
+                    // levels (bit d = the links at depth d hand over) on which a path link is not the first child of its parent (it does not
+                    // sit in the lane next to it and hands over through a pull)
                     const unsigned sideb = ((unsigned)(uk0 >> 12) | (unsigned)(uk1 >> 12)) & 0xfffu;
-                    const unsigned longb = sideb | (ul0 < 15 ? 2u << ul0 : 0u) | (ul1 < 15 ? 2u << ul1 : 0u);
                     // ---- up  (levels in a gap between the two envs' ranges run idle: a range test here makes the compiler run the whole
                     // loop with per-lane exits and d in a VGPR)
-                    for (int dctr = du0 > du1 ? du0 : du1; dctr > ulmin; --dctr) {
-                        // (an opaque SCALAR copy of the level for everything the body compares with per-lane depths: where the body tests
-                        // `turndep == d - 1`, value numbering rewrites the loop counter itself with the per-lane value it was found equal to, and
-                        // the whole loop runs with its counter in a VGPR and per-lane exits - +20 VALU instructions per level)
-                        int d = dctr;
-                        asm volatile("" : "+s"(d));
-                        V3 cn{0.f, 0.f, 0.f}, cf{0.f, 0.f, 0.f};
-                        if (updep == d) {
-                            const V3 na = aug * mul(Di, un_new);
-                            const V3 fa = uf_new - V3{dot(col(E, 0), un_new), dot(col(E, 1), un_new), dot(col(E, 2), un_new)};
-                            cn = na + cross(r, fa);
-                            cf = fa;
-                            un_new = V3{0.f, 0.f, 0.f};
-                            uf_new = V3{0.f, 0.f, 0.f};
-                            if (LIMITS) {  // the reaction of the joint's limit impulses: a pure torque on the parent
-                                cn = cn - jt_new;
-                                jt_new = V3{0.f, 0.f, 0.f};
+                    // A level's cn, cf are written by the one link per env that hands over (updep == d) and stay in its registers: no
+                    // zero-fill, the other lanes hold whatever they last wrote.  What arrives is added under an EXEC mask instead: the
+                    // handing links and their parents (the ancestor of cur at depth d - 1).  A DPP shift and a ds_bpermute return 0 for a
+                    // source lane that EXEC has switched off, and the only lanes switched on at depth d are the handing ones; so a parent
+                    // receives its handing child's values through the shift (first child), through a pull (second, third child; a link
+                    // without such a child pulls from lane 31 of its env, which is never on), and zeros from every other source, and
+                    // the handing links - the lane after them and their children are off - add zeros onto what they have just cleared.
+                    // rn, rf = what arrived last; a lane receives on one level of a move only (its own depth + 1), so after the loop the
+                    // link where this env's walk turns still holds what arrived there, and answers it with its Lambda - once, behind the
+                    // loop, for both envs together (zeros if its level was not walked).  One form for every level: no select, no copy
+                    // between two forms, Dw, Dv are not touched inside the loop.
+                    if constexpr (UPMASK) {
+                        const int dmax = du0 > du1 ? du0 : du1;
+                        if (dmax > ulmin) {
+                            const int rcdep = onc ? dep + 1 : -1;  // the level on which this lane's link receives
+                            const int ucl1 = has1 ? cl1 : base + 31, ucl2 = has2 ? cl2 : base + 31;
+                            V3 cn, cf, rn{0.f, 0.f, 0.f}, rf{0.f, 0.f, 0.f};
+                            asm("" : "=v"(cn.x), "=v"(cn.y), "=v"(cn.z), "=v"(cf.x), "=v"(cf.y), "=v"(cf.z));  // (never read before they are written)
+                            for (int dctr = dmax; dctr > ulmin; --dctr) {
+                                // (an opaque SCALAR copy of the level for everything the body compares with per-lane depths: value numbering
+                                // otherwise rewrites the loop counter itself with the per-lane value it was found equal to, and the whole loop
+                                // runs with its counter in a VGPR and per-lane exits - +20 VALU instructions per level)
+                                int d = dctr;
+                                asm volatile("" : "+s"(d));
+                                if (updep == d) {
+                                    // cn = aug Di un_new + r x fa,  fa = uf_new - E^T un_new.  (Written as the fused chains the compiler used to
+                                    // make of the plain expressions: under -fassociative-math the order of a sum follows the shape of the code
+                                    // around it, and the dumps of bench.py pin this one)
+                                    const float axx = aug * Di.xx, axy = aug * Di.xy, axz = aug * Di.xz, ayy = aug * Di.yy, ayz = aug * Di.yz, azz = aug * Di.zz;
+                                    const V3 na{__builtin_fmaf(un_new.x, axx, __builtin_fmaf(un_new.y, axy, un_new.z * axz)),
+                                                __builtin_fmaf(un_new.x, axy, __builtin_fmaf(un_new.y, ayy, un_new.z * ayz)),
+                                                __builtin_fmaf(un_new.x, axz, __builtin_fmaf(un_new.y, ayz, un_new.z * azz))};
+                                    const V3 fa{uf_new.x - __builtin_fmaf(un_new.x, E.m[0], __builtin_fmaf(E.m[3], un_new.y, E.m[6] * un_new.z)),
+                                                uf_new.y - __builtin_fmaf(un_new.x, E.m[1], __builtin_fmaf(E.m[4], un_new.y, E.m[7] * un_new.z)),
+                                                uf_new.z - __builtin_fmaf(un_new.x, E.m[2], __builtin_fmaf(E.m[5], un_new.y, E.m[8] * un_new.z))};
+                                    cn = V3{__builtin_fmaf(fa.z, r.y, __builtin_fmaf(-r.z, fa.y, na.x)), __builtin_fmaf(-r.x, fa.z, __builtin_fmaf(fa.x, r.z, na.y)),
+                                            __builtin_fmaf(fa.y, r.x, __builtin_fmaf(-r.y, fa.x, na.z))};
+                                    cf = fa;
+                                    un_new = V3{0.f, 0.f, 0.f};
+                                    uf_new = V3{0.f, 0.f, 0.f};
+                                }
+                                if (updep == d || rcdep == d) {
+                                    rn = from_next(cn);
+                                    rf = from_next(cf);
+                                    if ((sideb >> d) & 1u) {
+                                        rn = rn + pull(cn, ucl1) + pull(cn, ucl2);
+                                        rf = rf + pull(cf, ucl1) + pull(cf, ucl2);
+                                    }
+                                    un_new = un_new + rn;
+                                    uf_new = uf_new + rf;
+                                    un_tot = un_tot + rn;
+                                }
                             }
-                        }
-                        if (!((longb >> d) & 1u)) {
-                            // every link that hands over is the first child of its parent = the lane before it; the others hand over zeros:
-                            // the shifted values are added as they are (DPP operand of the add)
-                            un_new = un_new + from_next(cn);
-                            uf_new = uf_new + from_next(cf);
-                            un_tot = un_tot + from_next(cn);
-                        } else {
-                            // what arrives is kept apart: the link where a walk turns answers it with its Lambda
-                            V3 rn = from_next(mask(firstchild, cn)), rf = from_next(mask(firstchild, cf));
-                            if ((sideb >> d) & 1u) {
-                                rn = rn + mask(has1, pull(cn, cl1)) + mask(has2, pull(cn, cl2));
-                                rf = rf + mask(has1, pull(cf, cl1)) + mask(has2, pull(cf, cl2));
-                            }
-                            un_new = un_new + rn;
-                            uf_new = uf_new + rf;
-                            un_tot = un_tot + rn;
-                            if (turndep == d - 1) {
+                            if (turndep >= 0) {
                                 Dw = Dw + mul(Lam.A, rn) + mul(Lam.B, rf);
                                 Dv = Dv + V3{dot(col(Lam.B, 0), rn), dot(col(Lam.B, 1), rn), dot(col(Lam.B, 2), rn)} + mul(Lam.C, rf);
+                            }
+                        }
+                    } else {
+                        // (the earlier form: contributions zero-filled on every level, selects for the first-child and side-entry masks,
+                        // the turn inside the loop on the levels of the long form)
+                        const unsigned longb = sideb | (ul0 < 15 ? 2u << ul0 : 0u) | (ul1 < 15 ? 2u << ul1 : 0u);
+                        for (int dctr = du0 > du1 ? du0 : du1; dctr > ulmin; --dctr) {
+                            // (an opaque SCALAR copy of the level for everything the body compares with per-lane depths: where the body tests
+                            // `turndep == d - 1`, value numbering rewrites the loop counter itself with the per-lane value it was found equal to, and
+                            // the whole loop runs with its counter in a VGPR and per-lane exits - +20 VALU instructions per level)
+                            int d = dctr;
+                            asm volatile("" : "+s"(d));
+                            V3 cn{0.f, 0.f, 0.f}, cf{0.f, 0.f, 0.f};
+                            if (updep == d) {
+                                const V3 na = aug * mul(Di, un_new);
+                                const V3 fa = uf_new - V3{dot(col(E, 0), un_new), dot(col(E, 1), un_new), dot(col(E, 2), un_new)};
+                                cn = na + cross(r, fa);
+                                cf = fa;
+                                un_new = V3{0.f, 0.f, 0.f};
+                                uf_new = V3{0.f, 0.f, 0.f};
+                                if (LIMITS) {  // the reaction of the joint's limit impulses: a pure torque on the parent
+                                    cn = cn - jt_new;
+                                    jt_new = V3{0.f, 0.f, 0.f};
+                                }
+                            }
+                            if (!((longb >> d) & 1u)) {
+                                // every link that hands over is the first child of its parent = the lane before it; the others hand over zeros:
+                                // the shifted values are added as they are (DPP operand of the add)
+                                un_new = un_new + from_next(cn);
+                                uf_new = uf_new + from_next(cf);
+                                un_tot = un_tot + from_next(cn);
+                            } else {
+                                // what arrives is kept apart: the link where a walk turns answers it with its Lambda
+                                V3 rn = from_next(mask(firstchild, cn)), rf = from_next(mask(firstchild, cf));
+                                if ((sideb >> d) & 1u) {
+                                    rn = rn + mask(has1, pull(cn, cl1)) + mask(has2, pull(cn, cl2));
+                                    rf = rf + mask(has1, pull(cf, cl1)) + mask(has2, pull(cf, cl2));
+                                }
+                                un_new = un_new + rn;
+                                uf_new = uf_new + rf;
+                                un_tot = un_tot + rn;
+                                if (turndep == d - 1) {
+                                    Dw = Dw + mul(Lam.A, rn) + mul(Lam.B, rf);
+                                    Dv = Dv + V3{dot(col(Lam.B, 0), rn), dot(col(Lam.B, 1), rn), dot(col(Lam.B, 2), rn)} + mul(Lam.C, rf);
+                                }
                             }
                         }
                     }
