@@ -1485,10 +1485,38 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 // LIMITS: the walk also stops at the joints that carry limit rows (their block comes right before the contact block of the link)
                 const unsigned v0 = LIMITS ? m0 | lm0 : m0, v1 = LIMITS ? m1 | lm1 : m1;
                 V3 jt_new{0.f, 0.f, 0.f};  // LIMITS: limit impulse of this joint not yet handed up (its reaction, -jt, goes to the parent)
+                // VTAB (the kernels without joint limits and TGS): the same moves filed by VISIT instead of by link.  The walk takes the k-th
+                // stop of both envs in the same visit, in every iteration, so everything about visit k but `live` and `done` is fixed for the
+                // substep:
+                //   vis    lane k of an env's half: the move into its k-th stop (as minfo) | bit 24: the env moves in this visit once it is
+                //          live - it has a k-th stop and more than one stop.  (An env with fewer stops than its partner rests in the surplus
+                //          visits, its lanes there hold 0; an env with a single stop stands on it for the whole substep.)
+                //   anc    per lane: bit k + 1 = this link is an ancestor (or self) of its env's k-th stop, bit 0 = ... of its LAST stop.
+                //          The walk stands on the previous stop, cyclically, from the env's first visit on, whether it is live or not, and
+                //          before that visit the env is not live and does not move: in visit k "on the path from where the walk stands"
+                //          is bit k, "on the path to the next stop" bit k + 1 (the move into stop 0 of a later iteration comes from the
+                //          env's own last stop, whose number differs between the envs: hence a bit of its own).  24 links: 25 bits.
+                //   mystop the visit in which this lane's link is its env's stop, or -1
+                // (24 links per env: every env's stops fit the 32 lanes of its half, the table has no capacity limit.)
+                // The joint-limit kernels carry moves of their own inside a visit (the one-joint bounce) and keep the earlier form, the TGS
+                // kernels with them (as UPMASK below); with the table the ball kernels of the register build need 16 B more scratch per
+                // lane and its diagnostic kernel 20 B: they keep the earlier form too (docs/NOTES.md B, 2026-10-19, the sweep's visits).
+#ifdef V2P_LL_REGS_BUILD
+                constexpr bool VTAB = !LIMITS && !TGS && !BALL && !DIAG;
+#else
+                constexpr bool VTAB = !LIMITS && !TGS && !BALL;
+#endif
                 int minfo = 0;
+                [[maybe_unused]] int vis = 0, mystop = -1, nvis0 = 0, nvis1 = 0;
+                [[maybe_unused]] unsigned anc = 0u;
                 {
                     int p0 = v0 ? 31 - __clz(v0) : 0, p1 = v1 ? 31 - __clz(v1) : 0;
-                    for (unsigned s0 = v0, s1 = v1; s0 | s1; s0 &= s0 - 1, s1 &= s1 - 1) {
+                    if constexpr (VTAB) {
+                        nvis0 = __popc(v0);
+                        nvis1 = __popc(v1);
+                    }
+                    int k = 0;
+                    for (unsigned s0 = v0, s1 = v1; s0 | s1; s0 &= s0 - 1, s1 &= s1 - 1, ++k) {
                         const int b0 = s0 ? __ffs(s0) - 1 : p0, b1 = s1 ? __ffs(s1) - 1 : p1;
                         const int selp = half ? p1 : p0, selb = half ? b1 : b0;
                         const bool ap = valid && ((desc >> selp) & 1), ab = valid && ((desc >> selb) & 1);
@@ -1498,16 +1526,29 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         // (levels of the way up where the path link is not its parent's first child: it hands over through a pull, see walk_to)
                         const int sd = (half ? M.side_depths[p1] : M.side_depths[p0]) & ~((2 << dl) - 1);
                         // (bit 28: the link itself is not its parent's first child - the one-joint bounce of a limit block needs it)
-                        if (valid && lb == selb && ((half ? s1 : s0) != 0u)) minfo = dl | (du << 4) | (dn << 8) | (sd << 12) | ((LIMITS && !firstchild) ? 1 << 28 : 0);
+                        if constexpr (VTAB) {
+                            const bool has = (half ? s1 : s0) != 0u;
+                            if (has && lb == k) vis = dl | (du << 4) | (dn << 8) | ((sd & 0xfff) << 12) | ((half ? nvis1 : nvis0) > 1 ? 1 << 24 : 0);
+                            if (has && valid && lb == selb) mystop = k;
+                            if (has && ab) anc |= 2u << k;
+                            if (k == 0 && ap) anc |= 1u;
+                        } else {
+                            if (valid && lb == selb && ((half ? s1 : s0) != 0u)) minfo = dl | (du << 4) | (dn << 8) | (sd << 12) | ((LIMITS && !firstchild) ? 1 << 28 : 0);
+                        }
                         p0 = b0;
                         p1 = b1;
                     }
+                }
+                if constexpr (VTAB) {  // (nothing tracks where a walk stands; where it closes, after whole sweeps, it stands on the env's last stop)
+                    cur0 = v0 ? 31 - __clz(v0) : 0;
+                    cur1 = v1 ? 31 - __clz(v1) : 0;
                 }
                 // whether walk_to runs the way up in its masked form.  The joint-limit and TGS kernels keep the earlier form: with the masked
                 // one the joint-limit kernels of the register build need 4 .. 16 B more scratch per lane, and two TGS tests of the racket + ball
                 // kernels missed their bounds by 1 % and 5 % - cause not found, see docs/NOTES.md B 2026-10-19
                 constexpr bool UPMASK = !LIMITS && !TGS;
                 // one move of both walks: env h goes from cur_h to its next link when mv_h (info_h = the move, see minfo), else it rests
+                [[maybe_unused]] int vk = 0;  // VTAB: the visit in which walk_to runs (it reads the roles from anc; nx0, nx1 are not used then)
                 auto walk_to = [&](int nx0, int nx1, int info0, int info1, bool mv0, bool mv1) {
                     long long tsub = DIAG && a.prof ? clock64() : 0;
                     // a resting env: empty ranges that do not widen the loops (LCA depth 15, depths 0)
@@ -1516,7 +1557,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     const int dl0 = pk0 & 15, dn0 = (pk0 >> 8) & 15;
                     const int dl1 = pk1 & 15, dn1 = (pk1 >> 8) & 15;
                     const int selc = half ? cur1 : cur0, seln = half ? nx1 : nx0, mydl = half ? dl1 : dl0;
-                    const bool onc = valid && ((desc >> selc) & 1), onn = valid && ((desc >> seln) & 1);  // ancestors (or self) of cur / of next
+                    // ancestors (or self) of cur / of next
+                    const bool onc = VTAB ? ((anc >> vk) & 1u) != 0u : valid && ((desc >> selc) & 1), onn = VTAB ? ((anc >> vk) & 2u) != 0u : valid && ((desc >> seln) & 1);
                     // LIMITS: a way up on which no link holds anything to hand over is not walked (the stops at joints whose limit rows
                     // do not act - most of them - leave nothing behind; the lowest common ancestor has been current since the walk came
                     // down through it): that env's way up counts as resting
@@ -1662,6 +1704,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     const int i0 = ((int)__builtin_amdgcn_readlane(dep, cur0) << 4) | (M.side_depths[cur0] << 12);
                     const int i1 = ((int)__builtin_amdgcn_readlane(dep, 32 + cur1) << 4) | (M.side_depths[cur1] << 12);
                     const int slive = __builtin_amdgcn_readfirstlane((live0 ? 1 : 0) | (live1 ? 2 : 0));
+                    // (VTAB: a walk closes after whole sweeps only - it stands on the env's last stop, bit 0 of anc; nothing goes down)
+                    vk = 0;
                     walk_to(0, 0, i0, i1, (slive & 1) != 0, (slive & 2) != 0);
                     long long tsub = DIAG && a.prof ? clock64() : 0;
                     V3 ddw{0.f, 0.f, 0.f}, ddv{0.f, 0.f, 0.f};
@@ -1752,21 +1796,41 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             }
                         }
                     }
-                    while (t0 | t1) {
-                        const int b0 = t0 ? __ffs(t0) - 1 : -1, b1 = t1 ? __ffs(t1) - 1 : -1;
-                        t0 &= ~(b0 < 0 ? 0u : 1u << b0);
-                        t1 &= ~(b1 < 0 ? 0u : 1u << b1);
-                        if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[8], 1ull);
-                        // (readfirstlane: wave-uniform by construction, and the compiler must know it - the level loops are scalar loops)
-                        const int smv = __builtin_amdgcn_readfirstlane(((live0 && b0 >= 0 && b0 != cur0) ? 1 : 0) | ((live1 && b1 >= 0 && b1 != cur1) ? 2 : 0));
-                        int came_down = 0;  // LIMITS: bit h = env h has just come DOWN to its link (the lowest common ancestor of the move lies above it)
-                        if (smv) {
-                            const int i0 = __builtin_amdgcn_readlane(minfo, b0 < 0 ? 0 : b0), i1 = __builtin_amdgcn_readlane(minfo, 32 + (b1 < 0 ? 0 : b1));
-                            walk_to(b0 < 0 ? 0 : b0, b1 < 0 ? 0 : b1, i0, i1, (smv & 1) != 0, (smv & 2) != 0);
-                            if (LIMITS) came_down = smv & (((i0 & 15) < ((i0 >> 8) & 15) ? 1 : 0) | ((i1 & 15) < ((i1 >> 8) & 15) ? 2 : 0));
+                    // VTAB: a counted loop over the visits of the envs that still iterate
+                    const int nvis = VTAB ? __builtin_amdgcn_readfirstlane(max((done & 1) ? 0 : nvis0, (done & 2) ? 0 : nvis1)) : 0;
+                    if (VTAB && ((done >> half) & 1)) {  // (done only grows: the env's visits are struck out once)
+                        vis = 0;
+                        mystop = -1;
+                    }
+                    // one visit: the k-th stop of both envs (VTAB; the earlier form takes the stops off t0, t1 and does not count)
+                    [[maybe_unused]] int k = 0;
+                    while (VTAB ? k < nvis : (t0 | t1) != 0u) {
+                        const int b0 = !VTAB && t0 ? __ffs(t0) - 1 : -1, b1 = !VTAB && t1 ? __ffs(t1) - 1 : -1;  // (VTAB: not needed)
+                        if constexpr (!VTAB) {
+                            t0 &= ~(b0 < 0 ? 0u : 1u << b0);
+                            t1 &= ~(b1 < 0 ? 0u : 1u << b1);
                         }
-                        if (b0 >= 0) cur0 = b0;
-                        if (b1 >= 0) cur1 = b1;
+                        if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[8], 1ull);
+                        int came_down = 0;  // LIMITS: bit h = env h has just come DOWN to its link (the lowest common ancestor of the move lies above it)
+                        // (readfirstlane: wave-uniform by construction, and the compiler must know it - the level loops are scalar loops)
+                        if constexpr (VTAB) {
+                            // (bit 24 of a visit word: the env has a stop here and more than one stop - it moves if it is live)
+                            const int vi0 = __builtin_amdgcn_readlane(vis, k), vi1 = __builtin_amdgcn_readlane(vis, 32 + k);
+                            const int smv = __builtin_amdgcn_readfirstlane((live0 ? (vi0 >> 24) & 1 : 0) | (live1 ? (vi1 >> 23) & 2 : 0));
+                            if (smv) {
+                                vk = k;
+                                walk_to(0, 0, vi0, vi1, (smv & 1) != 0, (smv & 2) != 0);
+                            }
+                        } else {
+                            const int smv = __builtin_amdgcn_readfirstlane(((live0 && b0 >= 0 && b0 != cur0) ? 1 : 0) | ((live1 && b1 >= 0 && b1 != cur1) ? 2 : 0));
+                            if (smv) {
+                                const int i0 = __builtin_amdgcn_readlane(minfo, b0 < 0 ? 0 : b0), i1 = __builtin_amdgcn_readlane(minfo, 32 + (b1 < 0 ? 0 : b1));
+                                walk_to(b0 < 0 ? 0 : b0, b1 < 0 ? 0 : b1, i0, i1, (smv & 1) != 0, (smv & 2) != 0);
+                                if (LIMITS) came_down = smv & (((i0 & 15) < ((i0 >> 8) & 15) ? 1 : 0) | ((i1 & 15) < ((i1 >> 8) & 15) ? 2 : 0));
+                            }
+                            if (b0 >= 0) cur0 = b0;
+                            if (b1 >= 0) cur1 = b1;
+                        }
                         const int bsel = half ? b1 : b0;
                         if constexpr (LIMITS) {
                             // ---- the limit rows of the joint the walk stands on (before the contact rows of its link).  A limit impulse is a
@@ -1824,7 +1888,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         }
                         // ---- the rows of the link the walk stands on
                         long long tsub = DIAG && a.prof ? clock64() : 0;
-                        const bool me = valid && lb == bsel && (!LIMITS || (((half ? m1 : m0) >> (bsel < 0 ? 0 : bsel)) & 1u));
+                        const bool me = VTAB ? mystop == k : valid && lb == bsel && (!LIMITS || (((half ? m1 : m0) >> (bsel < 0 ? 0 : bsel)) & 1u));
                         V3 gn{0.f, 0.f, 0.f}, gf{0.f, 0.f, 0.f};  // what these rows add to the link's impulse
                         if (me) {
                             V3 wl = w + Dw, xl = xd + Dv;
@@ -1923,6 +1987,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         moved |= ((unsigned)chg != 0u ? 1 : 0) | ((unsigned)(chg >> 32) != 0u ? 2 : 0);
                         if (DIAG && a.prof && !chg && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[19], 1ull);
                         LLSUB(11);
+                        if constexpr (VTAB) ++k;
                     }
                     if (BALL) moved |= ball_ground_rows(done);
                     if (TGS && (live0 || live1)) {
