@@ -214,7 +214,19 @@ __device__ __forceinline__ void grp_arg(float& v, int& k) {
     v = g;
 }
 
-#define LLSUB(k) do { if (DIAG && a.prof) { long long t_ = clock64(); if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t_ - tsub)); tsub = t_; } } while (0)
+#define LLSUBV(k, tv) do { if (DIAG && a.prof) { long long t_ = clock64(); if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t_ - tv)); tv = t_; } } while (0)
+#define LLSUB(k) LLSUBV(k, tsub)
+// the split of the sweep's remainder (counters 20 - 23: closing move, closing pass, head and tail of a visit, set-up) is timed in the
+// default build's diagnostic kernel only: in the register build's it costs 12 B of scratch per lane
+#ifdef V2P_LL_REGS_BUILD
+#define LLSUBX(k, tv) do { } while (0)
+#define LLSUBX_OR(k, kparent) LLSUB(kparent)  // (where the parent timed the same stretch into another counter: as the parent)
+#define V2P_LL_DIAGX false
+#else
+#define LLSUBX(k, tv) LLSUBV(k, tv)
+#define LLSUBX_OR(k, kparent) LLSUB(k)
+#define V2P_LL_DIAGX DIAG
+#endif
 #define LLPH(k) do { if (DIAG && a.prof) { long long t_ = clock64(); if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t_ - tprev)); tprev = t_; } } while (0)
 
 // Everything from here to the end of the kernel depends on the build (register budget, what is parked in LDS and with it the LDS
@@ -1506,8 +1518,14 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
 #else
                 constexpr bool VTAB = !LIMITS && !TGS && !BALL;
 #endif
+                // LIVEM (with the visit table): whether an env has applied an impulse yet is bit h of ONE scalar word (`livem`), fed by the two
+                // halves of the change ballot as two scalars.  As two bools (the earlier form, which the other kernels keep with their visits)
+                // the compiler holds `live` in two lane masks, and every visit turns them into a scalar through a VGPR again
+                // (docs/NOTES.md B, 2026-10-19, the way down and the rest of the sweep).
+                constexpr bool LIVEM = VTAB;
                 int minfo = 0;
                 [[maybe_unused]] int vis = 0, mystop = -1, nvis0 = 0, nvis1 = 0;
+                [[maybe_unused]] int livem = 0;  // LIVEM: bit h = env h is live (wave-uniform, in a scalar register)
                 [[maybe_unused]] unsigned anc = 0u;
                 {
                     int p0 = v0 ? 31 - __clz(v0) : 0, p1 = v1 ? 31 - __clz(v1) : 0;
@@ -1701,12 +1719,23 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 // the walk returns to the root (its Lambda answers the total) and one root -> leaves pass moves the links down to depth dlast
                 // (all of them, or those the sweep reads: the links down to the env's deepest stop)
                 auto walk_close = [&](int dlast, bool all) {
+                    [[maybe_unused]] long long tclose = V2P_LL_DIAGX && a.prof ? clock64() : 0;
                     const int i0 = ((int)__builtin_amdgcn_readlane(dep, cur0) << 4) | (M.side_depths[cur0] << 12);
                     const int i1 = ((int)__builtin_amdgcn_readlane(dep, 32 + cur1) << 4) | (M.side_depths[cur1] << 12);
-                    const int slive = __builtin_amdgcn_readfirstlane((live0 ? 1 : 0) | (live1 ? 2 : 0));
+                    const int slive = LIVEM ? livem : __builtin_amdgcn_readfirstlane((live0 ? 1 : 0) | (live1 ? 2 : 0));
                     // (VTAB: a walk closes after whole sweeps only - it stands on the env's last stop, bit 0 of anc; nothing goes down)
                     vk = 0;
+                    [[maybe_unused]] const long long tmove = V2P_LL_DIAGX && a.prof ? clock64() : 0;
                     walk_to(0, 0, i0, i1, (slive & 1) != 0, (slive & 2) != 0);
+                    // (counter 20: the closing move - its descriptor, the way up to the root, the turn there.  walk_to has timed itself into
+                    // the counters of the moves: taken out of `up` again, so that a counter of walk_to's own - one more captured variable,
+                    // which moves the register allocation of every kernel - is not needed; `down` keeps the closing move's test of its
+                    // empty range, a few cycles per substep)
+                    if (V2P_LL_DIAGX && a.prof) {
+                        const long long tdone = clock64();
+                        if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[12], (unsigned long long)(tmove - tdone));
+                    }
+                    LLSUBX(20, tclose);
                     long long tsub = DIAG && a.prof ? clock64() : 0;
                     V3 ddw{0.f, 0.f, 0.f}, ddv{0.f, 0.f, 0.f};
                     if (lb == 0) {
@@ -1726,7 +1755,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             xd = xd + ddv;
                         }
                     }
-                    LLSUB(14);
+                    LLSUBX_OR(21, 14);  // (counter 21: the root -> leaves pass of a closing walk; it was counted with the ways down before)
                 };
                 // ---- ball x ground: a stop of its own after the last link - the last rows of a sweep (point at -R z of the centre; rows
                 // n = z, t1 = x, t2 = y); returns whether any lane's rows changed something
@@ -1764,6 +1793,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 // whatever the env it shares the wave with still does.  (Its later sweeps change nothing: the same moves re-derive the same
                 // velocities - the block updates they would take are saved.)
                 int done = 0;
+                if (V2P_LL_DIAGX && a.prof) { long long tsub = tprev; LLSUBX(23, tsub); }  // (counter 23: the sweep's set-up since the end of the Lambda phase - moves, visit table)
                 for (int it = 0; it < P.n_iter; ++it) {
                     unsigned t0 = (done & 1) ? 0u : v0, t1 = (done & 2) ? 0u : v1;
                     int moved = 0;  // bit h: env h changed something in this sweep (wave-uniform)
@@ -1811,21 +1841,27 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             t1 &= ~(b1 < 0 ? 0u : 1u << b1);
                         }
                         if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[8], 1ull);
+                        [[maybe_unused]] long long thead = V2P_LL_DIAGX && a.prof ? clock64() : 0;  // (counter 22: head and tail of a visit - what neither the move nor the rows time)
                         int came_down = 0;  // LIMITS: bit h = env h has just come DOWN to its link (the lowest common ancestor of the move lies above it)
                         // (readfirstlane: wave-uniform by construction, and the compiler must know it - the level loops are scalar loops)
                         if constexpr (VTAB) {
                             // (bit 24 of a visit word: the env has a stop here and more than one stop - it moves if it is live)
                             const int vi0 = __builtin_amdgcn_readlane(vis, k), vi1 = __builtin_amdgcn_readlane(vis, 32 + k);
-                            const int smv = __builtin_amdgcn_readfirstlane((live0 ? (vi0 >> 24) & 1 : 0) | (live1 ? (vi1 >> 23) & 2 : 0));
+                            const int smv = LIVEM ? livem & (((vi0 >> 24) & 1) | ((vi1 >> 23) & 2))
+                                                  : __builtin_amdgcn_readfirstlane((live0 ? (vi0 >> 24) & 1 : 0) | (live1 ? (vi1 >> 23) & 2 : 0));
                             if (smv) {
                                 vk = k;
+                                LLSUBX(22, thead);
                                 walk_to(0, 0, vi0, vi1, (smv & 1) != 0, (smv & 2) != 0);
+                                if (V2P_LL_DIAGX && a.prof) thead = clock64();
                             }
                         } else {
                             const int smv = __builtin_amdgcn_readfirstlane(((live0 && b0 >= 0 && b0 != cur0) ? 1 : 0) | ((live1 && b1 >= 0 && b1 != cur1) ? 2 : 0));
                             if (smv) {
                                 const int i0 = __builtin_amdgcn_readlane(minfo, b0 < 0 ? 0 : b0), i1 = __builtin_amdgcn_readlane(minfo, 32 + (b1 < 0 ? 0 : b1));
+                                LLSUBX(22, thead);
                                 walk_to(b0 < 0 ? 0 : b0, b1 < 0 ? 0 : b1, i0, i1, (smv & 1) != 0, (smv & 2) != 0);
+                                if (V2P_LL_DIAGX && a.prof) thead = clock64();
                                 if (LIMITS) came_down = smv & (((i0 & 15) < ((i0 >> 8) & 15) ? 1 : 0) | ((i1 & 15) < ((i1 >> 8) & 15) ? 2 : 0));
                             }
                             if (b0 >= 0) cur0 = b0;
@@ -1887,6 +1923,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             }
                         }
                         // ---- the rows of the link the walk stands on
+                        LLSUBX(22, thead);
                         long long tsub = DIAG && a.prof ? clock64() : 0;
                         const bool me = VTAB ? mystop == k : valid && lb == bsel && (!LIMITS || (((half ? m1 : m0) >> (bsel < 0 ? 0 : bsel)) & 1u));
                         V3 gn{0.f, 0.f, 0.f}, gf{0.f, 0.f, 0.f};  // what these rows add to the link's impulse
@@ -1981,12 +2018,24 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             un_new = un_new + gn;
                             uf_new = uf_new + gf;
                         }
+                        LLSUBX(11, tsub);
                         const unsigned long long chg = __ballot(gn.x != 0.f || gn.y != 0.f || gn.z != 0.f || gf.x != 0.f || gf.y != 0.f || gf.z != 0.f);
-                        live0 = live0 || (unsigned)chg != 0u;
-                        live1 = live1 || (unsigned)(chg >> 32) != 0u;
-                        moved |= ((unsigned)chg != 0u ? 1 : 0) | ((unsigned)(chg >> 32) != 0u ? 2 : 0);
+                        if constexpr (LIVEM) {
+                            // (the same ballot, its halves as two opaque scalars: `(unsigned)(chg >> 32) != 0` otherwise becomes a 64-bit
+                            // "greater than", which the scalar unit does not have, and `live` a pair of lane masks that every visit turns
+                            // into a scalar through a VGPR again)
+                            int clo = (int)(unsigned)chg, chi = (int)(unsigned)(chg >> 32);
+                            asm("" : "+s"(clo), "+s"(chi));
+                            const int cb = (clo != 0 ? 1 : 0) | (chi != 0 ? 2 : 0);
+                            livem |= cb;
+                            moved |= cb;
+                        } else {
+                            live0 = live0 || (unsigned)chg != 0u;
+                            live1 = live1 || (unsigned)(chg >> 32) != 0u;
+                            moved |= ((unsigned)chg != 0u ? 1 : 0) | ((unsigned)(chg >> 32) != 0u ? 2 : 0);
+                        }
                         if (DIAG && a.prof && !chg && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[19], 1ull);
-                        LLSUB(11);
+                        LLSUBX_OR(22, 11);  // (the tail: the ballot of the change, live, moved)
                         if constexpr (VTAB) ++k;
                     }
                     if (BALL) moved |= ball_ground_rows(done);
@@ -2000,7 +2049,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         if (done == 3) break;
                     }
                 }
-                if (!TGS && (live0 || live1)) walk_close(maxd, true);
+                if (!TGS && (LIVEM ? livem != 0 : (live0 || live1))) walk_close(maxd, true);
                 // links below the deepest touched one: one catch-up pass with the accumulated motion of their parents
                 // (PGS: the walk moves every link when it closes)
                 V3 accw = w - park_get3(PARK_W0), accv = xd - park_get3(PARK_XD0);
