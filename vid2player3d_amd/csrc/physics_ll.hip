@@ -1523,6 +1523,18 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 // the compiler holds `live` in two lane masks, and every visit turns them into a scalar through a VGPR again
                 // (docs/NOTES.md B, 2026-10-19, the way down and the rest of the sweep).
                 constexpr bool LIVEM = VTAB;
+                // ROWX: the rows of a visit's stops, point by point, without selects and without a dispatch between the points: a point's
+                // three rows run as a divergent region of the lanes whose point is active.  ROWCNT (with the visit table): whether point c
+                // exists for either stop is a scalar test on the stops' numbers of points, which the visit words carry in bits 25 - 27;
+                // without the table it stays a vote.  The register build's kernels without the table keep the earlier form, a vote per point
+                // and `dl` selected per row: with the regions its TGS + joint-limit kernel needs 12 B more scratch per lane
+                // (docs/NOTES.md B, 2026-10-19, the rows).
+#ifdef V2P_LL_REGS_BUILD
+                constexpr bool ROWX = VTAB;
+#else
+                constexpr bool ROWX = true;
+#endif
+                constexpr bool ROWCNT = ROWX && VTAB;
                 int minfo = 0;
                 [[maybe_unused]] int vis = 0, mystop = -1, nvis0 = 0, nvis1 = 0;
                 [[maybe_unused]] int livem = 0;  // LIVEM: bit h = env h is live (wave-uniform, in a scalar register)
@@ -1546,7 +1558,10 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         // (bit 28: the link itself is not its parent's first child - the one-joint bounce of a limit block needs it)
                         if constexpr (VTAB) {
                             const bool has = (half ? s1 : s0) != 0u;
-                            if (has && lb == k) vis = dl | (du << 4) | (dn << 8) | ((sd & 0xfff) << 12) | ((half ? nvis1 : nvis0) > 1 ? 1 << 24 : 0);
+                            // (bits 25 - 27, ROWCNT: the stop's number of points)
+                            int np = 0;
+                            if constexpr (ROWCNT) { const int c0 = __builtin_amdgcn_readlane(cnt, b0), c1 = __builtin_amdgcn_readlane(cnt, 32 + b1); np = (half ? c1 : c0) << 25; }
+                            if (has && lb == k) vis = dl | (du << 4) | (dn << 8) | ((sd & 0xfff) << 12) | ((half ? nvis1 : nvis0) > 1 ? 1 << 24 : 0) | np;
                             if (has && valid && lb == selb) mystop = k;
                             if (has && ab) anc |= 2u << k;
                             if (k == 0 && ap) anc |= 1u;
@@ -1843,10 +1858,12 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[8], 1ull);
                         [[maybe_unused]] long long thead = V2P_LL_DIAGX && a.prof ? clock64() : 0;  // (counter 22: head and tail of a visit - what neither the move nor the rows time)
                         int came_down = 0;  // LIMITS: bit h = env h has just come DOWN to its link (the lowest common ancestor of the move lies above it)
+                        [[maybe_unused]] int npts = 0;  // ROWCNT: the larger of the two stops' numbers of points (0 for an env that rests or is done)
                         // (readfirstlane: wave-uniform by construction, and the compiler must know it - the level loops are scalar loops)
                         if constexpr (VTAB) {
                             // (bit 24 of a visit word: the env has a stop here and more than one stop - it moves if it is live)
                             const int vi0 = __builtin_amdgcn_readlane(vis, k), vi1 = __builtin_amdgcn_readlane(vis, 32 + k);
+                            if constexpr (ROWCNT) npts = max((vi0 >> 25) & 7, (vi1 >> 25) & 7);
                             const int smv = LIVEM ? livem & (((vi0 >> 24) & 1) | ((vi1 >> 23) & 2))
                                                   : __builtin_amdgcn_readfirstlane((live0 ? (vi0 >> 24) & 1 : 0) | (live1 ? (vi1 >> 23) & 2 : 0));
                             if (smv) {
@@ -1936,6 +1953,56 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             for (int c = 0; c < 4; ++c) { rr4[c] = CS.cr(c); lam4[c] = CS.lam(c); bias4[c] = CS.bias(c); }
                             V3 ws0{0.f, 0.f, 0.f}, xs0{0.f, 0.f, 0.f};  // VFRIC: v* of the link
                             if constexpr (VFRIC) { ws0 = park_get3(PARK_W0); xs0 = park_get3(PARK_XD0); }
+                            if constexpr (ROWX) {
+                                // An unrolled loop without `break` / `continue`.  ROWCNT: npts is a scalar, "c < npts" for c = 0 .. 3 are four
+                                // scalar compares, and since c >= npts implies c + 1 >= npts the compiler threads them into four nested blocks.
+                                // Without the table: four votes (uniform over the at most two touched links solved here).
+                                // (The same body as an inlined lambda per point, called from four nested ifs, is NOT the same arithmetic: a
+                                // function is optimised on its own first, the rows' loop is unrolled there, and the relaxed-math flags then
+                                // merge the normal row's relative velocity with the one of the `act` test and fold `ln + (nl - ln)`.)
+#pragma unroll
+                                for (int c = 0; c < 4; ++c) {
+                                    if (ROWCNT ? c < npts : any64(c < cnt)) {
+                                        const V3 rr = rr4[c];
+                                        V3 t1{1.f, 0.f, 0.f}, t2{0.f, 1.f, 0.f};
+                                        if constexpr (VFRIC) vfric_frame(ws0, xs0, rr, t1, t2);
+                                        const V3 lam0 = lam4[c];
+                                        float ln = lam0.x, l1 = lam0.y, l2 = lam0.z;
+                                        // a point without normal impulse (hence without friction impulses: they are clamped to mu x normal)
+                                        // that is separating stays as it is: its three rows would change nothing.  The rows run under EXEC for
+                                        // the lanes whose point is active and write in place; a lane whose point is not active, or does not
+                                        // exist, executes nothing, so an env's numbers do not depend on what its wave partner does by construction
+                                        // (`&`, not `&&`: one region per point; with `&&` the compiler nests a region for c < cnt around it)
+                                        const float bias_c = rowbias(bias4[c]);
+                                        const bool act = bool((c < cnt) & !((ln == 0.f) & (rr.y * wl.x - rr.x * wl.y + xl.z + bias_c >= 0.f)));
+                                        if (act) {
+#pragma unroll
+                                            for (int ax = 0; ax < 3; ++ax) {
+                                                const V3 dir = ax == 0 ? V3{0.f, 0.f, 1.f} : (VFRIC ? (ax == 1 ? t1 : t2) : (ax == 1 ? V3{1.f, 0.f, 0.f} : V3{0.f, 1.f, 0.f}));
+                                                const V3 jn = cross(rr, dir);
+                                                const V3 yw = mul(Lam.A, jn) + mul(Lam.B, dir);
+                                                const V3 yv = V3{dot(col(Lam.B, 0), jn), dot(col(Lam.B, 1), jn), dot(col(Lam.B, 2), jn)} + mul(Lam.C, dir);
+                                                const float wii = dot(jn, yw) + dot(dir, yv);
+                                                const float rel = dot(jn, wl) + dot(dir, xl) + (ax == 0 ? bias_c : 0.f);
+                                                const float old = ax == 0 ? ln : (ax == 1 ? l1 : l2);
+                                                float nl = old - rel * __builtin_amdgcn_rcpf(wii);
+                                                if (ax == 0) nl = fmaxf(nl, 0.f);
+                                                else { const float lim = P.mu * ln; nl = fminf(fmaxf(nl, -lim), lim); }
+                                                float dl = nl - old;
+                                                // (opaque: without the select of the earlier form the relaxed-math flags fold `old + (nl - old)`
+                                                // below to `nl`, which rounds differently)
+                                                asm("" : "+v"(dl));
+                                                if (ax == 0) ln += dl; else if (ax == 1) l1 += dl; else l2 += dl;
+                                                wl = wl + dl * yw;
+                                                xl = xl + dl * yv;
+                                                gn = gn + dl * jn;
+                                                gf = gf + dl * dir;
+                                            }
+                                            CS.set_lam(c, V3{ln, l1, l2});
+                                        }
+                                    }
+                                }
+                            } else {
 #pragma unroll
                             for (int c = 0; c < 4; ++c) {
                                 const bool active = c < cnt;
@@ -1971,6 +2038,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                                     gf = gf + dl * dir;
                                 }
                                 CS.set_lam(c, V3{ln, l1, l2});
+                            }
                             }
                             if (BALL && ballhit) {
                                 // ---- ball x racket points: two-body rows (ball point velocity minus racket point velocity); the ball side is
