@@ -1,6 +1,6 @@
 """Contact generation of the link-per-lane physics kernel, case by case: the hull scan by groups of 8 lanes, the manifold reduction
 and the contact points of the chosen vertices, against the selection rule of the C oracle (oracle/phys) - vertex ids EXACTLY, in every
-substep - and the state after one control step at the bounds of the contact parity tests (tests/test_gpu_physics.py).
+substep - and the state after one control step at the bounds of the contact parity tests (rows_all of tests/gpu_util.py).
 
 The fixture is a body whose every link carries a "probe": a hull with a flat plate of K candidate vertices hanging down to a level of
 its own, 1/1024 m apart from link to link, under a humanoid that stands upright with identity rotations.  The height of the root then
@@ -19,11 +19,10 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import task_oracle as O
-from oracle.phys_oracle import BatchOracle, default_params
+from tests import phys_poses as P
+from tests import phys_step as S
+from tests.phys_poses import NB, NSUB
 
-NSUB = 4
-NB = 24
 GRID = 1024.0        # link levels and root heights: multiples of 1/1024 m
 COFF = 0.02          # contact offset (oracle.default_params)
 TOP_LEVEL = 20       # a plate at (s + level) / 1024 m is within the contact offset while s + level <= 20 (21 / 1024 is beyond the box cull too)
@@ -129,12 +128,8 @@ def expected_structure(counts):
     return cands, near
 
 
-def oracle_for(counts, par=None):
-    model, _ = probe_model()
-    root, dpos, dvel = probe_states(counts)
-    oracle = BatchOracle(model, len(counts), par or default_params(enable_contact=True))
-    oracle.set_state(root, dpos, dvel)
-    return oracle
+def oracle_for(counts):
+    return P.oracle_for(probe_states(counts), model=probe_model()[0], enable_contact=True)
 
 
 def test_oracle_alone_produces_every_case():
@@ -181,51 +176,14 @@ def test_oracle_alone_produces_every_case():
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
 @functools.lru_cache(maxsize=None)
-def _mlib():
-    from tests.gpu_util import DEV, synth_tables
-    from vid2player3d_amd.motion_lib import MotionLib
-
-    return MotionLib(synth_tables(seed=5, num_clips=8, min_frames=60, max_frames=120), DEV)
-
-
-@functools.lru_cache(maxsize=None)
 def run_case(n, build):
     """One control step of the kernel from the probe poses and the oracle's step from the same state with the kernel's vertices forced
     (its own picks and their margins beside them).  Shared by the tests; nothing modifies what it returns."""
-    import torch
-
-    from tests.gpu_util import N, T, close, make_task
-
     counts = {34: COUNTS_34, 3: COUNTS_3}[n]
-    model, _ = probe_model()
-    task = make_task(n, _mlib(), body_model=model, enable_contact=True, residual_force_hold="first_sim", debug_contacts=2, pair_envs_by_load=False,
-                     kernel_build=build, contact_solver="pgs", joint_limits=False)
-    task.reset_with_times(None, T(np.full(n, 0.3)))
-    root, dpos, dvel = probe_states(counts)
-    task._humanoid_root_states[:] = T(root)
-    task._dof_pos[:] = T(dpos)
-    task._dof_vel[:] = T(dvel)
-    task._reset_env_tensors(None)
-    oracle = oracle_for(counts)
     # PD targets = the pose the probes stand in (all joints at zero), no residual wrench: the drives hold the pose, what moves the links
     # is gravity, the root's velocity and the contacts
-    act = np.zeros((n, 75), dtype=np.float32)
-    rb0 = N(task._rigid_body_state).reshape(n, NB, 13).copy()
-    dpos_before = N(task._dof_pos).copy()
-    task.pre_physics_step(T(act))
-    task._physics_step()
-    torch.cuda.synchronize()
-    pd_tar = N(task._pd_target)
-    _, pd_ref, _, force, torque = O.pre_physics(act, N(task.reset_buf), dpos_before, rb0[:, 0, 3:7], task.body_model.kp.astype(np.float32))
-    close(pd_tar, pd_ref, 1e-6, "pd target")
-    got = {"root": N(task._humanoid_root_states), "dpos": N(task._dof_pos), "dvel": N(task._dof_vel), "rb": N(task._rigid_body_state).reshape(n, NB, 13),
-           "cf": N(task._contact_forces), "df": N(task.dof_force_tensor), "ids": N(task.debug_contacts()), "ids_sub": N(task.debug_contacts_substeps())}
-    name = task.kernel_build()
-    task.close()
-    sens = oracle.sensitivity(pd_tar, force, torque, nsub=NSUB, hold=2, forced_ids=got["ids_sub"], seed=n)
-    ref = oracle.step(pd_tar, force, torque, nsub=NSUB, hold=2, forced_ids=got["ids_sub"], want_selection=True)
-    ref["sens"] = sens
-    return got, ref, name
+    got = S.kernel_step(*probe_states(counts), np.zeros((n, 75), dtype=np.float32), build=build, body_model=probe_model()[0])
+    return got, S.reference(oracle_for(counts), got)
 
 
 CASES = [(3, 1), (3, 2), (34, 1), (34, 2)]
@@ -234,8 +192,7 @@ CASES = [(3, 1), (3, 2), (34, 1), (34, 2)]
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,build", CASES)
 def test_contact_vertex_ids_equal_the_oracles_in_every_substep(n, build):
-    got, ref, name = run_case(n, build)
-    assert name.startswith({1: "lds-parked", 2: "registers"}[build])
+    got, ref = run_case(n, build)  # (it asserts that the build is the one asked for)
     counts = {34: COUNTS_34, 3: COUNTS_3}[n]
     ids, own = got["ids_sub"], ref["own"]
     assert ids.shape == own.shape == (n, NSUB, NB, 4)
@@ -255,9 +212,9 @@ def test_contact_vertex_ids_equal_the_oracles_in_every_substep(n, build):
 def test_state_after_one_control_step_matches_oracle(n, build):
     """The drives hold the probe pose (PD targets = the pose), so the step is as well conditioned as the parity fixtures' and the
     parity tests' bounds apply as they are: measured, 2 of 34 envs need the conditioning term (4 may), largest share of a bound 0.03."""
-    from tests.test_gpu_physics import _compare
+    from tests.gpu_util import _compare
 
-    got, ref, _ = run_case(n, build)
+    got, ref = run_case(n, build)
     assert np.abs(got["cf"]).max() > 1.0, "the contacts must carry load"
     _compare(got, ref, "probe poses n=%d build %d" % (n, build))
 
@@ -267,7 +224,7 @@ def test_state_after_one_control_step_matches_oracle(n, build):
 def test_same_env_next_to_different_partners_gives_identical_bits(build):
     """Envs 4, 8 and 11 hold the same state beside partners with 4, 0 and 0 near links, in the lower and the upper half of the wave:
     the same vertices in every substep and bit-identical states and forces."""
-    got, _, _ = run_case(34, build)
+    got, _ = run_case(34, build)
     for other in (8, 11):
         assert np.array_equal(got["ids_sub"][4], got["ids_sub"][other])
         for key in ("root", "dpos", "dvel", "rb", "cf", "df"):

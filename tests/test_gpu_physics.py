@@ -13,7 +13,8 @@ import torch
 
 from oracle import task_oracle as O
 from oracle.phys_oracle import BatchOracle, default_params
-from tests.gpu_util import DEV, N, T, close, make_task, rows_close, synth_tables
+from tests.gpu_util import (DEV, FORCE_ATOL, FORCE_RTOL, K_SENS, POS_ATOL, VEL_ATOL, VEL_RTOL, N, T, _compare, assert_none_over, close, make_task,
+                            rows_all, rows_close, synth_tables)  # noqa: F401  (rows_all: tools/parity_sweep.py reads it from this module)
 
 pytestmark = pytest.mark.gpu
 
@@ -119,47 +120,6 @@ def _run_pair(mlib, n, contact, seed, lift=0.0, vel_sigma=0.5, steps=1, hold="fi
         task.post_physics_step()
     task.close()
     return out
-
-
-# Velocities and forces are judged PER ELEMENT on EVERY env:  |hip - oracle| <= atol + rtol |oracle| + K_SENS * sens,  float32 O(n)
-# recursion against float64 dense solve after 4 substeps.  `sens` is the CONDITIONING of the oracle's own step at that element
-# (BatchOracle.sensitivity: largest change of the float64 result when its inputs are perturbed by float32 rounding - 2e-7 on positions
-# and quaternions, 1e-6 on velocities).  Why it is there (round 4, profiles/r04_parity_*.log, tools/gain_probe.py): the step map of
-# this model is piecewise linear but NOT contractive - box friction bounded by the current normal impulse couples the rows
-# non-symmetrically - and in ~1 % of the perturbed states of these fixtures one substep multiplies a velocity perturbation by 10^2 and
-# more (the float64 oracle does this to itself).  Those envs are exactly the ones that used to miss the flat bound, by the amounts the
-# oracle's sensitivity predicts (error / sens 0.1 .. 9 in every one of 78 dumped outliers), in the precise build
-# (V2P_LL_STRICT_MATH) and in the env-per-lane kernel as often as in the default build.  No share of the envs is exempt any more.
-# Measured (pytest -s prints the percentiles of every comparison): median error 5e-7 .. 2e-6, 99th percentile 1e-5 .. 5e-5.
-VEL_ATOL, VEL_RTOL = 2e-4, 5e-4
-FORCE_ATOL, FORCE_RTOL = 0.05, 1e-3
-POS_ATOL = 2e-5
-K_SENS = 16.0   # the kernel's result must be what the oracle gives for inputs within K_SENS x float32 rounding
-
-
-def assert_none_over(bad, what):
-    assert not bad.any(), "%s: %d of %d envs over the per-element bounds (envs %s)" % (what, int(bad.sum()), bad.shape[0], np.nonzero(bad)[0][:8].tolist())
-
-
-def rows_all(got, ref, what, contact=True, k_sens=K_SENS):
-    """Every per-element comparison of one control step; returns the mask of the envs over a bound."""
-    S = ref["sens"]
-    qs = np.sign(np.sum(got["rb"][..., 3:7] * ref["rb"][..., 3:7], axis=-1, keepdims=True))  # quaternion sign is arbitrary
-    bad = rows_close(got["root"][:, :3], ref["root"][:, :3], POS_ATOL, 0.0, what + " root pos", S["root"][:, :3], k_sens)
-    bad |= rows_close(got["dpos"], ref["dpos"], 5e-5, 0.0, what + " dof_pos", S["dpos"], k_sens)
-    bad |= rows_close(got["rb"][..., :3], ref["rb"][..., :3], POS_ATOL, 0.0, what + " rb pos", S["rb"][..., :3], k_sens)
-    bad |= rows_close(got["rb"][..., 3:7] * qs, ref["rb"][..., 3:7], POS_ATOL, 0.0, what + " rb rot", S["rb"][..., 3:7], k_sens)
-    bad |= rows_close(got["root"][:, 7:], ref["root"][:, 7:], VEL_ATOL, VEL_RTOL, what + " root vel", S["root"][:, 7:], k_sens)
-    bad |= rows_close(got["dvel"], ref["dvel"], VEL_ATOL, VEL_RTOL, what + " dof_vel", S["dvel"], k_sens)
-    bad |= rows_close(got["rb"][..., 7:], ref["rb"][..., 7:], VEL_ATOL, VEL_RTOL, what + " rb vel", S["rb"][..., 7:], k_sens)
-    bad |= rows_close(got["df"], ref["df"], FORCE_ATOL, FORCE_RTOL, what + " dof force", S["df"], k_sens)
-    if contact:
-        bad |= rows_close(got["cf"], ref["cf"], FORCE_ATOL, FORCE_RTOL, what + " contact force", S["cf"], k_sens)
-    return bad
-
-
-def _compare(got, ref, what, contact=True):
-    assert_none_over(rows_all(got, ref, what, contact), what)
 
 
 def test_pd_only_step_matches_oracle(mlib):

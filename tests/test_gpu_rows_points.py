@@ -2,9 +2,9 @@
 the two stops of a visit, each with three rows, and which of them run.  A point exists for a lane when the lane's link has that many
 points; it is solved when it carries a normal impulse or is not separating.  One control step (4 substeps x 4 sweeps), PGS, both builds
 of the kernel, with the launch uncut and cut into substep jobs, batches of 1, 2 and 3 envs (a wave with one env, a wave with two, a lone
-env in a second wave) - against the float64 C oracle (oracle/phys) with the bound rows_all of tests/test_gpu_physics.py, and bit for bit
+env in a second wave) - against the float64 C oracle (oracle/phys) with the bound rows_all of tests/gpu_util.py, and bit for bit
 between batches.  Poses, their builder, the states that keep every hull vertex MARGIN away from the contact offset and the oracle set-up
-are those of tests/test_gpu_walk_down.py (`hover`, `late`: tests/test_gpu_sweep_visits.py); `wake` is new here.
+are those of tests/phys_poses.py, the step and its reference those of tests/phys_step.py; `wake` is new here.
 
 An env is (pose, state number); a batch is a list of envs:
   partner   env A's bits are the same alone, beside X (standing: four stops of four points), beside Y (lying on its back: nine stops,
@@ -24,12 +24,9 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import task_oracle as O
-from oracle.phys_oracle import BatchOracle, default_params
-from tests import test_gpu_sweep_visits as V
-from tests import test_gpu_walk_down as D
-from tests import test_gpu_walk_up as W
-from tests.test_gpu_tree_passes import NB, NSUB, _mlib, _model, _rot_expmap, _rot_quat, lowest_point
+from tests import phys_poses as P
+from tests import phys_step as S
+from tests.phys_poses import FEET, NSUB, _names, _quat_of, _rot_expmap, _rot_quat, lowest_point
 
 WAKE_STATE, WAKE_PITCH = 2, 0.012   # wake: which `feet` state, and its pitch about the body's left axis, rad (found on the CPU: see the fixture test)
 MODES = [(build, jobs) for build in (1, 2) for jobs in (0, 2)]   # (kernel_build, substep_jobs)
@@ -50,41 +47,30 @@ REQUIRED_COUNTS = {(1, 4), (4, 1), (2, 3), (4, 4)}
 
 @functools.lru_cache(maxsize=None)
 def wake_state(seed, k):
-    """`feet` state WAKE_STATE + k of tests/test_gpu_walk_up.py, pitched by WAKE_PITCH about the body's left axis and set down again
-    (the lowest vertex as deep in the ground as that state's draw of W.SINK)."""
-    root, dpos, dvel, wrench = [a.copy() for a in W.state("feet", seed, WAKE_STATE + k)]
-    sink = np.random.default_rng([131, seed, WAKE_STATE + k]).uniform(*W.SINK)
-    root[3:7] = W._quat_of(_rot_expmap(W.X * WAKE_PITCH) @ _rot_quat(root[3:7])).astype(np.float32)
+    """`feet` state WAKE_STATE + k of tests/phys_poses.py, pitched by WAKE_PITCH about the body's left axis and set down again
+    (the lowest vertex as deep in the ground as a draw of P.SINK)."""
+    root, dpos, dvel, wrench = [a.copy() for a in P.state("feet", seed, WAKE_STATE + k)]
+    sink = np.random.default_rng([131, seed, WAKE_STATE + k]).uniform(*P.SINK)
+    root[3:7] = _quat_of(_rot_expmap(P.X * WAKE_PITCH) @ _rot_quat(root[3:7])).astype(np.float32)
     root[2] = -lowest_point(root[3:7], dpos).min() - sink
     return root, dpos, dvel, wrench
 
 
 @functools.lru_cache(maxsize=None)
 def env_state(pose, k):
-    return wake_state(0, k) if pose == "wake" else D.well_conditioned(pose, 0, k)
+    return wake_state(0, k) if pose == "wake" else P.well_conditioned(pose, 0, k)
 
 
 def states(batch):
-    parts = [env_state(pose, k) for pose, k in batch]
-    return [np.stack([p[i] for p in parts]) for i in range(4)]
+    return P.stack(env_state(pose, k) for pose, k in batch)
 
 
-def actions(batch):
-    _, dpos, _, wrench = states(batch)
-    return np.concatenate([dpos, wrench], axis=1).astype(np.float32)
-
-
-def oracle_for(batch, **kw):
-    root, dpos, dvel, _ = states(batch)
-    oracle = BatchOracle(_model(), len(batch), default_params(solver_type=0, **kw))
-    oracle.set_state(root, dpos, dvel)
-    return oracle
+def oracle_for(batch, **params):
+    return P.oracle_for(states(batch), solver_type=0, **params)
 
 
 def oracle_inputs(batch):
-    root, dpos, _, _ = states(batch)
-    _, pd, _, force, torque = O.pre_physics(actions(batch), np.zeros(len(batch), dtype=np.int64), dpos, root[:, 3:7], _model().kp.astype(np.float32))
-    return pd, force, torque
+    return P.oracle_inputs(states(batch))
 
 
 @functools.lru_cache(maxsize=None)
@@ -108,8 +94,8 @@ def visit_counts(batch):
 
 def test_fixtures_are_what_they_claim():
     """CPU, from one substep of the oracle per env."""
-    names = W._names()
-    feet = [names.index(c) for c in V.FEET]
+    names = _names()
+    feet = [names.index(c) for c in FEET]
     # partners: X has four stops of four points and solves them all, Y has more stops and stops of 1 - 3 points, Z solves nothing
     sx, cx, fx = first_substep(X, 4)
     sy, cy, fy = first_substep(Y, 4)
@@ -144,46 +130,15 @@ def test_fixtures_are_what_they_claim():
 @functools.lru_cache(maxsize=None)
 def run_kernel(batch, build, jobs):
     """One control step of the kernel from a batch's states.  Shared by the tests; nothing modifies what it returns."""
-    import torch
-
-    from tests.gpu_util import N, T, close, make_task
-
-    n = len(batch)
-    task = make_task(n, _mlib(), enable_contact=True, residual_force_hold="first_sim", debug_contacts=2, pair_envs_by_load=False,
-                     kernel_build=build, contact_solver="pgs", joint_limits=False, substep_jobs=jobs)
-    task.reset_with_times(None, T(np.full(n, 0.3)))
-    root, dpos, dvel, _ = states(batch)
-    task._humanoid_root_states[:] = T(root)
-    task._dof_pos[:] = T(dpos)
-    task._dof_vel[:] = T(dvel)
-    task._reset_env_tensors(None)
-    act = actions(batch)
-    rb0 = N(task._rigid_body_state).reshape(n, NB, 13).copy()
-    dpos_before = N(task._dof_pos).copy()
-    task.pre_physics_step(T(act))
-    task._physics_step()
-    torch.cuda.synchronize()
-    pd_tar = N(task._pd_target)
-    _, pd_ref, _, force, torque = O.pre_physics(act, N(task.reset_buf), dpos_before, rb0[:, 0, 3:7], task.body_model.kp.astype(np.float32))
-    close(pd_tar, pd_ref, 1e-6, "pd target")
-    got = {"root": N(task._humanoid_root_states), "dpos": N(task._dof_pos), "dvel": N(task._dof_vel), "rb": N(task._rigid_body_state).reshape(n, NB, 13),
-           "cf": N(task._contact_forces), "df": N(task.dof_force_tensor), "ids": N(task.debug_contacts()), "ids_sub": N(task.debug_contacts_substeps()),
-           "pd": pd_tar, "force": force, "torque": torque}
-    name = task.kernel_build()
-    task.close()
-    assert name.startswith({1: "lds-parked", 2: "registers"}[build])
-    return got
+    st = states(batch)
+    return S.kernel_step(*st[:3], P.actions(st), build=build, substep_jobs=jobs)
 
 
 @functools.lru_cache(maxsize=None)
 def _reference(batch, ids_bytes):
     got = run_kernel(batch, 1, 0)
     ids = np.frombuffer(ids_bytes, dtype=got["ids_sub"].dtype).reshape(got["ids_sub"].shape)
-    oracle = oracle_for(batch)
-    sens = oracle.sensitivity(got["pd"], got["force"], got["torque"], nsub=NSUB, hold=2, forced_ids=ids, seed=len(batch))
-    ref = oracle.step(got["pd"], got["force"], got["torque"], nsub=NSUB, hold=2, forced_ids=ids, want_selection=True)
-    ref["sens"] = sens
-    return ref
+    return S.reference(oracle_for(batch), dict(got, ids_sub=ids))
 
 
 def reference(batch, got):
@@ -196,7 +151,7 @@ def reference(batch, got):
 
 
 def compare(batch, build, jobs, what):
-    from tests.test_gpu_physics import _compare
+    from tests.gpu_util import _compare
 
     got = run_kernel(batch, build, jobs)
     ref = reference(batch, got)
@@ -218,7 +173,7 @@ def test_env_bits_do_not_depend_on_the_partner(a, build, jobs):
     for batch, e in (((A, X), 0), ((A, Y), 0), ((A, Z), 0)):
         got = run_kernel(batch, build, jobs)
         partners.append(got["dvel"][1])
-        for key in ("root", "dpos", "dvel", "rb", "cf", "df", "ids_sub"):
+        for key in S.BITS:
             assert np.array_equal(alone[key][0], got[key][e]), (a, batch, key)
     assert not np.array_equal(partners[0], partners[1]) and not np.array_equal(partners[0], partners[2]), "the partners must differ"
     loaded = np.abs(alone["cf"]).max() > 1.0
@@ -243,7 +198,7 @@ def test_point_that_wakes_up_matches_oracle(name, build, jobs):
     batch = tuple(WAKE_BATCHES[name])
     got, _ = compare(batch, build, jobs, "wake " + name)
     e = batch.index(A_ENVS["wake"])
-    feet = [W._names().index(c) for c in V.FEET]
+    feet = [_names().index(c) for c in FEET]
     assert (np.abs(got["cf"][e][feet]).max(axis=-1) > 0).all(), "both feet must carry load at the end of the step"
 
 

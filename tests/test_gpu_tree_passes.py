@@ -6,11 +6,11 @@ Three fixtures, built here from the baked body (forward kinematics in numpy deci
   air       every joint bent by 0.15 .. 0.45 rad, joint rates of ~1 rad/s, root tilted, tumbling and high above the ground: with
             enable_contact=False passes 1 - 3 and the integrator alone decide the result, every level of the tree, the links with two
             extra children (pelvis, chest) and the leaves all carry nonzero contributions.  Bound: the FLAT per-element bound of
-            tests/test_gpu_physics.py, no conditioning term.
+            tests/gpu_util.py, no conditioning term.
   standing  upright on both feet (deepest touched links: the toes, depth 4), drives holding the pose.
   fallen    on the ground with the arms spread, rolled about the body's long axis onto one hand (left in the even states, right in the
             odd ones): the deepest touched link is a hand, depth 8.
-            Bound of both: rows_all of tests/test_gpu_physics.py (conditioning-aware, at most 2 % of the envs / 4 envs may need the
+            Bound of both: rows_all of tests/gpu_util.py (conditioning-aware, at most 2 % of the envs / 4 envs may need the
             conditioning term); test_contact_fixtures_are_well_conditioned checks on the CPU that the float64 oracle, perturbed at the
             level of float32 rounding, stays inside that cap on its own.
 Env 0 holds the same state in the 3-env and in the 34-env batch beside different partners: its bits must not depend on the partner."""
@@ -19,11 +19,10 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import task_oracle as O
-from oracle.phys_oracle import BatchOracle, default_params
+from tests import phys_poses as P
+from tests import phys_step as S
+from tests.phys_poses import STATE_IDS, _depths, lowest_point
 
-NSUB = 4
-NB = 24
 SIZES = (3, 34)
 CASES = [(n, build) for n in SIZES for build in (1, 2)]
 KINDS = ("air", "standing", "fallen")
@@ -31,55 +30,6 @@ REST_VEL = {"standing": 0.05, "fallen": 0.05}       # joint rates of the resting
 SINK = {"standing": (0.002, 0.004), "fallen": (0.002, 0.004)}  # how far the lowest vertex is inside the ground, m
 ROLL = (0.05, 0.25)  # rad
 SEEDS = {"air": 0, "standing": 2, "fallen": 0}  # (chosen on the CPU: test_contact_fixtures_are_well_conditioned)
-# state number of every env: env 0 is state 0 in both batches, its partner (env 1) is state 1 in one and state 3 in the other
-STATE_IDS = {3: [0, 1, 2], 34: [0] + list(range(3, 36))}
-
-
-def _model():
-    from vid2player3d_amd.model import load_baked_model
-
-    return load_baked_model()
-
-
-def _depths():
-    par = np.asarray(_model().parents)
-    dep = np.zeros(NB, dtype=int)
-    for b in range(1, NB):
-        dep[b] = dep[par[b]] + 1
-    return dep
-
-
-def _rot_expmap(v):
-    a = float(np.linalg.norm(v))
-    if a < 1e-12:
-        return np.eye(3)
-    k = np.asarray(v, dtype=np.float64) / a
-    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
-    return np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
-
-
-def _rot_quat(q):  # xyzw
-    x, y, z, w = [float(c) for c in q]
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-
-
-def lowest_point(quat, dpos):
-    """Height of the lowest hull vertex of every link above the root's origin (forward kinematics, float64)."""
-    m = _model()
-    par, lp = np.asarray(m.parents), np.asarray(m.local_pos, dtype=np.float64)
-    hv, ho = np.asarray(m.hull_verts, dtype=np.float64), np.asarray(m.hull_offsets)
-    R, x = [None] * NB, np.zeros((NB, 3))
-    R[0] = _rot_quat(quat)
-    low = np.zeros(NB)
-    for b in range(NB):
-        if b:
-            p = int(par[b])
-            x[b] = x[p] + R[p] @ lp[b]
-            R[b] = R[p] @ _rot_expmap(dpos[3 * (b - 1):3 * b])
-        low[b] = (hv[ho[b]:ho[b + 1]] @ R[b].T)[:, 2].min() + x[b, 2]
-    return low
 
 
 @functools.lru_cache(maxsize=None)
@@ -118,21 +68,11 @@ def state(kind, k):
 
 
 def states(kind, n):
-    parts = [state(kind, k) for k in STATE_IDS[n]]
-    return [np.stack([p[i] for p in parts]) for i in range(4)]
-
-
-def actions(kind, n):
-    """PD targets = the pose the fixture is in (the drives hold it), plus the fixture's residual wrench."""
-    _, dpos, _, wrench = states(kind, n)
-    return np.concatenate([dpos, wrench], axis=1).astype(np.float32)
+    return P.stack(state(kind, k) for k in STATE_IDS[n])
 
 
 def oracle_for(kind, n):
-    root, dpos, dvel, _ = states(kind, n)
-    oracle = BatchOracle(_model(), n, default_params(enable_contact=kind != "air"))
-    oracle.set_state(root, dpos, dvel)
-    return oracle
+    return P.oracle_for(states(kind, n), enable_contact=kind != "air")
 
 
 @pytest.mark.parametrize("kind", ["standing", "fallen"])
@@ -141,83 +81,32 @@ def test_contact_fixtures_are_well_conditioned(kind, n):
     """CPU: the fixtures touch the ground with the links they were built for (the deepest touched link sets how far the Lambda recursion
     runs), and the float64 oracle moved by float32 rounding of its inputs (the largest change over 32 perturbed runs, on every element)
     against itself needs the conditioning term in no more envs than rows_close allows - it asserts that cap itself."""
-    from tests.gpu_util import N  # noqa: F401  (the helpers import torch; no GPU is touched here)
-    from tests.test_gpu_physics import rows_all
-
     dep = _depths()
-    root, dpos, _, _ = states(kind, n)
-    act = actions(kind, n)
-    reset = np.zeros(n, dtype=np.int64)
-    _, pd, _, force, torque = O.pre_physics(act, reset, dpos, root[:, 3:7], _model().kp.astype(np.float32))
-    own = oracle_for(kind, n).step(pd, force, torque, nsub=NSUB, hold=2, want_selection=True)["own"]
+    inputs = P.oracle_inputs(states(kind, n))
+    own = oracle_for(kind, n).step(*inputs, nsub=P.NSUB, hold=2, want_selection=True)["own"]
     touched = (own >= 0).any(axis=-1)  # [n, nsub, NB]
     deepest = np.where(touched, dep[None, None, :], -1).max(axis=2)
     assert (deepest[:, 0] == {"standing": 4, "fallen": 8}[kind]).all(), deepest[:, 0].tolist()
     assert (touched[:, 0].sum(axis=1) >= {"standing": 2, "fallen": 1}[kind]).all()
-    oracle = oracle_for(kind, n)
-    sens = oracle.sensitivity(pd, force, torque, nsub=NSUB, hold=2, forced_ids=own, seed=n)
-    ref = oracle.step(pd, force, torque, nsub=NSUB, hold=2, forced_ids=own)
-    ref["sens"] = sens
-    moved = {k: ref[k] + sens[k] for k in ("root", "dpos", "dvel", "rb", "cf", "df")}
-    bad = rows_all(moved, ref, "oracle at float32 rounding, %s n=%d" % (kind, n))
-    assert not bad.any()
+    S.assert_oracle_holds_its_own_bound(oracle_for(kind, n), inputs, own, "%s n=%d" % (kind, n))
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
 @functools.lru_cache(maxsize=None)
-def _mlib():
-    from tests.gpu_util import DEV, synth_tables
-    from vid2player3d_amd.motion_lib import MotionLib
-
-    return MotionLib(synth_tables(seed=5, num_clips=8, min_frames=60, max_frames=120), DEV)
-
-
-@functools.lru_cache(maxsize=None)
 def run_case(kind, n, build):
     """One control step of the kernel from a fixture and the oracle's step from the same state (with the kernel's contact vertices
     forced).  Shared by the tests; nothing modifies what it returns."""
-    import torch
-
-    from tests.gpu_util import N, T, close, make_task
-
-    contact = kind != "air"
-    task = make_task(n, _mlib(), enable_contact=contact, residual_force_hold="first_sim", debug_contacts=2, pair_envs_by_load=False,
-                     kernel_build=build, contact_solver="pgs", joint_limits=False)
-    task.reset_with_times(None, T(np.full(n, 0.3)))
-    root, dpos, dvel, _ = states(kind, n)
-    task._humanoid_root_states[:] = T(root)
-    task._dof_pos[:] = T(dpos)
-    task._dof_vel[:] = T(dvel)
-    task._reset_env_tensors(None)
-    oracle = oracle_for(kind, n)
-    act = actions(kind, n)
-    rb0 = N(task._rigid_body_state).reshape(n, NB, 13).copy()
-    dpos_before = N(task._dof_pos).copy()
-    task.pre_physics_step(T(act))
-    task._physics_step()
-    torch.cuda.synchronize()
-    pd_tar = N(task._pd_target)
-    _, pd_ref, _, force, torque = O.pre_physics(act, N(task.reset_buf), dpos_before, rb0[:, 0, 3:7], task.body_model.kp.astype(np.float32))
-    close(pd_tar, pd_ref, 1e-6, "pd target")
-    got = {"root": N(task._humanoid_root_states), "dpos": N(task._dof_pos), "dvel": N(task._dof_vel), "rb": N(task._rigid_body_state).reshape(n, NB, 13),
-           "cf": N(task._contact_forces), "df": N(task.dof_force_tensor), "ids": N(task.debug_contacts()), "ids_sub": N(task.debug_contacts_substeps())}
-    name = task.kernel_build()
-    task.close()
-    assert name.startswith({1: "lds-parked", 2: "registers"}[build])
-    forced = got["ids_sub"] if contact else None
-    sens = oracle.sensitivity(pd_tar, force, torque, nsub=NSUB, hold=2, forced_ids=forced, seed=n) if contact else None
-    ref = oracle.step(pd_tar, force, torque, nsub=NSUB, hold=2, forced_ids=forced, want_selection=True)
-    ref["sens"] = sens
-    return got, ref
+    st = states(kind, n)
+    got = S.kernel_step(*st[:3], P.actions(st), build=build, contact=kind != "air")
+    return got, S.reference(oracle_for(kind, n), got, contact=kind != "air")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,build", CASES)
 def test_pd_only_step_matches_oracle_at_the_flat_bound(n, build):
-    """Passes 1 - 3 and the integrator alone: every element of every env within the flat bounds of tests/test_gpu_physics.py, no
+    """Passes 1 - 3 and the integrator alone: every element of every env within the flat bounds of tests/gpu_util.py, no
     conditioning term (docs/NOTES.md A: PD-only runs never needed one; largest velocity error measured there 8e-6 rad/s)."""
-    from tests.gpu_util import rows_close
-    from tests.test_gpu_physics import POS_ATOL, VEL_ATOL, VEL_RTOL, FORCE_ATOL, FORCE_RTOL, assert_none_over
+    from tests.gpu_util import FORCE_ATOL, FORCE_RTOL, POS_ATOL, VEL_ATOL, VEL_RTOL, assert_none_over, rows_close
 
     got, ref = run_case("air", n, build)
     what = "tree passes, PD only n=%d build %d" % (n, build)
@@ -241,7 +130,7 @@ def test_pd_only_step_matches_oracle_at_the_flat_bound(n, build):
 @pytest.mark.parametrize("n,build", CASES)
 def test_contact_step_matches_oracle(kind, n, build):
     """With contacts: the Lambda recursion runs to depth 4 (standing, toes) and to depth 8 (fallen, hands); bounds of rows_all."""
-    from tests.test_gpu_physics import _compare
+    from tests.gpu_util import _compare
 
     got, ref = run_case(kind, n, build)
     dep = _depths()
@@ -257,8 +146,4 @@ def test_contact_step_matches_oracle(kind, n, build):
 @pytest.mark.parametrize("build", [1, 2])
 def test_env_bits_do_not_depend_on_the_partner(kind, build):
     """Env 0 holds the same state in the 3-env and in the 34-env batch; the env it shares its wave with differs."""
-    a, _ = run_case(kind, 3, build)
-    b, _ = run_case(kind, 34, build)
-    assert not np.array_equal(a["dvel"][1], b["dvel"][1]), "the partners must differ"
-    for key in ("root", "dpos", "dvel", "rb", "cf", "df", "ids_sub"):
-        assert np.array_equal(a[key][0], b[key][0]), key
+    S.assert_env0_ignores_its_partner(run_case(kind, 3, build)[0], run_case(kind, 34, build)[0])

@@ -1,8 +1,8 @@
 """The way down of the contact sweep's walk, the closing move and the closing root -> leaves pass, and the head and tail of a visit
 (walk_to, walk_close and the visit loop of the link-per-lane physics kernel) - against the float64 C oracle (oracle/phys), one control
 step (4 substeps x 4 sweeps), PGS, both builds of the kernel, batches of 2 envs (one full wave), 3 envs (a full wave and a wave with
-one env) and 34 envs.  Poses, their builder, the oracle set-up and the bound (rows_all of tests/test_gpu_physics.py with its cap on the
-conditioning term) are those of tests/test_gpu_walk_up.py; `hover` is that of tests/test_gpu_sweep_visits.py; `sit` is new here.
+one env) and 34 envs.  Poses, their builder, the oracle set-up and the bound (rows_all of tests/gpu_util.py with its cap on the
+conditioning term) are those of tests/phys_poses.py and tests/phys_step.py, `hover` and `sit` among them.
 
 Named by what they make the changed loops do (links are lanes in depth-first order; a move goes up from the stop the walk stands on to
 the lowest common ancestor and down to the next stop, level by level, for both envs of a wave at once):
@@ -34,22 +34,14 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import task_oracle as O
-from oracle.phys_oracle import BatchOracle, default_params
-from tests import test_gpu_sweep_visits as V
-from tests import test_gpu_walk_up as W
-from tests.test_gpu_tree_passes import NB, NSUB, _depths, _mlib, _model, _rot_expmap, _rot_quat, lowest_point
+from tests import phys_poses as P
+from tests import phys_step as S
+from tests.phys_poses import CONTACT_OFFSET, FEET, FLAT_MIN_TOUCHED, MARGIN, NB, POSES, SIT, STATE_IDS, _depths, _model, _names, vertex_heights
 
 SIZES = (2, 3, 34)
 CASES = [(n, build) for n in SIZES for build in (1, 2)]
-CONTACT_OFFSET = 0.02   # a hull vertex closer to the ground than this is a contact point, m
-MARGIN = 1e-4           # EVERY hull vertex of every link is at least this far from CONTACT_OFFSET in the state a step starts from, m
-# nominal state number of every env (env 0 is state 0 in every batch; its partner differs between the 3-env and the 34-env batch).  The state an
-# env really gets is the first of k, k + 100, k + 200, ... whose hull vertices all keep MARGIN: well_conditioned()
-STATE_IDS = {2: [0, 1], 3: W.STATE_IDS[3], 34: W.STATE_IDS[34]}
-STRIDE, TRIES = 100, 200
-# sit: the baked body lies on its back; legs raised to the vertical, spine and chest curled up, a tilt of the root levels Pelvis and Torso
-SIT = ({"L_Hip": W.X * -np.pi / 2, "R_Hip": W.X * -np.pi / 2, "Spine": W.X * 1.0, "Chest": W.X * 0.5}, ("Pelvis", "Torso"), W.X)
+# STATE_IDS gives the nominal state number of every env; the state an env really gets is the first of k, k + 100, k + 200, ... whose hull
+# vertices all keep MARGIN from the contact offset: phys_poses.well_conditioned()
 # (the 3-env batch - its first two envs are the 2-env batch -, the first pair of the 34-env batch, the pairs that fill it)
 FIXTURES = {
     "one_level": (["ankle_toe", "ankle_toe", "ankle_toe"], ["ankle_toe", "head"], [("ankle_toe", "ankle_toe"), ("ankle_toe", "head"), ("head", "ankle_toe")]),
@@ -63,7 +55,7 @@ FIXTURES = {
     "counts": (["flat", "flat2", "feet"], ["flat", "ankle_toe"], [("flat", "feet"), ("feet", "hands"), ("feet", "flat"), ("hands", "feet")]),
 }
 SEEDS = dict.fromkeys(FIXTURES, 0)
-TOUCHING = {"hover": V.FEET, "sit": SIT[1], "flat2": None}
+TOUCHING = {"hover": FEET, "sit": SIT[1], "flat2": None}
 
 
 def env_poses(fixture, n):
@@ -73,117 +65,28 @@ def env_poses(fixture, n):
     return first + [p for i in range(16) for p in fill[i % len(fill)]]
 
 
-@functools.lru_cache(maxsize=None)
-def sit_state(seed, k):
-    """As state() of tests/test_gpu_walk_up.py, for the pose SIT: the tilt of the root about the body's left axis is solved so that
-    the lowest vertices of Pelvis and Torso are level; every other link stays more than W.CLEAR above them."""
-    names = W._names()
-    rng = np.random.default_rng([1009, seed, k])
-    joints, chosen, axis = SIT
-    fixed = {names.index(j): _rot_expmap(v) for j, v in joints.items()}
-    R0 = _rot_expmap(rng.normal(0, 0.002, size=3))
-    noise = rng.normal(0, 0.004, size=69)
-    dpos = np.concatenate([W._expmap_of(fixed.get(b, np.eye(3)) @ _rot_expmap(noise[3 * (b - 1):3 * b])) for b in range(1, NB)])
-    ids = [names.index(c) for c in chosen]
-
-    def resid(a):
-        low = lowest_point(W._quat_of(_rot_expmap(axis * a) @ R0), dpos)[ids]
-        return low[1] - low[0]
-
-    lo, hi = -0.6, 0.6  # (bisection: the difference of the two lowest vertices is monotonic in the tilt over this range)
-    assert resid(lo) * resid(hi) < 0, (resid(lo), resid(hi))
-    for _ in range(60):
-        mid = 0.5 * (lo + hi)
-        lo, hi = (mid, hi) if resid(lo) * resid(mid) > 0 else (lo, mid)
-    q = W._quat_of(_rot_expmap(axis * 0.5 * (lo + hi)) @ R0)
-    root = np.zeros(13)
-    root[3:7] = q
-    dvel = rng.normal(0, W.REST_VEL, size=69)
-    root[7:10] = rng.normal(0, 0.4 * W.REST_VEL, size=3)
-    root[10:13] = rng.normal(0, 0.4 * W.REST_VEL, size=3)
-    root, dpos, dvel = root.astype(np.float32), dpos.astype(np.float32), dvel.astype(np.float32)
-    low = lowest_point(root[3:7], dpos)
-    assert np.ptp(low[ids]) < W.LEVEL and np.delete(low, ids).min() > low[ids].max() + W.CLEAR, (k, np.round(np.sort(low) - low.min(), 4)[:6])
-    root[2] = -low.min() - rng.uniform(*W.SINK)
-    return root, dpos, dvel, rng.normal(0, 0.02, size=6).astype(np.float32)
-
-
-def state(pose, seed, k):
-    """(flat2: a `flat` state - which of them, well_conditioned() decides)"""
-    return sit_state(seed, k) if pose == "sit" else V.state("flat" if pose == "flat2" else pose, seed, k)
-
-
-def vertex_heights(root, dpos):
-    """Height above the ground of every hull vertex of every link (forward kinematics, float64), as one array, and the link of each."""
-    m = _model()
-    par, lp = np.asarray(m.parents), np.asarray(m.local_pos, dtype=np.float64)
-    hv, ho = np.asarray(m.hull_verts, dtype=np.float64), np.asarray(m.hull_offsets)
-    R, x = [None] * NB, np.zeros((NB, 3))
-    R[0] = _rot_quat(root[3:7])
-    out, link = [], []
-    for b in range(NB):
-        if b:
-            q = int(par[b])
-            x[b] = x[q] + R[q] @ lp[b]
-            R[b] = R[q] @ _rot_expmap(dpos[3 * (b - 1):3 * b])
-        out.append((hv[ho[b]:ho[b + 1]] @ R[b].T)[:, 2] + x[b, 2] + float(root[2]))
-        link.append(np.full(len(out[-1]), b))
-    return np.concatenate(out), np.concatenate(link)
-
-
-def flip_margin(st):
-    """How far the closest hull vertex of a state is from the offset plane: the smallest change of height that would make a vertex a
-    contact point or stop it being one (and so change a link's number of points, or whether it is a stop of the walk)."""
-    return float(np.abs(vertex_heights(st[0], st[1])[0] - CONTACT_OFFSET).min())
-
-
-@functools.lru_cache(maxsize=None)
-def well_conditioned(pose, seed, k):
-    """The first of the states k, k + STRIDE, ... of a pose in which every hull vertex keeps MARGIN from the offset plane."""
-    for j in range(TRIES):
-        st = state(pose, seed, k + STRIDE * j)
-        if flip_margin(st) < MARGIN:
-            continue
-        if pose in ("flat", "flat2"):  # (lying on the back: seven links or more; flat2: one of them with exactly two vertices below the plane)
-            height, link = vertex_heights(st[0], st[1])
-            below = np.bincount(link[height < CONTACT_OFFSET], minlength=NB)
-            if (below > 0).sum() < W.FLAT_MIN_TOUCHED or (pose == "flat2" and not (below == 2).any()):
-                continue
-        return st
-    raise AssertionError("no state of %s among %d keeps %g m" % (pose, TRIES, MARGIN))
-
-
 def states(fixture, n):
-    parts = [well_conditioned(pose, SEEDS[fixture], k) for pose, k in zip(env_poses(fixture, n), STATE_IDS[n])]
-    return [np.stack([p[i] for p in parts]) for i in range(4)]
+    return P.stack(P.well_conditioned(pose, SEEDS[fixture], k) for pose, k in zip(env_poses(fixture, n), STATE_IDS[n]))
 
 
-def actions(fixture, n):
-    _, dpos, _, wrench = states(fixture, n)
-    return np.concatenate([dpos, wrench], axis=1).astype(np.float32)
-
-
-def oracle_for(fixture, n):
-    root, dpos, dvel, _ = states(fixture, n)
-    oracle = BatchOracle(_model(), n, default_params(solver_type=0))
-    oracle.set_state(root, dpos, dvel)
-    return oracle
+def oracle_for(fixture, n, **params):
+    return P.oracle_for(states(fixture, n), solver_type=0, **params)
 
 
 def chosen_links(pose):
-    return TOUCHING[pose] if pose in TOUCHING else W.POSES[pose][2]
+    return TOUCHING[pose] if pose in TOUCHING else POSES[pose][2]
 
 
 def assert_touched(own, fixture, n):
     """own [n, nsub, NB, 4]: the oracle's contact selection.  In the first substep every env touches the ground with exactly the links
     its pose was built for (flat: seven or more).  Returns the touched links [n, NB] and their numbers of points [n, NB]."""
-    names = W._names()
+    names = _names()
     cnt = (own[:, 0] >= 0).sum(axis=-1)
     touched = cnt > 0
     for e, pose in enumerate(env_poses(fixture, n)):
         got = {names[b] for b in np.nonzero(touched[e])[0]}
         if chosen_links(pose) is None:
-            assert len(got) >= W.FLAT_MIN_TOUCHED, (fixture, e, sorted(got))
+            assert len(got) >= FLAT_MIN_TOUCHED, (fixture, e, sorted(got))
         else:
             assert got == set(chosen_links(pose)), (fixture, e, pose, sorted(got))
     return touched, cnt
@@ -200,14 +103,10 @@ def test_fixtures_are_what_they_claim(fixture, n):
     the contact offset in the state the step starts from; the walks these stops give are what the fixture's name says (from the tree's
     depths and parents); and the float64 oracle moved by float32 rounding of its inputs (the largest change over 32 perturbed runs, on
     every element) against itself needs the conditioning term in no more envs than rows_close allows - it asserts that cap itself."""
-    from tests.gpu_util import N  # noqa: F401  (the helpers import torch; no GPU is touched here)
-    from tests.test_gpu_physics import rows_all
-
-    names, dep, par = W._names(), _depths(), [int(p) for p in _model().parents]
+    names, dep, par = _names(), _depths(), [int(p) for p in _model().parents]
     root, dpos, _, _ = states(fixture, n)
-    act = actions(fixture, n)
-    _, pd, _, force, torque = O.pre_physics(act, np.zeros(n, dtype=np.int64), dpos, root[:, 3:7], _model().kp.astype(np.float32))
-    out = oracle_for(fixture, n).step(pd, force, torque, nsub=NSUB, hold=2, want_selection=True)
+    inputs = P.oracle_inputs(states(fixture, n))
+    out = oracle_for(fixture, n).step(*inputs, nsub=P.NSUB, hold=2, want_selection=True)
     own = out["own"]
     touched, cnt = assert_touched(own, fixture, n)
     poses = env_poses(fixture, n)
@@ -265,10 +164,8 @@ def test_fixtures_are_what_they_claim(fixture, n):
         # ... and the partner of the hovering env 0 still changes something in its FOURTH sweep: the first substep alone with three
         # and with four sweeps gives it other contact forces (an env that is struck out stays struck out, so it ran all four), and
         # the hovering env none with either
-        three = BatchOracle(_model(), n, default_params(solver_type=0, n_iter=3))
-        three.set_state(*states(fixture, n)[:3])
-        cf3 = three.step(pd, force, torque, nsub=1, hold=2)["cf"]
-        cf4 = oracle_for(fixture, n).step(pd, force, torque, nsub=1, hold=2)["cf"]
+        cf3 = oracle_for(fixture, n, n_iter=3).step(*inputs, nsub=1, hold=2)["cf"]
+        cf4 = oracle_for(fixture, n).step(*inputs, nsub=1, hold=2)["cf"]
         assert poses[0] == "hover" and poses[1] != "hover"
         assert np.abs(cf4[1] - cf3[1]).max() > 1e-6 * np.abs(cf4[1]).max() > 0.0, (np.abs(cf4[1] - cf3[1]).max(), np.abs(cf4[1]).max())
         assert np.abs(cf4[0]).max() == 0.0 and np.abs(cf3[0]).max() == 0.0
@@ -276,13 +173,7 @@ def test_fixtures_are_what_they_claim(fixture, n):
     cf = np.abs(out["cf"]).reshape(n, -1).max(axis=1)
     for e, pose in enumerate(poses):
         assert (cf[e] == 0.0) == (pose == "hover"), (fixture, e, pose, cf[e])
-    oracle = oracle_for(fixture, n)
-    sens = oracle.sensitivity(pd, force, torque, nsub=NSUB, hold=2, forced_ids=own, seed=n)
-    ref = oracle.step(pd, force, torque, nsub=NSUB, hold=2, forced_ids=own)
-    ref["sens"] = sens
-    moved = {k: ref[k] + sens[k] for k in ("root", "dpos", "dvel", "rb", "cf", "df")}
-    bad = rows_all(moved, ref, "oracle at float32 rounding, %s n=%d" % (fixture, n))
-    assert not bad.any()
+    S.assert_oracle_holds_its_own_bound(oracle_for(fixture, n), inputs, own, "%s n=%d" % (fixture, n))
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
@@ -290,37 +181,9 @@ def test_fixtures_are_what_they_claim(fixture, n):
 def run_case(fixture, n, build):
     """One control step of the kernel from a fixture and the oracle's step from the same state (with the kernel's contact vertices
     forced).  Shared by the tests; nothing modifies what it returns."""
-    import torch
-
-    from tests.gpu_util import N, T, close, make_task
-
-    task = make_task(n, _mlib(), enable_contact=True, residual_force_hold="first_sim", debug_contacts=2, pair_envs_by_load=False,
-                     kernel_build=build, contact_solver="pgs", joint_limits=False)
-    task.reset_with_times(None, T(np.full(n, 0.3)))
-    root, dpos, dvel, _ = states(fixture, n)
-    task._humanoid_root_states[:] = T(root)
-    task._dof_pos[:] = T(dpos)
-    task._dof_vel[:] = T(dvel)
-    task._reset_env_tensors(None)
-    oracle = oracle_for(fixture, n)
-    act = actions(fixture, n)
-    rb0 = N(task._rigid_body_state).reshape(n, NB, 13).copy()
-    dpos_before = N(task._dof_pos).copy()
-    task.pre_physics_step(T(act))
-    task._physics_step()
-    torch.cuda.synchronize()
-    pd_tar = N(task._pd_target)
-    _, pd_ref, _, force, torque = O.pre_physics(act, N(task.reset_buf), dpos_before, rb0[:, 0, 3:7], task.body_model.kp.astype(np.float32))
-    close(pd_tar, pd_ref, 1e-6, "pd target")
-    got = {"root": N(task._humanoid_root_states), "dpos": N(task._dof_pos), "dvel": N(task._dof_vel), "rb": N(task._rigid_body_state).reshape(n, NB, 13),
-           "cf": N(task._contact_forces), "df": N(task.dof_force_tensor), "ids": N(task.debug_contacts()), "ids_sub": N(task.debug_contacts_substeps())}
-    name = task.kernel_build()
-    task.close()
-    assert name.startswith({1: "lds-parked", 2: "registers"}[build])
-    sens = oracle.sensitivity(pd_tar, force, torque, nsub=NSUB, hold=2, forced_ids=got["ids_sub"], seed=n)
-    ref = oracle.step(pd_tar, force, torque, nsub=NSUB, hold=2, forced_ids=got["ids_sub"], want_selection=True)
-    ref["sens"] = sens
-    return got, ref
+    st = states(fixture, n)
+    got = S.kernel_step(*st[:3], P.actions(st), build=build)
+    return got, S.reference(oracle_for(fixture, n), got)
 
 
 @pytest.mark.gpu
@@ -330,7 +193,7 @@ def test_way_down_and_close_match_oracle(fixture, n, build):
     """Every env touches the ground with the links its pose was built for (the kernel's selection agrees on which links touch and on
     how many points each has), the envs that stand on something carry load, the hovering ones none, and the step is the oracle's within
     the bounds of rows_all."""
-    from tests.test_gpu_physics import _compare
+    from tests.gpu_util import _compare
 
     got, ref = run_case(fixture, n, build)
     assert_touched(ref["own"], fixture, n)
@@ -347,8 +210,4 @@ def test_way_down_and_close_match_oracle(fixture, n, build):
 def test_env_bits_do_not_depend_on_the_partner(fixture, build):
     """Env 0 holds the same state in the 3-env and in the 34-env batch; the env it shares its wave with is another state, and in most
     fixtures another pose."""
-    a, _ = run_case(fixture, 3, build)
-    b, _ = run_case(fixture, 34, build)
-    assert not np.array_equal(a["dvel"][1], b["dvel"][1]), "the partners must differ"
-    for key in ("root", "dpos", "dvel", "rb", "cf", "df", "ids_sub"):
-        assert np.array_equal(a[key][0], b[key][0]), key
+    S.assert_env0_ignores_its_partner(run_case(fixture, 3, build)[0], run_case(fixture, 34, build)[0])
