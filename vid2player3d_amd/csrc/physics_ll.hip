@@ -214,6 +214,18 @@ __device__ __forceinline__ void grp_arg(float& v, int& k) {
     v = g;
 }
 
+// maximum of a non-negative per-lane value over each env's 32 lanes, on the DPP network: four shifts inside the rows of 16 (a lane
+// without a source takes 0), then the last lane of rows 0 and 2 handed to the row behind.  Lane 31 of the result holds the first
+// env's maximum, lane 63 the second's.  All lanes have to be on.
+__device__ __forceinline__ int half_max_last(int v) {
+    int o = __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true); v = o > v ? o : v;
+    o = __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true); v = o > v ? o : v;
+    o = __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true); v = o > v ? o : v;
+    o = __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true); v = o > v ? o : v;
+    o = __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false); v = o > v ? o : v;
+    return v;
+}
+
 #define LLSUBV(k, tv) do { if (DIAG && a.prof) { long long t_ = clock64(); if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t_ - tv)); tv = t_; } } while (0)
 #define LLSUB(k) LLSUBV(k, tsub)
 // the split of the sweep's remainder (counters 20 - 23: closing move, closing pass, head and tail of a visit, set-up) is timed in the
@@ -1301,7 +1313,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             }
             const bool ballhit = BALL && valid && ((racket_lane && (bl[BL_RK + RK_A] != 0.f || bl[BL_RK + 16 + RK_A] != 0.f)) || myhull);
             const bool ballground = BALL && ball_lane && bl[BL_GA] != 0.f;
-            const unsigned long long tb = __ballot(valid && (cnt > 0 || ballhit));
+            const bool touched = valid && (cnt > 0 || ballhit);
+            const unsigned long long tb = __ballot(touched);
             const unsigned m0 = (unsigned)tb, m1 = (unsigned)(tb >> 32);
             if (LIMITS && any64(limact)) {
                 // speculative activation of the limit rows (the model is stated in oracle/phys/v2p_phys_oracle.c): a row exists in this substep
@@ -1326,11 +1339,33 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             const unsigned long long lmb = LIMITS ? __ballot(valid && limact) : 0ull;
             const unsigned lm0 = (unsigned)lmb, lm1 = (unsigned)(lmb >> 32);
             if (DIAG && a.wave_times) { const int tt = __popc(half ? m1 : m0); tsum += tt; tmaxs = tt > tmaxs ? tt : tmaxs; }
+            // SETUPX (the kernels with the visit table, see VTAB below): the depth of each env's deepest touched link is a reduction of the
+            // lanes' own depths on the DPP network, and the visit table is formed by the stops' own lanes (below, where it is built).  The other kernels
+            // walk the touched links with a load of the model's depth table per link, and fill the table stop by stop: with the reduction
+            // alone, nine of the racket + ball, joint-limit and TGS kernels of the default build need 4 - 16 B more scratch per lane and
+            // four of the register build 4 - 8 B (profiles/r21a_kres_*_reduction_in_every_kernel.txt against r21a_kres_*_all_kernels.txt).
+#ifdef V2P_LL_REGS_BUILD
+            constexpr bool SETUPX = !LIMITS && !TGS && !BALL && !DIAG;
+#else
+            constexpr bool SETUPX = !LIMITS && !TGS && !BALL;
+#endif
+            [[maybe_unused]] int tdep0 = 0, tdep1 = 0;
+            if constexpr (SETUPX) {
+                // (half_max_last: all 64 lanes are on here - top level of the substep - and the value is never negative; `touched` keeps
+                // the 99 of the idle lanes out)
+                const int tdred = half_max_last(touched ? dep : 0);
+                tdep0 = __builtin_amdgcn_readlane(tdred, 31);
+                tdep1 = __builtin_amdgcn_readlane(tdred, 63);
+            }
             if (last) {
                 const unsigned mine = half ? m1 : m0;
                 ksum = __popc(mine);
-                kdep = 0;
-                for (unsigned t = mine; t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; kdep = dd > kdep ? dd : kdep; }
+                if constexpr (SETUPX) {
+                    kdep = half ? tdep1 : tdep0;
+                } else {
+                    kdep = 0;
+                    for (unsigned t = mine; t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; kdep = dd > kdep ? dd : kdep; }
+                }
             }
             if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) { atomicAdd((unsigned long long*)&a.prof[9], (unsigned long long)(__popc(m0) + __popc(m1))); atomicAdd((unsigned long long*)&a.prof[10], 1ull); }
             const bool sweep_on = ((m0 | m1 | lm0 | lm1) || (BALL && any64(ballground))) && P.n_iter > 0;
@@ -1340,8 +1375,13 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 // per-update propagation stop there; their velocities catch up once at the end (the propagation is linear)
                 // (each env stops at ITS deepest touched link, so its arithmetic does not depend on which env shares the wave)
                 int dn0 = 0, dn1 = 0;
-                for (unsigned t = m0 | lm0; t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; dn0 = dd > dn0 ? dd : dn0; }
-                for (unsigned t = m1 | lm1; t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; dn1 = dd > dn1 ? dd : dn1; }
+                if constexpr (SETUPX) {
+                    dn0 = tdep0;
+                    dn1 = tdep1;
+                } else {
+                    for (unsigned t = m0 | lm0; t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; dn0 = dd > dn0 ? dd : dn0; }
+                    for (unsigned t = m1 | lm1; t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; dn1 = dd > dn1 ? dd : dn1; }
+                }
                 const int dneed = dn0 > dn1 ? dn0 : dn1, dmin = dn0 < dn1 ? dn0 : dn1;
                 const bool insweep = dep <= (half ? dn1 : dn0);  // this link moves with every update; the others catch up afterwards
                 LLPH(4);
@@ -1449,11 +1489,11 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     park_put3(PARK_XD0, xd);
                 }
                 // touched links whose parent is the touched link right before them (ascending).  Nothing reads these masks any more (the
-                // per-group sweep that did is gone), but without this loop the compiler lowers the control flow of the sweep differently:
-                // 0.5 % slower in an A/B then; measured again on top of the way up without fills and copies (docs/NOTES.md B, 2026-10-19):
-                // 21.24 / 21.29 / 21.27 M env-steps/s without it against 21.50 / 21.52 / 21.49 with it (-1.1 %).  It stays.
-                [[maybe_unused]] unsigned chain0 = 0u, chain1 = 0u;
-                {
+                // per-group sweep that did is gone), but without this loop the compiler lowered the control flow of the sweep differently
+                // (-0.5 %, later -1.1 %: docs/NOTES.md B, 2026-10-19).  With the set-up of SETUPX in front of the sweep that no longer
+                // holds (measured again, same section): those kernels go without it; the others keep the loop and stay as they were.
+                if constexpr (!SETUPX) {
+                    [[maybe_unused]] unsigned chain0 = 0u, chain1 = 0u;
                     int prev = -1;
                     for (unsigned t = m0; t; t &= t - 1) {
                         const int nn = __ffs(t) - 1;
@@ -1522,6 +1562,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 // halves of the change ballot as two scalars.  As two bools (the earlier form, which the other kernels keep with their visits)
                 // the compiler holds `live` in two lane masks, and every visit turns them into a scalar through a VGPR again
                 // (docs/NOTES.md B, 2026-10-19, the way down and the rest of the sweep).
+                static_assert(VTAB == SETUPX, "the set-up in front of the sweep and the table go together");
                 constexpr bool LIVEM = VTAB;
                 // ROWX: the rows of a visit's stops, point by point, without selects and without a dispatch between the points: a point's
                 // three rows run as a divergent region of the lanes whose point is active.  ROWCNT (with the visit table): whether point c
@@ -1539,14 +1580,48 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 [[maybe_unused]] int vis = 0, mystop = -1, nvis0 = 0, nvis1 = 0;
                 [[maybe_unused]] int livem = 0;  // LIVEM: bit h = env h is live (wave-uniform, in a scalar register)
                 [[maybe_unused]] unsigned anc = 0u;
-                {
-                    int p0 = v0 ? 31 - __clz(v0) : 0, p1 = v1 ? 31 - __clz(v1) : 0;
-                    if constexpr (VTAB) {
-                        nvis0 = __popc(v0);
-                        nvis1 = __popc(v1);
+                // The table (VTAB) is formed by the STOPS' OWN LANES, all at once, instead of stop by stop for the wave: a stop's lane knows
+                // its number (the stops below it in its env's mask), the stop before it (cyclically), its own depth and number of points;
+                // the depths of the stop before and of their lowest common ancestor are counts of the model's ancestor masks (what the
+                // three ballots per stop of the earlier form counted), read with the side levels in loads under one wait.  The word goes
+                // to lane k of the env through the wave's scratch row in LDS (free outside contact generation).  What is left of the loop
+                // over the stops is the bit of `anc`: the ancestor mask of the env's k-th stop, read from the stop's lane, IS the lane
+                // mask of bit k + 1 - both envs' masks side by side are one 64-bit lane mask, one select and one OR per stop.
+                if constexpr (VTAB) {
+                    const unsigned mine = half ? v1 : v0;
+                    nvis0 = __popc(v0);
+                    nvis1 = __popc(v1);
+                    const int nmine = half ? nvis1 : nvis0;
+                    const unsigned below = mine & ((1u << lb) - 1u);
+                    const int kme = __popc(below);
+                    const int plast0 = v0 ? 31 - __clz(v0) : 0, plast1 = v1 ? 31 - __clz(v1) : 0;
+                    const unsigned ancme = valid ? (unsigned)M.anc_mask[bo] : 0u;  // (bit i: link i is an ancestor of this lane's link, or the link itself)
+                    int* const vrow = (int*)(park + PARK_SCR * 64);  // this lane's word of the scratch row
+                    if (valid && ((mine >> lb) & 1u)) {
+                        const int pv = below ? 31 - __clz(below) : (half ? plast1 : plast0);
+                        const unsigned ancp = (unsigned)M.anc_mask[pv];
+                        const int sdp = M.side_depths[pv];
+                        const int du = __popc(ancp) - 1, dl = __popc(ancp & ancme) - 1;
+                        // (levels of the way up where the path link is not its parent's first child: it hands over through a pull, see walk_to)
+                        const int sd = sdp & ~((2 << dl) - 1);
+                        // (bits 25 - 27, ROWCNT: the stop's number of points)
+                        vrow[kme - lb] = dl | (du << 4) | (dep << 8) | ((sd & 0xfff) << 12) | (nmine > 1 ? 1 << 24 : 0) | (ROWCNT ? cnt << 25 : 0);
+                        mystop = kme;
                     }
-                    int k = 0;
+                    vis = lb < nmine ? vrow[0] : 0;
+                    auto lanes_of = [&](unsigned lo, unsigned hi) -> bool { return __builtin_amdgcn_inverse_ballot_w64(((unsigned long long)hi << 32) | lo); };
+                    // (bit 0: the env's last stop; an env without stops: link 0, as before)
+                    anc = lanes_of(__builtin_amdgcn_readlane(ancme, plast0), __builtin_amdgcn_readlane(ancme, 32 + plast1)) ? 1u : 0u;
+                    // (an env that has run out of stops reads lane 31 of its half: no link, an empty mask)
+                    int k = 1;
                     for (unsigned s0 = v0, s1 = v1; s0 | s1; s0 &= s0 - 1, s1 &= s1 - 1, ++k) {
+                        const unsigned a0 = __builtin_amdgcn_readlane(ancme, __ffs(s0 | 0x80000000u) - 1);
+                        const unsigned a1 = __builtin_amdgcn_readlane(ancme, 32 + __ffs(s1 | 0x80000000u) - 1);
+                        anc |= lanes_of(a0, a1) ? 1u << k : 0u;
+                    }
+                } else {
+                    int p0 = v0 ? 31 - __clz(v0) : 0, p1 = v1 ? 31 - __clz(v1) : 0;
+                    for (unsigned s0 = v0, s1 = v1; s0 | s1; s0 &= s0 - 1, s1 &= s1 - 1) {
                         const int b0 = s0 ? __ffs(s0) - 1 : p0, b1 = s1 ? __ffs(s1) - 1 : p1;
                         const int selp = half ? p1 : p0, selb = half ? b1 : b0;
                         const bool ap = valid && ((desc >> selp) & 1), ab = valid && ((desc >> selb) & 1);
@@ -1556,18 +1631,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         // (levels of the way up where the path link is not its parent's first child: it hands over through a pull, see walk_to)
                         const int sd = (half ? M.side_depths[p1] : M.side_depths[p0]) & ~((2 << dl) - 1);
                         // (bit 28: the link itself is not its parent's first child - the one-joint bounce of a limit block needs it)
-                        if constexpr (VTAB) {
-                            const bool has = (half ? s1 : s0) != 0u;
-                            // (bits 25 - 27, ROWCNT: the stop's number of points)
-                            int np = 0;
-                            if constexpr (ROWCNT) { const int c0 = __builtin_amdgcn_readlane(cnt, b0), c1 = __builtin_amdgcn_readlane(cnt, 32 + b1); np = (half ? c1 : c0) << 25; }
-                            if (has && lb == k) vis = dl | (du << 4) | (dn << 8) | ((sd & 0xfff) << 12) | ((half ? nvis1 : nvis0) > 1 ? 1 << 24 : 0) | np;
-                            if (has && valid && lb == selb) mystop = k;
-                            if (has && ab) anc |= 2u << k;
-                            if (k == 0 && ap) anc |= 1u;
-                        } else {
-                            if (valid && lb == selb && ((half ? s1 : s0) != 0u)) minfo = dl | (du << 4) | (dn << 8) | (sd << 12) | ((LIMITS && !firstchild) ? 1 << 28 : 0);
-                        }
+                        if (valid && lb == selb && ((half ? s1 : s0) != 0u)) minfo = dl | (du << 4) | (dn << 8) | (sd << 12) | ((LIMITS && !firstchild) ? 1 << 28 : 0);
                         p0 = b0;
                         p1 = b1;
                     }
