@@ -163,7 +163,7 @@ static int alloc_env(v2p_env* e, const v2p_model* const* shapes, const int32_t* 
     }
     // (one record per wave; per JOB in a V2P_LL_TIMELINE build: up to nsub per wave)
     if (rc == V2P_OK && debug_env("V2P_WAVE_TIMES")) rc = own.alloc(&e->wave_times, 4 * (N / 2 + 1) * nsub, "wave_times", Z);
-    if (rc == V2P_OK && debug_env("V2P_PHASE_TIMING")) rc = own.alloc(&e->prof, (size_t)24, "prof", Z);
+    if (rc == V2P_OK && debug_env("V2P_PHASE_TIMING")) rc = own.alloc(&e->prof, (size_t)PROF_COUNT, "prof", Z);
     return rc;
 }
 
@@ -241,7 +241,7 @@ void v2p_env_destroy(v2p_env* e) {
         if (f) fclose(f);
     }
     if (e->prof) {
-        long long h[24];
+        long long h[PROF_COUNT];
         if (hipMemcpy(h, e->prof, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr,
                     "[v2p phase cycles, workgroup 0] link-per-lane: counter k = phase k-1 of {pass1, pass2, root+pass3, contacts, lambda, sweep, "
@@ -251,7 +251,9 @@ void v2p_env_destroy(v2p_env* e) {
                     "sweep, the rest: close-up %lld close-pass %lld visit-head-tail %lld set-up %lld "
                     "(where these four are counted - the default build - `up` is without the closing move, `down` without the closing pass and `rows` "
                     "without the tail of a visit: not comparable with logs that lack them)\n",
-                    h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15], h[16], h[17], h[18], h[19], h[20], h[21], h[22], h[23]);
+                    h[PROF_HEAD], h[PROF_PASS1], h[PROF_PASS2], h[PROF_PASS3], h[PROF_CONTACTS], h[PROF_LAMBDA], h[PROF_SWEEP], h[PROF_INTEGRATE],
+                    h[PROF_UPDATES], h[PROF_TOUCHED], h[PROF_SUBSTEPS], h[PROF_ROWS], h[PROF_UP], h[PROF_ROUNDS], h[PROF_DOWN], h[PROF_MANIFOLDS],
+                    h[PROF_CULL], h[PROF_SCAN], h[PROF_POINTS], h[PROF_NULL_UPDATES], h[PROF_CLOSE_MOVE], h[PROF_CLOSE_PASS], h[PROF_VISIT_ENDS], h[PROF_SWEEP_SETUP]);
     }
     delete e;
 }

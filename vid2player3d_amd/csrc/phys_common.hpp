@@ -60,6 +60,34 @@ struct PostArgs {
     int32_t on;   // 1: the job of an env's last substep also runs its post-physics (obs, reward, reset flags, next target)
 };
 
+// The cycle counters of PhysArgs::prof (V2P_PHASE_TIMING; the batch allocates PROF_COUNT of them and prints them by name when it is
+// destroyed, env.hip).  HEAD .. INTEGRATE: cycles per phase of a substep (HEAD: what lies in front of pass 1 - the env-per-lane kernel's
+// staging, the link-per-lane kernel's loop head); the rest split contact generation and the sweep, or count events.  The env-per-lane
+// kernel (physics.hip) fills HEAD .. DOWN only.
+enum Prof : int {
+    PROF_HEAD = 0, PROF_PASS1, PROF_PASS2, PROF_PASS3, PROF_CONTACTS, PROF_LAMBDA, PROF_SWEEP, PROF_INTEGRATE,
+    PROF_UPDATES,       // count: block updates (visits of the sweep)
+    PROF_TOUCHED,       // count: touched links, summed over the substeps
+    PROF_SUBSTEPS,      // count: substeps
+    PROF_ROWS,          // sweep: the rows of a visit
+    PROF_UP,            // sweep: the way up of a move
+    PROF_ROUNDS,        // count: rounds of contact generation (env-per-lane: cycles of the root's response)
+    PROF_DOWN,          // sweep: the way down of a move
+    PROF_MANIFOLDS,     // count: manifold reductions
+    PROF_CULL,          // contact generation: the box test
+    PROF_SCAN,          // contact generation: the rounds
+    PROF_POINTS,        // contact generation: the points' records
+    PROF_NULL_UPDATES,  // count: block updates that changed nothing
+    // the sweep's remainder, timed where LlForms::DIAGX says so (there UP is without the closing move, DOWN without the closing pass
+    // and ROWS without the tail of a visit)
+    PROF_CLOSE_MOVE,    // the closing move: its descriptor, the way up to the root, the turn there
+    PROF_CLOSE_PASS,    // the root -> leaves pass of a closing walk
+    PROF_VISIT_ENDS,    // head and tail of a visit: what neither the move nor the rows time
+    PROF_SWEEP_SETUP,   // the sweep's set-up since the end of the Lambda phase: moves, visit table
+    PROF_COUNT
+};
+static_assert(PROF_COUNT == 24, "the counters' numbers are what logs under profiles/ are read by");
+
 struct PhysArgs {
     const DevModel* __restrict__ model;
     float* __restrict__ state;

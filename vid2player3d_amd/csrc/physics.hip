@@ -142,7 +142,7 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
             const int cb = CT_PD + 3 * (b - 1);
             SG(b, 11) = f4(a.ctrl[CIDX(cb + 0)], a.ctrl[CIDX(cb + 1)], a.ctrl[CIDX(cb + 2)], 0.f);
         }
-        PHASE(0);
+        PHASE(PROF_HEAD);
         // ================================================================ pass 1: root -> leaves
         for (int b = 0; b < NB; ++b) {
             const int par = M.parents[b];
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
             SG(b, 12) = f4(0.f, 0.f, m, 0.f);
         }
 
-        PHASE(1);
+        PHASE(PROF_PASS1);
         // ================================================================ pass 2: leaves -> root
         for (int b = NB - 1; b >= 1; --b) {
             const int par = M.parents[b];
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
             SG(par, 8) = p0; SG(par, 9) = p1; SG(par, 10) = p2; SG(par, 11) = p3; SG(par, 12) = p4; SG(par, 1) = pg1; SG(par, 3) = pg3; SG(par, 4) = pg4;
         }
 
-        PHASE(2);
+        PHASE(PROF_PASS2);
         // ================================================================ root: 6x6 solve
         Blocks Lsave[MAX_BRANCH];  // Lambda of the branching links (root, chest): children that do not follow their parent read it here
         {
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
             SG(b, 7) = f4(dv.y, dv.z, 0.f, 0.f);
         }
 
-        PHASE(3);
+        PHASE(PROF_PASS3);
         if (CONTACT) {
             // ============================================================ contact generation
             const float coff = P.contact_offset;
@@ -462,7 +462,7 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
                 G(b, GCN) = (float)cnt;
             }
 
-            PHASE(4);
+            PHASE(PROF_CONTACTS);
             // ============================================================ Lambda_b recursion (root -> leaves)
             {
                 Blocks Lprev = Lsave[0];
@@ -555,16 +555,16 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
                 }
             }
 
-            PHASE(5);
+            PHASE(PROF_LAMBDA);
             // ============================================================ block Gauss-Seidel over the touched bodies
-            if (a.prof && blockIdx.x == 0 && lane == 0) { atomicAdd((unsigned long long*)&a.prof[9], (unsigned long long)__popc(touch)); atomicAdd((unsigned long long*)&a.prof[10], 1ull); }
+            if (a.prof && blockIdx.x == 0 && lane == 0) { atomicAdd((unsigned long long*)&a.prof[PROF_TOUCHED], (unsigned long long)__popc(touch)); atomicAdd((unsigned long long*)&a.prof[PROF_SUBSTEPS], 1ull); }
             if (touch && P.n_iter > 0) {
                 for (int it = 0; it < P.n_iter; ++it) {
                     unsigned todo = touch;
                     while (todo) {
                         const int b = __ffs(todo) - 1;
                         todo &= todo - 1;
-                        if (a.prof && blockIdx.x == 0 && lane == 0) atomicAdd((unsigned long long*)&a.prof[8], 1ull);
+                        if (a.prof && blockIdx.x == 0 && lane == 0) atomicAdd((unsigned long long*)&a.prof[PROF_UPDATES], 1ull);
                         const BodyContacts cur0 = load_body(ws, N, e, b);
                         BodyContacts cur = cur0;
                         long long tsub = a.prof ? clock64() : 0;
@@ -599,7 +599,7 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
                             cur.lam[c] = V3{ln, l1, l2};
                             G(b, GCL + 3 * c) = ln; G(b, GCL + 3 * c + 1) = l1; G(b, GCL + 3 * c + 2) = l2;
                         }
-                        SUBPH(11);
+                        SUBPH(PROF_ROWS);
                         // ---- propagate the net impulse (phin, phif) applied at link b: leaf -> root
                         V3 nI = phin, fI = phif;
                         unsigned path = 0;
@@ -617,7 +617,7 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
                             i = par;
                             rec = prec;
                         }
-                        SUBPH(12);
+                        SUBPH(PROF_UP);
                         // root response
                         {
                             const Blocks& L0 = Lsave[0];
@@ -628,7 +628,7 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
                             SG(0, 3) = f4(g3.x + dv.y, g3.y + dv.z, dw.x, dw.y);
                             SG(0, 4) = f4(dw.z, dv.x, dv.y, dv.z);
                         }
-                        SUBPH(13);
+                        SUBPH(PROF_ROUNDS);  // (this kernel's own use of the slot: the root's response)
                         // root -> leaves in level order: every link moves; the next link's record is prefetched
                         {
                             int i = unpack5(a.ord_pack, 1);
@@ -652,13 +652,13 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
                                 i = inext; fr = nr; g2 = ng2; g3 = ng3;
                             }
                         }
-                        SUBPH(14);
+                        SUBPH(PROF_DOWN);
                     }
                 }
             }
         }
 
-        PHASE(6);
+        PHASE(PROF_SWEEP);
         // ================================================================ velocities -> generalized, damping, clamp, integrate
         const float sc = 1.f / (1.f + h * P.ang_damp);
         const float wmax = P.max_ang_vel;
@@ -712,7 +712,7 @@ __global__ __launch_bounds__(L) void physics_kernel(PhysArgs a) {
         }
     }
 
-    PHASE(7);
+    PHASE(PROF_INTEGRATE);
     // ==================================================================== final kinematics -> state, rigid-body state, dof_pos
     for (int b = 0; b < NB; ++b) {
         const int par = M.parents[b];

@@ -31,6 +31,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 // This translation unit is compiled with -fassociative-math -freciprocal-math -fno-signed-zeros -fno-trapping-math -fno-honor-nans
 // (build.py) and NOT with -ffast-math: reassociation and NaN-free selects for the code of this file, but the device libraries it
 // links and the way the HIP headers map sinf / cosf / atan2f stay the precise ones (-ffast-math, or the full set of its component
@@ -52,6 +54,7 @@
 #endif
 #include "phys_common.hpp"
 #include "hull_gjk.hpp"
+#include "ll_forms.hpp"
 
 // This file is compiled TWICE into libv2p_rollout.so (build.py): the default object (V2P_LL_WPS* = 3, V2P_LL_PARK2 / 3 = 1: 168 VGPRs,
 // three waves per SIMD, contact records and phase-dead values parked in LDS) and, with -DV2P_LL_REGS_BUILD and the knobs set to
@@ -61,9 +64,11 @@
 #if defined(V2P_LL_REGS_BUILD)
 #define V2P_LL_NS ll_regs
 #define V2P_LL_LAUNCHER launch_env_physics_ll_regs
+#define V2P_LL_BUILD LlBuild::Regs
 #else
 #define V2P_LL_NS ll_lds
 #define V2P_LL_LAUNCHER launch_env_physics_ll
+#define V2P_LL_BUILD LlBuild::Lds
 #endif
 
 namespace v2p {
@@ -226,20 +231,22 @@ __device__ __forceinline__ int half_max_last(int v) {
     return v;
 }
 
-#define LLSUBV(k, tv) do { if (DIAG && a.prof) { long long t_ = clock64(); if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t_ - tv)); tv = t_; } } while (0)
+// The probes of the diagnostic instantiation (counters: enum Prof, phys_common.hpp).  They read the kernel's `a`, `lane` and `F` (the
+// form policy, ll_forms.hpp) where they stand.
+// which lane of the launch samples: lane 0 of every 64th workgroup, or (V2P_PHASE_HEAVY) of the first 8 - the heaviest env pairs
+#define LLSAMPLED (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0)
+// add v to counter k.  LLADD: the caller has tested DIAG && a.prof; LLCOUNT tests them itself.  (Plain `if` statements, to be used as
+// statements of their own, not do { } while (0) blocks: the wrapper's empty blocks, in kernels where the probe compiles to nothing,
+// moved the block numbers of the rows' dispatch in the register build's kernels and their code with them: docs/NOTES.md L)
+#define LLADD(k, v) if (LLSAMPLED) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(v))
+#define LLCOUNT(k, v) if (DIAG && a.prof && LLSAMPLED) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(v))
+// the cycles since the stamp tv into counter k, and tv moves on
+#define LLSUBV(k, tv) do { if (DIAG && a.prof) { long long t_ = clock64(); LLADD(k, t_ - tv); tv = t_; } } while (0)
 #define LLSUB(k) LLSUBV(k, tsub)
-// the split of the sweep's remainder (counters 20 - 23: closing move, closing pass, head and tail of a visit, set-up) is timed in the
-// default build's diagnostic kernel only: in the register build's it costs 12 B of scratch per lane
-#ifdef V2P_LL_REGS_BUILD
-#define LLSUBX(k, tv) do { } while (0)
-#define LLSUBX_OR(k, kparent) LLSUB(kparent)  // (where the parent timed the same stretch into another counter: as the parent)
-#define V2P_LL_DIAGX false
-#else
-#define LLSUBX(k, tv) LLSUBV(k, tv)
-#define LLSUBX_OR(k, kparent) LLSUB(k)
-#define V2P_LL_DIAGX DIAG
-#endif
-#define LLPH(k) do { if (DIAG && a.prof) { long long t_ = clock64(); if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t_ - tprev)); tprev = t_; } } while (0)
+// the split of the sweep's remainder (F::DIAGX): timed where the policy says so, else nothing
+#define LLSUBX(k, tv) do { if constexpr (F::DIAGX) LLSUBV(k, tv); } while (0)
+#define LLSUBX_OR(k, kparent) LLSUB(F::DIAGX ? (k) : (kparent))  // (where the parent timed the same stretch into another counter: as the parent)
+#define LLPH(k) LLSUBV(k, tprev)
 
 // Everything from here to the end of the kernel depends on the build (register budget, what is parked in LDS and with it the LDS
 // layout): it lives in a namespace of its own per build, which also keeps the two objects' kernels (and their host stubs) apart for
@@ -256,6 +263,7 @@ inline namespace V2P_LL_NS {
 #define V2P_LL_WPS_LIMITS 3   // ... of the joint-limit instantiations without a ball
 #endif
 constexpr int LL_WPB = V2P_LL_WPB;
+constexpr LlBuild LL_BUILD = V2P_LL_BUILD;  // which of the two objects this is: the one place the macro is read for the form policy (ll_forms.hpp)
 // V2P_LL_PARK2: phase-scoped parking of values that a phase does not touch (link velocities during pass 2 / contact generation / the
 // Lambda recursion, Lambda of the root during contact generation, the contact records during the Lambda recursion): lowers the
 // register peak of those phases so that nothing long-lived is spilled ACROSS the sweep loops when the kernel is built for 3 waves/SIMD.
@@ -284,7 +292,28 @@ constexpr int ROOTLAM_FLOATS = 2 * 24;  // (PARK2) Lambda of the two root links 
 // at the start of the substep, a large value when the row does not bounce: it caps the bias of every slice)
 constexpr int BL_POS = 0, BL_QUAT = 3, BL_VEL = 7, BL_ANG = 10, BL_F = 13, BL_GA = 16, BL_GGAP = 17, BL_GBIAS = 18, BL_GLAM = 19, BL_GREST = 22, BL_RK = 24,
               RK_A = 0, RK_GAP = 1, RK_BIAS = 2, RK_RL = 3, RK_N = 6, RK_LAM = 9, RK_LINK = 12, RK_REST = 13, NBREC = 5, BL_V0 = BL_RK + 16 * NBREC, BL_SLOTS = BL_V0 + 8;
-constexpr int LDS_FLOATS_PER_WAVE = PARK_SLOTS * 64 + 2 * BL_SLOTS + ROOTLAM_FLOATS;
+// The LDS block of a wave (`wave_lds` in the kernel), in floats - the one statement of its layout:
+//   LDS_PARK     [PARK_SLOTS][64]   the parking slots: slot k of lane l at k * 64 + l (PARK_* above).  The last slot, PARK_SCR, is the
+//                                   wave's scratch row (lane of the k-th near link during contact generation, the visit words of the
+//                                   sweep's set-up).  In the PARK_TAR slots the columns of an env's lanes WRENCH_FORCE_LANE and
+//                                   WRENCH_TORQUE_LANE hold the residual wrench of the fused step (neither lane has a joint target).
+//   LDS_BALL     [2][BL_SLOTS]      the ball block of each env (BL_* above)
+//   LDS_ROOTLAM  [2][ROOTLAM_ROW]   (PARK2) Lambda of each env's root while the contacts are generated
+// and, once the substeps are over and the parking slots are idle, two overlays on LDS_PARK:
+//   LDS_STAGE    [2][STAGE_FLOATS]  the rigid-body rows [24][13] of each env on their way to the caller's tensor
+//   slots 0 .. REWARD_SLOTS - 1     the reward terms of the fused post-physics, a slot per term (the rows have left by then)
+constexpr int ROOTLAM_ROW = ROOTLAM_FLOATS / 2, STAGE_FLOATS = NB * 13, REWARD_SLOTS = 4;
+constexpr int WRENCH_FORCE_LANE = 0, WRENCH_TORQUE_LANE = 25;  // (lanes of the env)
+constexpr int LDS_PARK = 0, LDS_STAGE = LDS_PARK, LDS_BALL = LDS_PARK + PARK_SLOTS * 64, LDS_ROOTLAM = LDS_BALL + 2 * BL_SLOTS;
+constexpr int LDS_FLOATS_PER_WAVE = LDS_ROOTLAM + ROOTLAM_FLOATS;
+static_assert(LDS_STAGE + 2 * STAGE_FLOATS <= LDS_BALL && REWARD_SLOTS <= PARK_SLOTS, "an overlay does not fit the parking slots");
+static_assert(WRENCH_TORQUE_LANE > NB && WRENCH_TORQUE_LANE < LPE, "the torque's lane must be one without a link (and not the ball's)");
+// the residual wrench's home: envcol = wave_lds + the env's first lane, l = WRENCH_FORCE_LANE / WRENCH_TORQUE_LANE
+__device__ __forceinline__ void wrench_put(float* envcol, int l, float x, float y, float z) {
+    envcol[l + PARK_TAR * 64] = x; envcol[l + (PARK_TAR + 1) * 64] = y; envcol[l + (PARK_TAR + 2) * 64] = z;
+}
+__device__ __forceinline__ float wrench_at(const float* envcol, int l, int k) { return envcol[l + (PARK_TAR + k) * 64]; }  // component k
+__device__ __forceinline__ V3 wrench_get(const float* envcol, int l) { return V3{wrench_at(envcol, l, 0), wrench_at(envcol, l, 1), wrench_at(envcol, l, 2)}; }
 // ball x hull narrow phase, out of line: it runs on the few substeps in which a ball is within reach of a link, and inlined its
 // registers would be spilled around on every substep
 // (the closest point comes back BY VALUE, xyz = point, w = distance: an out-parameter by reference is a stack slot of the caller that the
@@ -358,8 +387,8 @@ __device__ __forceinline__ void vfric_frame(const V3& w0, const V3& xd0, const V
 // cost the third wave per SIMD.  An instantiation of its own: with general tangent directions the rows lose the zeros the world frame
 // gives them (~+40 % instructions in the friction rows), which the default kernel must not pay.
 template <bool CONTACT, bool MULTI, bool TGS, bool DIAG, bool BALL, bool JOBS, bool LIMITS, bool VFRIC = false>
-__global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (LIMITS ? V2P_LL_WPS_LIMITS : V2P_LL_WPS))) void physics_ll_kernel(PhysArgs a) {
-    constexpr bool OPAQUE_H = BALL || LIMITS;  // (the headline instantiation keeps its 0 - 12 B of scratch either way: measured no difference, profiles/r06d_variants_spill.log)
+__global__ __launch_bounds__(64 * LL_WPB, (LlForms<LL_BUILD, TGS, DIAG, BALL, LIMITS>::waves_per_simd(V2P_LL_WPS, V2P_LL_WPS_BALL, V2P_LL_WPS_LIMITS))) void physics_ll_kernel(PhysArgs a) {
+    using F = LlForms<LL_BUILD, TGS, DIAG, BALL, LIMITS>;  // which form of each switched phase this instantiation runs (ll_forms.hpp)
     const int64_t N = a.n;
     const int lane = threadIdx.x & 63;
     const int half = lane >> 5;
@@ -488,12 +517,13 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     // the velocities at the start of the sweep).  Holding them in registers made the allocator spill them (or something else) to
     // scratch - private memory that ends up as HBM write traffic; 9 dwords x 64 lanes of LDS per wave cost nothing.
     extern __shared__ float park_all[];
-    float* const park = park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + lane;  // slot k of this lane: park[k * 64]
+    float* const wave_lds = park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE;  // this wave's block (the map: LDS_FLOATS_PER_WAVE)
+    float* const park = wave_lds + LDS_PARK + lane;  // slot k of this lane: park[k * 64]
     // this env's ball block.  The pointer carries the LDS address space in its TYPE: the accesses are volatile (the ball lane writes what
     // link lanes read within the wave), and address-space inference leaves volatile accesses alone - as a plain `volatile float*` every
     // bl[k] was a FLAT load / store through its own 64-bit address, ~50 loop-invariant pointers that were kept (spilled: 400 B of
     // scratch per lane) across the substep loop
-    lds_vfloat* const bl = (lds_vfloat*)(park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + PARK_SLOTS * 64 + half * BL_SLOTS);
+    lds_vfloat* const bl = (lds_vfloat*)(wave_lds + LDS_BALL + half * BL_SLOTS);
     auto park_put3 = [&](int slot, V3 v) { park[slot * 64] = v.x; park[(slot + 1) * 64] = v.y; park[(slot + 2) * 64] = v.z; };
     auto park_get3 = [&](int slot) -> V3 { return V3{park[slot * 64], park[(slot + 1) * 64], park[(slot + 2) * 64]}; };
     // (PARK2) the link velocities leave the registers for the phases that do not touch them; the W0 / XD0 slots are free outside the sweep
@@ -595,22 +625,21 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     bool bgot = false;  // (BALL) the ball lane has its state from the hand-over
     if constexpr (JOBS) if (handed) {
         f4 c0, c1;
-        cload4x2(hand + 8 * b, hand + 8 * b + 4, c0, c1);
+        cload4x2(hand + 4 * hand_link(b), hand + 4 * (hand_link(b) + 1), c0, c1);
         if (b == 0) {
             f4 c2, c3;
-            cload4x2(hand + 4 * 48, hand + 4 * 49, c2, c3);
+            cload4x2(hand + 4 * HAND_ROOT_VEL, hand + 4 * (HAND_ROOT_VEL + 1), c2, c3);
             q = Q4{c0.x, c0.y, c0.z, c0.w};
             x = V3{c1.x, c1.y, c1.z};
             xd = V3{c1.w, c2.x, c2.y};
             w = V3{c2.z, c2.w, c3.x};
             if (a.actions && valid && jstart(sjob) < a.p.hold_sub) {
                 // the residual wrench of the fused step travels with the root's chunks while a later job still needs it (it is held for the
-                // first hold_sub substeps only): force behind w.z, torque in chunk 54
+                // first hold_sub substeps only): force behind w.z, torque in its own chunk
                 f4 c4, c5;
-                cload4x2(hand + 4 * 54, hand + 4 * 54, c4, c5);
-                float* const wp = park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + base;
-                wp[PARK_TAR * 64] = c3.y; wp[(PARK_TAR + 1) * 64] = c3.z; wp[(PARK_TAR + 2) * 64] = c3.w;
-                wp[25 + PARK_TAR * 64] = c4.x; wp[25 + (PARK_TAR + 1) * 64] = c4.y; wp[25 + (PARK_TAR + 2) * 64] = c4.z;
+                cload4x2(hand + 4 * HAND_TORQUE, hand + 4 * HAND_TORQUE, c4, c5);
+                wrench_put(wave_lds + base, WRENCH_FORCE_LANE, c3[HAND_FORCE_AT], c3[HAND_FORCE_AT + 1], c3[HAND_FORCE_AT + 2]);
+                wrench_put(wave_lds + base, WRENCH_TORQUE_LANE, c4.x, c4.y, c4.z);
             }
         } else {
             jq = Q4{c0.x, c0.y, c0.z, c0.w};
@@ -633,9 +662,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         }
         if (!a.actions) tar = V3{ldin(&a.ctrl[CIDX(cb + 0)]), ldin(&a.ctrl[CIDX(cb + 1)]), ldin(&a.ctrl[CIDX(cb + 2)])};
     }
-    // the residual root wrench of the fused step: lanes 0 (force) and 25 (torque) of the env keep it in the PARK_TAR slots of their LDS columns
-    // (neither has a joint target)
-    float* const wrench_park = park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + base;
+    // the residual root wrench of the fused step: lanes WRENCH_FORCE_LANE and WRENCH_TORQUE_LANE of the env keep it in the PARK_TAR slots of
+    // their LDS columns (neither has a joint target)
+    float* const wrench_park = wave_lds + base;
     if (pre_on) {
         // ---- pre-physics fused in (same functions, same rounding as env_pre_kernel below): lane b owns the three action components of
         // its joint, the root lane the residual wrench; dead envs are masked in place on the caller's tensor.  EVERY job of the env derives
@@ -670,15 +699,15 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             }
             if (need_wrench) {  // (a job past the substeps that hold the wrench has no use for it; a later job is handed it)
                 const float* rq4 = a.x_rb + e * NB * 13 + 3;
-                strict::V3 F, Tq;
-                strict::residual_wrench2(rq4, af, P.res_force_scale, P.res_torque_scale, F, Tq);
-                wrench_park[PARK_TAR * 64] = F.x; wrench_park[(PARK_TAR + 1) * 64] = F.y; wrench_park[(PARK_TAR + 2) * 64] = F.z;
-                wrench_park[25 + PARK_TAR * 64] = Tq.x; wrench_park[25 + (PARK_TAR + 1) * 64] = Tq.y; wrench_park[25 + (PARK_TAR + 2) * 64] = Tq.z;
+                strict::V3 Fr, Tq;  // (not `F`: that is the form policy in this function)
+                strict::residual_wrench2(rq4, af, P.res_force_scale, P.res_torque_scale, Fr, Tq);
+                wrench_put(wrench_park, WRENCH_FORCE_LANE, Fr.x, Fr.y, Fr.z);
+                wrench_put(wrench_park, WRENCH_TORQUE_LANE, Tq.x, Tq.y, Tq.z);
             }
         }
     }
 
-    if (valid && b != 0) park_put3(PARK_TAR, tar);  // constant for the whole launch (the columns of lanes 0 and 25 hold the wrench there)
+    if (valid && b != 0) park_put3(PARK_TAR, tar);  // constant for the whole launch (the columns of the two wrench lanes hold the wrench there)
     const BallDev& BP = a.ball;
     // this env's racket, through its shape (BALL only).  (MULTI: the address is formed where it is used, from sid - live anyway - instead
     // of being kept in a register pair across the substep loop: that pair cost the per-env-shape ball kernels 16 B of scratch per lane)
@@ -690,23 +719,26 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     const bool racket_lane = BALL && lb == racket()->racket_link;  // this lane's link carries the env's racket
     const bool ball_lane = BALL && lb == NB;  // the first idle lane of the env carries the ball
     if (ball_lane) {
-        // (JOBS: state and aerodynamic force - held over a simulate() call - come from the job of the substep before: chunks 50 .. 53)
+        // (JOBS: state and aerodynamic force - held over a simulate() call - come from the job of the substep before: the ball's chunks,
+        // BL_POS .. BL_F + 2 of the block)
+        static_assert(BL_POS == 0 && BL_QUAT == 3 && BL_VEL == 7 && BL_ANG == 10 && BL_F == 13 && BL_GA == 4 * HAND_BALL_CHUNKS, "what is handed over of the ball: state 13 | aerodynamic force 3");
         if constexpr (JOBS) if (handed) {
             f4 c0, c1, c2, c3;
-            cload4x2(hand + 4 * 50, hand + 4 * 51, c0, c1);
-            cload4x2(hand + 4 * 52, hand + 4 * 53, c2, c3);
-            bl[0] = c0.x; bl[1] = c0.y; bl[2] = c0.z; bl[3] = c0.w; bl[4] = c1.x; bl[5] = c1.y; bl[6] = c1.z; bl[7] = c1.w;
-            bl[8] = c2.x; bl[9] = c2.y; bl[10] = c2.z; bl[11] = c2.w; bl[12] = c3.x; bl[13] = c3.y; bl[14] = c3.z; bl[15] = c3.w;
+            cload4x2(hand + 4 * HAND_BALL, hand + 4 * (HAND_BALL + 1), c0, c1);
+            cload4x2(hand + 4 * (HAND_BALL + 2), hand + 4 * (HAND_BALL + 3), c2, c3);
+            // (written out, not a loop over the chunks: see the note at the storing side)
+            bl[BL_POS] = c0.x; bl[BL_POS + 1] = c0.y; bl[BL_POS + 2] = c0.z; bl[BL_QUAT] = c0.w; bl[BL_QUAT + 1] = c1.x; bl[BL_QUAT + 2] = c1.y; bl[BL_QUAT + 3] = c1.z; bl[BL_VEL] = c1.w;
+            bl[BL_VEL + 1] = c2.x; bl[BL_VEL + 2] = c2.y; bl[BL_ANG] = c2.z; bl[BL_ANG + 1] = c2.w; bl[BL_ANG + 2] = c3.x; bl[BL_F] = c3.y; bl[BL_F + 1] = c3.z; bl[BL_F + 2] = c3.w;
             bgot = true;
         }
         if (!bgot) {
 #pragma unroll
-            for (int k = 0; k < 13; ++k) bl[k] = BP.state[e * 13 + k];
+            for (int k = BL_POS; k < BL_F; ++k) bl[k] = BP.state[e * 13 + k];
 #pragma unroll
-            for (int k = 13; k < 16; ++k) bl[k] = 0.f;
+            for (int k = BL_F; k < BL_GA; ++k) bl[k] = 0.f;
         }
 #pragma unroll
-        for (int k = 16; k < BL_SLOTS; ++k) bl[k] = 0.f;
+        for (int k = BL_GA; k < BL_SLOTS; ++k) bl[k] = 0.f;
     }
     long long tprev = DIAG && a.prof ? clock64() : 0;
     const long long wt0 = DIAG && a.wave_times ? wall_clock64() : 0;
@@ -733,12 +765,12 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         // margin / h ... - are then evaluated where they are used, a few scalar-operand instructions each, instead of being hoisted in front
         // of the substep loop and kept - spilled: in the racket + ball kernels - across all of it)
         float h = h_launch;
-        if constexpr (OPAQUE_H) asm volatile("" : "+s"(h));
+        if constexpr (F::OPAQUE_H) asm volatile("" : "+s"(h));
         const bool wrench_on = sub < P.hold_sub;
         const bool last = sub == nsub - 1;
         // a substep that is being recomputed by a job that gave up waiting for its predecessor: it publishes nothing (the predecessor does)
         const bool replay = JOBS && !mono && sub < jstart(sjob);
-        LLPH(0);
+        LLPH(PROF_HEAD);
         // per-link model constants are (re)loaded where they are used (L1/K$ hits) instead of pinning ~20 registers for the whole
         // kernel; the opaque index keeps the compiler from hoisting the loads back out of the substep loop
         int bo = b;
@@ -791,11 +823,11 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     const float vspin = PHYS_SQRT(dot(bw, bw)) * (1.f / 6.28318530717959f);
                     float cl = PHYS_RCP(2.f + fabsf(vs * PHYS_RCP(vspin * BP.spin_scale + 1e-6f)));
                     cl = vspin > 0.f ? -cl : cl;
-                    const V3 F = (-kf * cd * vs) * bv - (kf * cl * vs * vs) * lt;
-                    bl[BL_F] = F.x; bl[BL_F + 1] = F.y; bl[BL_F + 2] = F.z;
+                    const V3 Fa = (-kf * cd * vs) * bv - (kf * cl * vs * vs) * lt;
+                    bl[BL_F] = Fa.x; bl[BL_F + 1] = Fa.y; bl[BL_F + 2] = Fa.z;
                 }
-                const V3 F{bl[BL_F], bl[BL_F + 1], bl[BL_F + 2]};
-                const V3 bvs = bv + h * (V3{0.f, 0.f, P.gravity_z} + BP.inv_mass * F);  // free flight: v*
+                const V3 Fa{bl[BL_F], bl[BL_F + 1], bl[BL_F + 2]};
+                const V3 bvs = bv + h * (V3{0.f, 0.f, P.gravity_z} + BP.inv_mass * Fa);  // free flight: v*
                 bl[BL_VEL] = bvs.x; bl[BL_VEL + 1] = bvs.y; bl[BL_VEL + 2] = bvs.z;
                 const float ih = PHYS_RCP(h), coff = P.contact_offset;
                 // ---- ball x ground (speculative margin: the distance the ball can close within this substep)
@@ -956,8 +988,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             if (b == 0 && wrench_on) {
                 V3 extF, extT;
                 if (a.actions) {
-                    extF = V3{wrench_park[PARK_TAR * 64], wrench_park[(PARK_TAR + 1) * 64], wrench_park[(PARK_TAR + 2) * 64]};
-                    extT = V3{wrench_park[25 + PARK_TAR * 64], wrench_park[25 + (PARK_TAR + 1) * 64], wrench_park[25 + (PARK_TAR + 2) * 64]};
+                    extF = wrench_get(wrench_park, WRENCH_FORCE_LANE);
+                    extT = wrench_get(wrench_park, WRENCH_TORQUE_LANE);
                 } else {
                     const float* cw = a.ctrl + env_here() * CTRL_SLOTS;
                     extF = V3{ldin(&cw[CT_FORCE + 0]), ldin(&cw[CT_FORCE + 1]), ldin(&cw[CT_FORCE + 2])};
@@ -971,7 +1003,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         // pose of the link: next used by contact generation, then by the integration
         park[PARK_Q * 64] = q.x; park[(PARK_Q + 1) * 64] = q.y; park[(PARK_Q + 2) * 64] = q.z; park[(PARK_Q + 3) * 64] = q.w;
         park_put3(PARK_X, x);
-        LLPH(1);
+        LLPH(PROF_PASS1);
         park_vel(w, xd);
         // ================================================================ pass 2: articulated inertia, leaves -> root by level
         Sym3 Di{1.f, 0.f, 0.f, 1.f, 0.f, 1.f};
@@ -1053,7 +1085,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             }
         }
 
-        LLPH(2);
+        LLPH(PROF_PASS2);
         unpark_vel(w, xd);
         // ================================================================ root: 6x6 solve (lane 0 of each env)
         Blocks Lam;  // operational-space inverse inertia of this lane's link (root: inverse articulated inertia)
@@ -1101,9 +1133,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             }
         }
 
-        LLPH(3);
+        LLPH(PROF_PASS3);
         if (CONTACT) park_vel(w, xd);
-        float* const rootlam = park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + PARK_SLOTS * 64 + 2 * BL_SLOTS + half * 24;
+        float* const rootlam = wave_lds + LDS_ROOTLAM + half * ROOTLAM_ROW;
         if (PARK2 && CONTACT && lb == 0) {  // only the root's Lambda exists yet: 21 floats per env, out of the way while contacts are generated
             const float lv[21] = {Lam.A.xx, Lam.A.xy, Lam.A.xz, Lam.A.yy, Lam.A.yz, Lam.A.zz, Lam.B.m[0], Lam.B.m[1], Lam.B.m[2], Lam.B.m[3], Lam.B.m[4], Lam.B.m[5],
                                   Lam.B.m[6], Lam.B.m[7], Lam.B.m[8], Lam.C.xx, Lam.C.xy, Lam.C.xz, Lam.C.yy, Lam.C.yz, Lam.C.zz};
@@ -1135,7 +1167,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             int pack = 0x0fffffff;  // four 7-bit vertex slots (127 = none), manifold size in bits 28..30
             long long tsub = DIAG && a.prof ? clock64() : 0;
             const unsigned long long nball = __ballot(near);
-            LLSUB(16);
+            LLSUB(PROF_CULL);
             if (nball) {
                 // The hulls of the few links near the ground are scanned by GROUPS of 8 lanes, 8 groups per wave: in every round group g
                 // takes the next near link of the WAVE (the near links of both envs in lane order), whichever env it belongs to - a
@@ -1149,14 +1181,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 const int rounds = (ntot + 7) >> 3;
                 const int myk = (half ? nr0 : 0) + __popc(nm & ((1u << lb) - 1u));  // rank of this link among the near links of the wave
                 const int grp = lane >> 3, gl = lane & 7;
-#ifdef V2P_LL_REGS_BUILD
-                constexpr bool FASTARG = !BALL && !LIMITS && !TGS && !DIAG;  // (see grp_arg; the register build spills in its TGS kernels with it)
-#else
-                constexpr bool FASTARG = !BALL && !LIMITS;
-#endif
-                int* const scr = (int*)(park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + PARK_SCR * 64);  // k-th near link -> its lane
+                int* const scr = (int*)(wave_lds + LDS_PARK + PARK_SCR * 64);  // k-th near link -> its lane
                 if (near) scr[myk] = lane;
-                if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[13], (unsigned long long)rounds);
+                LLCOUNT(PROF_ROUNDS, rounds);
                 for (int rd = 0; rd < rounds; ++rd) {
                     const int kk = 8 * rd + grp;
                     const bool gon = kk < ntot;
@@ -1201,7 +1228,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     clo |= grp_xor1(clo); chi |= grp_xor1(chi);
                     clo |= grp_xor2(clo); chi |= grp_xor2(chi);
                     clo |= grp_mirror(clo); chi |= grp_mirror(chi);
-                    grp_arg<false, FASTARG>(zmin, k0);
+                    grp_arg<false, F::FASTARG>(zmin, k0);
                     const unsigned long long cm = ((unsigned long long)chi << 32) | clo;
                     const int cntg = __popc(clo) + __popc(chi);
                     unsigned long long t = cm;
@@ -1212,7 +1239,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     int ns = cntg < 4 ? cntg : 4;
                     const bool big = gon && cntg > 4;
                     if (any64(big)) {
-                        if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[15], 1ull);
+                        LLCOUNT(PROF_MANIFOLDS, 1ull);
                         // manifold reduction: deepest, farthest from it, extreme on either side of that line
                         const int k0s = k0 < 0 ? 0 : k0;
                         const float4 u0 = hullv(v0L + k0s);
@@ -1231,7 +1258,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             best = take ? d2 : best;
                             k1 = take ? 8 * k + gl : k1;
                         }
-                        grp_arg<true, FASTARG>(best, k1);
+                        grp_arg<true, F::FASTARG>(best, k1);
                         const int k1s = k1 < 0 ? 0 : k1;
                         const float4 u1 = hullv(v0L + k1s);
                         const float ex = xx + r0 * u1.x + r1 * u1.y + r2 * u1.z - p0x;
@@ -1250,8 +1277,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             amax = up ? area : amax; k2 = up ? 8 * k + gl : k2;
                             amin = dn ? area : amin; k3 = dn ? 8 * k + gl : k3;
                         }
-                        grp_arg<true, FASTARG>(amax, k2);
-                        grp_arg<false, FASTARG>(amin, k3);
+                        grp_arg<true, F::FASTARG>(amax, k2);
+                        grp_arg<false, F::FASTARG>(amin, k3);
                         if (big) {
                             s0 = k0; s1 = k1;
                             s2 = k2 >= 0 ? k2 : k3;
@@ -1264,7 +1291,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     pack = (near && (myk >> 3) == rd) ? got : pack;
                 }
             }
-            LLSUB(17);
+            LLSUB(PROF_SCAN);
             int sel4[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -1293,7 +1320,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 for (int c = 0; c < 4; ++c) a.contact_ids_sub[((env_here() * nsub + sub) * NB + b) * 4 + c] = c < cnt ? b * 64 + sel4[c] : -1;
             }
 
-            LLSUB(18);
+            LLSUB(PROF_POINTS);
             if (PARK2 && lb == 0) {  // Lambda of the root back from its block
                 float lv[21];
 #pragma unroll
@@ -1339,18 +1366,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             const unsigned long long lmb = LIMITS ? __ballot(valid && limact) : 0ull;
             const unsigned lm0 = (unsigned)lmb, lm1 = (unsigned)(lmb >> 32);
             if (DIAG && a.wave_times) { const int tt = __popc(half ? m1 : m0); tsum += tt; tmaxs = tt > tmaxs ? tt : tmaxs; }
-            // SETUPX (the kernels with the visit table, see VTAB below): the depth of each env's deepest touched link is a reduction of the
-            // lanes' own depths on the DPP network, and the visit table is formed by the stops' own lanes (below, where it is built).  The other kernels
-            // walk the touched links with a load of the model's depth table per link, and fill the table stop by stop: with the reduction
-            // alone, nine of the racket + ball, joint-limit and TGS kernels of the default build need 4 - 16 B more scratch per lane and
-            // four of the register build 4 - 8 B (profiles/r21a_kres_*_reduction_in_every_kernel.txt against r21a_kres_*_all_kernels.txt).
-#ifdef V2P_LL_REGS_BUILD
-            constexpr bool SETUPX = !LIMITS && !TGS && !BALL && !DIAG;
-#else
-            constexpr bool SETUPX = !LIMITS && !TGS && !BALL;
-#endif
+            // (F::SETUPX, with the visit table: the depth of each env's deepest touched link by a reduction on the DPP network, ll_forms.hpp)
             [[maybe_unused]] int tdep0 = 0, tdep1 = 0;
-            if constexpr (SETUPX) {
+            if constexpr (F::SETUPX) {
                 // (half_max_last: all 64 lanes are on here - top level of the substep - and the value is never negative; `touched` keeps
                 // the 99 of the idle lanes out)
                 const int tdred = half_max_last(touched ? dep : 0);
@@ -1360,14 +1378,14 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             if (last) {
                 const unsigned mine = half ? m1 : m0;
                 ksum = __popc(mine);
-                if constexpr (SETUPX) {
+                if constexpr (F::SETUPX) {
                     kdep = half ? tdep1 : tdep0;
                 } else {
                     kdep = 0;
                     for (unsigned t = mine; t; t &= t - 1) { const int dd = M.depth[__ffs(t) - 1]; kdep = dd > kdep ? dd : kdep; }
                 }
             }
-            if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) { atomicAdd((unsigned long long*)&a.prof[9], (unsigned long long)(__popc(m0) + __popc(m1))); atomicAdd((unsigned long long*)&a.prof[10], 1ull); }
+            if (DIAG && a.prof && LLSAMPLED) { atomicAdd((unsigned long long*)&a.prof[PROF_TOUCHED], (unsigned long long)(__popc(m0) + __popc(m1))); atomicAdd((unsigned long long*)&a.prof[PROF_SUBSTEPS], 1ull); }
             const bool sweep_on = ((m0 | m1 | lm0 | lm1) || (BALL && any64(ballground))) && P.n_iter > 0;
             if (PARK2 && !sweep_on) unpark_vel(w, xd);
             if (sweep_on) {
@@ -1375,7 +1393,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 // per-update propagation stop there; their velocities catch up once at the end (the propagation is linear)
                 // (each env stops at ITS deepest touched link, so its arithmetic does not depend on which env shares the wave)
                 int dn0 = 0, dn1 = 0;
-                if constexpr (SETUPX) {
+                if constexpr (F::SETUPX) {
                     dn0 = tdep0;
                     dn1 = tdep1;
                 } else {
@@ -1384,7 +1402,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 }
                 const int dneed = dn0 > dn1 ? dn0 : dn1, dmin = dn0 < dn1 ? dn0 : dn1;
                 const bool insweep = dep <= (half ? dn1 : dn0);  // this link moves with every update; the others catch up afterwards
-                LLPH(4);
+                LLPH(PROF_CONTACTS);
                 // ======================================================== Lambda_b, root -> leaves by level
                 for (int d = 1; d <= dneed; ++d) {
                     Blocks Lp;
@@ -1483,16 +1501,16 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         }
                     }
                 }
-                LLPH(5);
+                LLPH(PROF_LAMBDA);
                 if (!PARK2) {
                     park_put3(PARK_W0, w);  // the sweep's total delta-velocity of a link = its velocity at the end - these
                     park_put3(PARK_XD0, xd);
                 }
                 // touched links whose parent is the touched link right before them (ascending).  Nothing reads these masks any more (the
                 // per-group sweep that did is gone), but without this loop the compiler lowered the control flow of the sweep differently
-                // (-0.5 %, later -1.1 %: docs/NOTES.md B, 2026-10-19).  With the set-up of SETUPX in front of the sweep that no longer
+                // (-0.5 %, later -1.1 %: docs/NOTES.md B, 2026-10-19).  With the set-up of F::SETUPX in front of the sweep that no longer
                 // holds (measured again, same section): those kernels go without it; the others keep the loop and stay as they were.
-                if constexpr (!SETUPX) {
+                if constexpr (!F::SETUPX) {
                     [[maybe_unused]] unsigned chain0 = 0u, chain1 = 0u;
                     int prev = -1;
                     for (unsigned t = m0; t; t &= t - 1) {
@@ -1537,7 +1555,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 // LIMITS: the walk also stops at the joints that carry limit rows (their block comes right before the contact block of the link)
                 const unsigned v0 = LIMITS ? m0 | lm0 : m0, v1 = LIMITS ? m1 | lm1 : m1;
                 V3 jt_new{0.f, 0.f, 0.f};  // LIMITS: limit impulse of this joint not yet handed up (its reaction, -jt, goes to the parent)
-                // VTAB (the kernels without joint limits and TGS): the same moves filed by VISIT instead of by link.  The walk takes the k-th
+                // F::VTAB (the kernels without joint limits and TGS): the same moves filed by VISIT instead of by link.  The walk takes the k-th
                 // stop of both envs in the same visit, in every iteration, so everything about visit k but `live` and `done` is fixed for the
                 // substep:
                 //   vis    lane k of an env's half: the move into its k-th stop (as minfo) | bit 24: the env moves in this visit once it is
@@ -1550,44 +1568,19 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 //          env's own last stop, whose number differs between the envs: hence a bit of its own).  24 links: 25 bits.
                 //   mystop the visit in which this lane's link is its env's stop, or -1
                 // (24 links per env: every env's stops fit the 32 lanes of its half, the table has no capacity limit.)
-                // The joint-limit kernels carry moves of their own inside a visit (the one-joint bounce) and keep the earlier form, the TGS
-                // kernels with them (as UPMASK below); with the table the ball kernels of the register build need 16 B more scratch per
-                // lane and its diagnostic kernel 20 B: they keep the earlier form too (docs/NOTES.md B, 2026-10-19, the sweep's visits).
-#ifdef V2P_LL_REGS_BUILD
-                constexpr bool VTAB = !LIMITS && !TGS && !BALL && !DIAG;
-#else
-                constexpr bool VTAB = !LIMITS && !TGS && !BALL;
-#endif
-                // LIVEM (with the visit table): whether an env has applied an impulse yet is bit h of ONE scalar word (`livem`), fed by the two
-                // halves of the change ballot as two scalars.  As two bools (the earlier form, which the other kernels keep with their visits)
-                // the compiler holds `live` in two lane masks, and every visit turns them into a scalar through a VGPR again
-                // (docs/NOTES.md B, 2026-10-19, the way down and the rest of the sweep).
-                static_assert(VTAB == SETUPX, "the set-up in front of the sweep and the table go together");
-                constexpr bool LIVEM = VTAB;
-                // ROWX: the rows of a visit's stops, point by point, without selects and without a dispatch between the points: a point's
-                // three rows run as a divergent region of the lanes whose point is active.  ROWCNT (with the visit table): whether point c
-                // exists for either stop is a scalar test on the stops' numbers of points, which the visit words carry in bits 25 - 27;
-                // without the table it stays a vote.  The register build's kernels without the table keep the earlier form, a vote per point
-                // and `dl` selected per row: with the regions its TGS + joint-limit kernel needs 12 B more scratch per lane
-                // (docs/NOTES.md B, 2026-10-19, the rows).
-#ifdef V2P_LL_REGS_BUILD
-                constexpr bool ROWX = VTAB;
-#else
-                constexpr bool ROWX = true;
-#endif
-                constexpr bool ROWCNT = ROWX && VTAB;
+                // (which kernels run which form - F::VTAB, and with it F::LIVEM, F::ROWX, F::ROWCNT - and why: ll_forms.hpp)
                 int minfo = 0;
                 [[maybe_unused]] int vis = 0, mystop = -1, nvis0 = 0, nvis1 = 0;
-                [[maybe_unused]] int livem = 0;  // LIVEM: bit h = env h is live (wave-uniform, in a scalar register)
+                [[maybe_unused]] int livem = 0;  // F::LIVEM: bit h = env h is live (wave-uniform, in a scalar register)
                 [[maybe_unused]] unsigned anc = 0u;
-                // The table (VTAB) is formed by the STOPS' OWN LANES, all at once, instead of stop by stop for the wave: a stop's lane knows
+                // The table (F::VTAB) is formed by the STOPS' OWN LANES, all at once, instead of stop by stop for the wave: a stop's lane knows
                 // its number (the stops below it in its env's mask), the stop before it (cyclically), its own depth and number of points;
                 // the depths of the stop before and of their lowest common ancestor are counts of the model's ancestor masks (what the
                 // three ballots per stop of the earlier form counted), read with the side levels in loads under one wait.  The word goes
                 // to lane k of the env through the wave's scratch row in LDS (free outside contact generation).  What is left of the loop
                 // over the stops is the bit of `anc`: the ancestor mask of the env's k-th stop, read from the stop's lane, IS the lane
                 // mask of bit k + 1 - both envs' masks side by side are one 64-bit lane mask, one select and one OR per stop.
-                if constexpr (VTAB) {
+                if constexpr (F::VTAB) {
                     const unsigned mine = half ? v1 : v0;
                     nvis0 = __popc(v0);
                     nvis1 = __popc(v1);
@@ -1604,8 +1597,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         const int du = __popc(ancp) - 1, dl = __popc(ancp & ancme) - 1;
                         // (levels of the way up where the path link is not its parent's first child: it hands over through a pull, see walk_to)
                         const int sd = sdp & ~((2 << dl) - 1);
-                        // (bits 25 - 27, ROWCNT: the stop's number of points)
-                        vrow[kme - lb] = dl | (du << 4) | (dep << 8) | ((sd & 0xfff) << 12) | (nmine > 1 ? 1 << 24 : 0) | (ROWCNT ? cnt << 25 : 0);
+                        // (bits 25 - 27, F::ROWCNT: the stop's number of points)
+                        vrow[kme - lb] = dl | (du << 4) | (dep << 8) | ((sd & 0xfff) << 12) | (nmine > 1 ? 1 << 24 : 0) | (F::ROWCNT ? cnt << 25 : 0);
                         mystop = kme;
                     }
                     vis = lb < nmine ? vrow[0] : 0;
@@ -1636,16 +1629,13 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         p1 = b1;
                     }
                 }
-                if constexpr (VTAB) {  // (nothing tracks where a walk stands; where it closes, after whole sweeps, it stands on the env's last stop)
+                if constexpr (F::VTAB) {  // (nothing tracks where a walk stands; where it closes, after whole sweeps, it stands on the env's last stop)
                     cur0 = v0 ? 31 - __clz(v0) : 0;
                     cur1 = v1 ? 31 - __clz(v1) : 0;
                 }
-                // whether walk_to runs the way up in its masked form.  The joint-limit and TGS kernels keep the earlier form: with the masked
-                // one the joint-limit kernels of the register build need 4 .. 16 B more scratch per lane, and two TGS tests of the racket + ball
-                // kernels missed their bounds by 1 % and 5 % - cause not found, see docs/NOTES.md B 2026-10-19
-                constexpr bool UPMASK = !LIMITS && !TGS;
+                // (F::UPMASK: whether walk_to runs the way up in its masked form, ll_forms.hpp)
                 // one move of both walks: env h goes from cur_h to its next link when mv_h (info_h = the move, see minfo), else it rests
-                [[maybe_unused]] int vk = 0;  // VTAB: the visit in which walk_to runs (it reads the roles from anc; nx0, nx1 are not used then)
+                [[maybe_unused]] int vk = 0;  // F::VTAB: the visit in which walk_to runs (it reads the roles from anc; nx0, nx1 are not used then)
                 auto walk_to = [&](int nx0, int nx1, int info0, int info1, bool mv0, bool mv1) {
                     long long tsub = DIAG && a.prof ? clock64() : 0;
                     // a resting env: empty ranges that do not widen the loops (LCA depth 15, depths 0)
@@ -1655,7 +1645,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     const int dl1 = pk1 & 15, dn1 = (pk1 >> 8) & 15;
                     const int selc = half ? cur1 : cur0, seln = half ? nx1 : nx0, mydl = half ? dl1 : dl0;
                     // ancestors (or self) of cur / of next
-                    const bool onc = VTAB ? ((anc >> vk) & 1u) != 0u : valid && ((desc >> selc) & 1), onn = VTAB ? ((anc >> vk) & 2u) != 0u : valid && ((desc >> seln) & 1);
+                    const bool onc = F::VTAB ? ((anc >> vk) & 1u) != 0u : valid && ((desc >> selc) & 1), onn = F::VTAB ? ((anc >> vk) & 2u) != 0u : valid && ((desc >> seln) & 1);
                     // LIMITS: a way up on which no link holds anything to hand over is not walked (the stops at joints whose limit rows
                     // do not act - most of them - leave nothing behind; the lowest common ancestor has been current since the walk came
                     // down through it): that env's way up counts as resting
@@ -1688,7 +1678,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                     // link where this env's walk turns still holds what arrived there, and answers it with its Lambda - once, behind the
                     // loop, for both envs together (zeros if its level was not walked).  One form for every level: no select, no copy
                     // between two forms, Dw, Dv are not touched inside the loop.
-                    if constexpr (UPMASK) {
+                    if constexpr (F::UPMASK) {
                         const int dmax = du0 > du1 ? du0 : du1;
                         if (dmax > ulmin) {
                             const int rcdep = onc ? dep + 1 : -1;  // the level on which this lane's link receives
@@ -1781,7 +1771,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             }
                         }
                     }
-                    LLSUB(12);
+                    LLSUB(PROF_UP);
                     // ---- down
                     const int dtop = dn0 > dn1 ? dn0 : dn1;
                     for (int d = dlmin + 1; d <= dtop; ++d) {
@@ -1793,28 +1783,28 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             Dv = tv;
                         }
                     }
-                    LLSUB(14);
+                    LLSUB(PROF_DOWN);
                 };
                 // the walk returns to the root (its Lambda answers the total) and one root -> leaves pass moves the links down to depth dlast
                 // (all of them, or those the sweep reads: the links down to the env's deepest stop)
                 auto walk_close = [&](int dlast, bool all) {
-                    [[maybe_unused]] long long tclose = V2P_LL_DIAGX && a.prof ? clock64() : 0;
+                    [[maybe_unused]] long long tclose = F::DIAGX && a.prof ? clock64() : 0;
                     const int i0 = ((int)__builtin_amdgcn_readlane(dep, cur0) << 4) | (M.side_depths[cur0] << 12);
                     const int i1 = ((int)__builtin_amdgcn_readlane(dep, 32 + cur1) << 4) | (M.side_depths[cur1] << 12);
-                    const int slive = LIVEM ? livem : __builtin_amdgcn_readfirstlane((live0 ? 1 : 0) | (live1 ? 2 : 0));
-                    // (VTAB: a walk closes after whole sweeps only - it stands on the env's last stop, bit 0 of anc; nothing goes down)
+                    const int slive = F::LIVEM ? livem : __builtin_amdgcn_readfirstlane((live0 ? 1 : 0) | (live1 ? 2 : 0));
+                    // (F::VTAB: a walk closes after whole sweeps only - it stands on the env's last stop, bit 0 of anc; nothing goes down)
                     vk = 0;
-                    [[maybe_unused]] const long long tmove = V2P_LL_DIAGX && a.prof ? clock64() : 0;
+                    [[maybe_unused]] const long long tmove = F::DIAGX && a.prof ? clock64() : 0;
                     walk_to(0, 0, i0, i1, (slive & 1) != 0, (slive & 2) != 0);
-                    // (counter 20: the closing move - its descriptor, the way up to the root, the turn there.  walk_to has timed itself into
+                    // (PROF_CLOSE_MOVE: the closing move - its descriptor, the way up to the root, the turn there.  walk_to has timed itself into
                     // the counters of the moves: taken out of `up` again, so that a counter of walk_to's own - one more captured variable,
                     // which moves the register allocation of every kernel - is not needed; `down` keeps the closing move's test of its
                     // empty range, a few cycles per substep)
-                    if (V2P_LL_DIAGX && a.prof) {
+                    if (F::DIAGX && a.prof) {
                         const long long tdone = clock64();
-                        if (((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[12], (unsigned long long)(tmove - tdone));
+                        LLADD(PROF_UP, tmove - tdone);
                     }
-                    LLSUBX(20, tclose);
+                    LLSUBX(PROF_CLOSE_MOVE, tclose);
                     long long tsub = DIAG && a.prof ? clock64() : 0;
                     V3 ddw{0.f, 0.f, 0.f}, ddv{0.f, 0.f, 0.f};
                     if (lb == 0) {
@@ -1834,7 +1824,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             xd = xd + ddv;
                         }
                     }
-                    LLSUBX_OR(21, 14);  // (counter 21: the root -> leaves pass of a closing walk; it was counted with the ways down before)
+                    LLSUBX_OR(PROF_CLOSE_PASS, PROF_DOWN);  // (the root -> leaves pass of a closing walk; it was counted with the ways down before)
                 };
                 // ---- ball x ground: a stop of its own after the last link - the last rows of a sweep (point at -R z of the centre; rows
                 // n = z, t1 = x, t2 = y); returns whether any lane's rows changed something
@@ -1872,7 +1862,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 // whatever the env it shares the wave with still does.  (Its later sweeps change nothing: the same moves re-derive the same
                 // velocities - the block updates they would take are saved.)
                 int done = 0;
-                if (V2P_LL_DIAGX && a.prof) { long long tsub = tprev; LLSUBX(23, tsub); }  // (counter 23: the sweep's set-up since the end of the Lambda phase - moves, visit table)
+                if (F::DIAGX && a.prof) { long long tsub = tprev; LLSUBX(PROF_SWEEP_SETUP, tsub); }  // (the sweep's set-up since the end of the Lambda phase - moves, visit table)
                 for (int it = 0; it < P.n_iter; ++it) {
                     unsigned t0 = (done & 1) ? 0u : v0, t1 = (done & 2) ? 0u : v1;
                     int moved = 0;  // bit h: env h changed something in this sweep (wave-uniform)
@@ -1905,44 +1895,44 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             }
                         }
                     }
-                    // VTAB: a counted loop over the visits of the envs that still iterate
-                    const int nvis = VTAB ? __builtin_amdgcn_readfirstlane(max((done & 1) ? 0 : nvis0, (done & 2) ? 0 : nvis1)) : 0;
-                    if (VTAB && ((done >> half) & 1)) {  // (done only grows: the env's visits are struck out once)
+                    // F::VTAB: a counted loop over the visits of the envs that still iterate
+                    const int nvis = F::VTAB ? __builtin_amdgcn_readfirstlane(max((done & 1) ? 0 : nvis0, (done & 2) ? 0 : nvis1)) : 0;
+                    if (F::VTAB && ((done >> half) & 1)) {  // (done only grows: the env's visits are struck out once)
                         vis = 0;
                         mystop = -1;
                     }
-                    // one visit: the k-th stop of both envs (VTAB; the earlier form takes the stops off t0, t1 and does not count)
+                    // one visit: the k-th stop of both envs (F::VTAB; the earlier form takes the stops off t0, t1 and does not count)
                     [[maybe_unused]] int k = 0;
-                    while (VTAB ? k < nvis : (t0 | t1) != 0u) {
-                        const int b0 = !VTAB && t0 ? __ffs(t0) - 1 : -1, b1 = !VTAB && t1 ? __ffs(t1) - 1 : -1;  // (VTAB: not needed)
-                        if constexpr (!VTAB) {
+                    while (F::VTAB ? k < nvis : (t0 | t1) != 0u) {
+                        const int b0 = !F::VTAB && t0 ? __ffs(t0) - 1 : -1, b1 = !F::VTAB && t1 ? __ffs(t1) - 1 : -1;  // (F::VTAB: not needed)
+                        if constexpr (!F::VTAB) {
                             t0 &= ~(b0 < 0 ? 0u : 1u << b0);
                             t1 &= ~(b1 < 0 ? 0u : 1u << b1);
                         }
-                        if (DIAG && a.prof && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[8], 1ull);
-                        [[maybe_unused]] long long thead = V2P_LL_DIAGX && a.prof ? clock64() : 0;  // (counter 22: head and tail of a visit - what neither the move nor the rows time)
+                        LLCOUNT(PROF_UPDATES, 1ull);
+                        [[maybe_unused]] long long thead = F::DIAGX && a.prof ? clock64() : 0;  // (PROF_VISIT_ENDS: head and tail of a visit - what neither the move nor the rows time)
                         int came_down = 0;  // LIMITS: bit h = env h has just come DOWN to its link (the lowest common ancestor of the move lies above it)
-                        [[maybe_unused]] int npts = 0;  // ROWCNT: the larger of the two stops' numbers of points (0 for an env that rests or is done)
+                        [[maybe_unused]] int npts = 0;  // F::ROWCNT: the larger of the two stops' numbers of points (0 for an env that rests or is done)
                         // (readfirstlane: wave-uniform by construction, and the compiler must know it - the level loops are scalar loops)
-                        if constexpr (VTAB) {
+                        if constexpr (F::VTAB) {
                             // (bit 24 of a visit word: the env has a stop here and more than one stop - it moves if it is live)
                             const int vi0 = __builtin_amdgcn_readlane(vis, k), vi1 = __builtin_amdgcn_readlane(vis, 32 + k);
-                            if constexpr (ROWCNT) npts = max((vi0 >> 25) & 7, (vi1 >> 25) & 7);
-                            const int smv = LIVEM ? livem & (((vi0 >> 24) & 1) | ((vi1 >> 23) & 2))
+                            if constexpr (F::ROWCNT) npts = max((vi0 >> 25) & 7, (vi1 >> 25) & 7);
+                            const int smv = F::LIVEM ? livem & (((vi0 >> 24) & 1) | ((vi1 >> 23) & 2))
                                                   : __builtin_amdgcn_readfirstlane((live0 ? (vi0 >> 24) & 1 : 0) | (live1 ? (vi1 >> 23) & 2 : 0));
                             if (smv) {
                                 vk = k;
-                                LLSUBX(22, thead);
+                                LLSUBX(PROF_VISIT_ENDS, thead);
                                 walk_to(0, 0, vi0, vi1, (smv & 1) != 0, (smv & 2) != 0);
-                                if (V2P_LL_DIAGX && a.prof) thead = clock64();
+                                if (F::DIAGX && a.prof) thead = clock64();
                             }
                         } else {
                             const int smv = __builtin_amdgcn_readfirstlane(((live0 && b0 >= 0 && b0 != cur0) ? 1 : 0) | ((live1 && b1 >= 0 && b1 != cur1) ? 2 : 0));
                             if (smv) {
                                 const int i0 = __builtin_amdgcn_readlane(minfo, b0 < 0 ? 0 : b0), i1 = __builtin_amdgcn_readlane(minfo, 32 + (b1 < 0 ? 0 : b1));
-                                LLSUBX(22, thead);
+                                LLSUBX(PROF_VISIT_ENDS, thead);
                                 walk_to(b0 < 0 ? 0 : b0, b1 < 0 ? 0 : b1, i0, i1, (smv & 1) != 0, (smv & 2) != 0);
-                                if (V2P_LL_DIAGX && a.prof) thead = clock64();
+                                if (F::DIAGX && a.prof) thead = clock64();
                                 if (LIMITS) came_down = smv & (((i0 & 15) < ((i0 >> 8) & 15) ? 1 : 0) | ((i1 & 15) < ((i1 >> 8) & 15) ? 2 : 0));
                             }
                             if (b0 >= 0) cur0 = b0;
@@ -2004,9 +1994,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             }
                         }
                         // ---- the rows of the link the walk stands on
-                        LLSUBX(22, thead);
+                        LLSUBX(PROF_VISIT_ENDS, thead);
                         long long tsub = DIAG && a.prof ? clock64() : 0;
-                        const bool me = VTAB ? mystop == k : valid && lb == bsel && (!LIMITS || (((half ? m1 : m0) >> (bsel < 0 ? 0 : bsel)) & 1u));
+                        const bool me = F::VTAB ? mystop == k : valid && lb == bsel && (!LIMITS || (((half ? m1 : m0) >> (bsel < 0 ? 0 : bsel)) & 1u));
                         V3 gn{0.f, 0.f, 0.f}, gf{0.f, 0.f, 0.f};  // what these rows add to the link's impulse
                         if (me) {
                             V3 wl = w + Dw, xl = xd + Dv;
@@ -2017,8 +2007,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             for (int c = 0; c < 4; ++c) { rr4[c] = CS.cr(c); lam4[c] = CS.lam(c); bias4[c] = CS.bias(c); }
                             V3 ws0{0.f, 0.f, 0.f}, xs0{0.f, 0.f, 0.f};  // VFRIC: v* of the link
                             if constexpr (VFRIC) { ws0 = park_get3(PARK_W0); xs0 = park_get3(PARK_XD0); }
-                            if constexpr (ROWX) {
-                                // An unrolled loop without `break` / `continue`.  ROWCNT: npts is a scalar, "c < npts" for c = 0 .. 3 are four
+                            if constexpr (F::ROWX) {
+                                // An unrolled loop without `break` / `continue`.  F::ROWCNT: npts is a scalar, "c < npts" for c = 0 .. 3 are four
                                 // scalar compares, and since c >= npts implies c + 1 >= npts the compiler threads them into four nested blocks.
                                 // Without the table: four votes (uniform over the at most two touched links solved here).
                                 // (The same body as an inlined lambda per point, called from four nested ifs, is NOT the same arithmetic: a
@@ -2026,7 +2016,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                                 // merge the normal row's relative velocity with the one of the `act` test and fold `ln + (nl - ln)`.)
 #pragma unroll
                                 for (int c = 0; c < 4; ++c) {
-                                    if (ROWCNT ? c < npts : any64(c < cnt)) {
+                                    if (F::ROWCNT ? c < npts : any64(c < cnt)) {
                                         const V3 rr = rr4[c];
                                         V3 t1{1.f, 0.f, 0.f}, t2{0.f, 1.f, 0.f};
                                         if constexpr (VFRIC) vfric_frame(ws0, xs0, rr, t1, t2);
@@ -2150,9 +2140,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             un_new = un_new + gn;
                             uf_new = uf_new + gf;
                         }
-                        LLSUBX(11, tsub);
+                        LLSUBX(PROF_ROWS, tsub);
                         const unsigned long long chg = __ballot(gn.x != 0.f || gn.y != 0.f || gn.z != 0.f || gf.x != 0.f || gf.y != 0.f || gf.z != 0.f);
-                        if constexpr (LIVEM) {
+                        if constexpr (F::LIVEM) {
                             // (the same ballot, its halves as two opaque scalars: `(unsigned)(chg >> 32) != 0` otherwise becomes a 64-bit
                             // "greater than", which the scalar unit does not have, and `live` a pair of lane masks that every visit turns
                             // into a scalar through a VGPR again)
@@ -2166,9 +2156,9 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                             live1 = live1 || (unsigned)(chg >> 32) != 0u;
                             moved |= ((unsigned)chg != 0u ? 1 : 0) | ((unsigned)(chg >> 32) != 0u ? 2 : 0);
                         }
-                        if (DIAG && a.prof && !chg && ((a.prof_heavy ? blockIdx.x < 8u : (blockIdx.x & 63) == 0)) && lane == 0) atomicAdd((unsigned long long*)&a.prof[19], 1ull);
-                        LLSUBX_OR(22, 11);  // (the tail: the ballot of the change, live, moved)
-                        if constexpr (VTAB) ++k;
+                        if (DIAG && a.prof && !chg && LLSAMPLED) atomicAdd((unsigned long long*)&a.prof[PROF_NULL_UPDATES], 1ull);
+                        LLSUBX_OR(PROF_VISIT_ENDS, PROF_ROWS);  // (the tail: the ballot of the change, live, moved)
+                        if constexpr (F::VTAB) ++k;
                     }
                     if (BALL) moved |= ball_ground_rows(done);
                     if (TGS && (live0 || live1)) {
@@ -2181,7 +2171,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                         if (done == 3) break;
                     }
                 }
-                if (!TGS && (LIVEM ? livem != 0 : (live0 || live1))) walk_close(maxd, true);
+                if (!TGS && (F::LIVEM ? livem != 0 : (live0 || live1))) walk_close(maxd, true);
                 // links below the deepest touched one: one catch-up pass with the accumulated motion of their parents
                 // (PGS: the walk moves every link when it closes)
                 V3 accw = w - park_get3(PARK_W0), accv = xd - park_get3(PARK_XD0);
@@ -2199,7 +2189,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             }
         }
 
-        LLPH(6);
+        LLPH(PROF_SWEEP);
         V3 cimp_v{0.f, 0.f, 0.f};  // VFRIC: net contact impulse of this link's ground points, world axes (v* is about to leave its slots)
         if constexpr (VFRIC && CONTACT) {
             const V3 ws0 = park_get3(PARK_W0), xs0 = park_get3(PARK_XD0);
@@ -2354,7 +2344,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         }
     }
 
-    LLPH(7);
+    LLPH(PROF_INTEGRATE);
     // (opaque copy of the link index for everything after the substeps: indices and addresses formed from it are computed here instead of
     // being kept - spilled to scratch, which is HBM write traffic for every wave - since the prologue)
     int bo2 = b;
@@ -2432,8 +2422,8 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
         {
             // Link b owns the adjacent chunks 2b, 2b + 1 (one 32-byte read per lane on the other side).  Written by their owner, every
             // store instruction would touch half of each 64-byte line (PMC WRITE_SIZE: +14 MB per launch of partial-line write-throughs);
-            // instead lane l of an env writes chunk 24 k + l in instruction k = 0, 1 - 24 adjacent chunks = six full lines -, fetching
-            // the values from the lane that owns them (link 12 k + l / 2, its first or second chunk).
+            // instead lane l of an env writes chunk hand_link(12 k) + l in instruction k = 0, 1 - 24 adjacent chunks = six full lines -,
+            // fetching the values from the lane that owns them (link 12 k + l / 2, its first or second chunk).
             const bool root = b == 0;
             const float A0 = root ? q.x : jq.x, A1 = root ? q.y : jq.y, A2 = root ? q.z : jq.z, A3 = root ? q.w : jq.w;
             const float B0 = root ? x.x : wt.x, B1 = root ? x.y : wt.y, B2 = root ? x.z : wt.z, B3 = root ? xd.x : 0.f;
@@ -2444,25 +2434,30 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
                 const int src = base + 12 * k + ((lb >> 1) < 12 ? (lb >> 1) : 0);
                 const float a0 = pull(A0, src), a1 = pull(A1, src), a2 = pull(A2, src), a3 = pull(A3, src);
                 const float b0 = pull(B0, src), b1 = pull(B1, src), b2 = pull(B2, src), b3 = pull(B3, src);
-                if (valid && live_env) cstore4(ho + 4 * (24 * k + lb), second ? b0 : a0, second ? b1 : a1, second ? b2 : a2, second ? b3 : a3);
+                if (valid && live_env) cstore4(ho + 4 * (hand_link(NB / 2 * k) + lb), second ? b0 : a0, second ? b1 : a1, second ? b2 : a2, second ? b3 : a3);
             }
             if (root && valid && live_env) {
-                cstore4(ho + 4 * 48, xd.y, xd.z, w.x, w.y);
+                static_assert(HAND_FORCE_AT == 1, "the residual force rides behind w.z");
+                cstore4(ho + 4 * HAND_ROOT_VEL, xd.y, xd.z, w.x, w.y);
                 if (a.actions && jstart(sjob + 1) < a.p.hold_sub) {  // the next job still applies the residual wrench: it travels along
-                    const float* wp = park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + base;
-                    cstore4(ho + 4 * 49, w.z, wp[PARK_TAR * 64], wp[(PARK_TAR + 1) * 64], wp[(PARK_TAR + 2) * 64]);
-                    cstore4(ho + 4 * 54, wp[25 + PARK_TAR * 64], wp[25 + (PARK_TAR + 1) * 64], wp[25 + (PARK_TAR + 2) * 64], 0.f);
+                    // (component by component in the argument lists, not through wrench_get: with a V3 in between, the register build's
+                    // racket + ball kernels compile to other code)
+                    const float* wp = wave_lds + base;
+                    cstore4(ho + 4 * (HAND_ROOT_VEL + 1), w.z, wrench_at(wp, WRENCH_FORCE_LANE, 0), wrench_at(wp, WRENCH_FORCE_LANE, 1), wrench_at(wp, WRENCH_FORCE_LANE, 2));
+                    cstore4(ho + 4 * HAND_TORQUE, wrench_at(wp, WRENCH_TORQUE_LANE, 0), wrench_at(wp, WRENCH_TORQUE_LANE, 1), wrench_at(wp, WRENCH_TORQUE_LANE, 2), 0.f);
                 } else {
-                    cstore4(ho + 4 * 49, w.z, 0.f, 0.f, 0.f);
+                    cstore4(ho + 4 * (HAND_ROOT_VEL + 1), w.z, 0.f, 0.f, 0.f);
                 }
             }
         }
         if (BALL && ball_lane && live_env) {
             float* const ho = a.job_hand + ((int64_t)sjob * N + e) * HAND_FLOATS;
-            cstore4(ho + 4 * 50, bl[0], bl[1], bl[2], bl[3]);
-            cstore4(ho + 4 * 51, bl[4], bl[5], bl[6], bl[7]);
-            cstore4(ho + 4 * 52, bl[8], bl[9], bl[10], bl[11]);
-            cstore4(ho + 4 * 53, bl[12], bl[13], bl[14], bl[15]);
+            // (written out: as an unrolled loop over the chunks the same stores move the block numbers of the rows' dispatch in the
+            // register build's ball kernels, and their code with them)
+            cstore4(ho + 4 * HAND_BALL, bl[BL_POS], bl[BL_POS + 1], bl[BL_POS + 2], bl[BL_QUAT]);
+            cstore4(ho + 4 * (HAND_BALL + 1), bl[BL_QUAT + 1], bl[BL_QUAT + 2], bl[BL_QUAT + 3], bl[BL_VEL]);
+            cstore4(ho + 4 * (HAND_BALL + 2), bl[BL_VEL + 1], bl[BL_VEL + 2], bl[BL_ANG], bl[BL_ANG + 1]);
+            cstore4(ho + 4 * (HAND_BALL + 3), bl[BL_ANG + 2], bl[BL_F], bl[BL_F + 1], bl[BL_F + 2]);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (inline asm: the compiler must not drop or move this drain)
         if (lane == 0) {
@@ -2517,7 +2512,7 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     // L2 with partial lines from two XCDs' worth of neighbours (PMC WRITE_SIZE 1.7x the bytes).  The rows are staged through the
     // (now idle) LDS parking area and leave as 78 contiguous 16-byte stores per env: full lines.
     {
-        float* const stage = park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + half * (NB * 13);
+        float* const stage = wave_lds + LDS_STAGE + half * STAGE_FLOATS;
         if (valid) {
             float* o = stage + b * 13;
             o[0] = x.x; o[1] = x.y; o[2] = x.z;
@@ -2553,11 +2548,12 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
             }
             // reward sums over the bodies, bodies ascending like env_post_kernel: the terms go through this lane's LDS column (the parking
             // area is idle by now; a wave's LDS accesses execute in order), lanes 0..3 of each env add one term each
+            static_assert(REWARD_SLOTS == 4, "dof, vel, pos, rot");
             park[0] = rp.dof; park[64] = rp.vel; park[128] = rp.pos; park[192] = rp.rot;
             const unsigned long long fb = __ballot(fl);
             const bool fell = (half ? (unsigned)(fb >> 32) : (unsigned)fb) != 0u;
             float sk = 0.f;
-            if (lb < 4) sk = strict::sum_bodies(park_all + (threadIdx.x >> 6) * LDS_FLOATS_PER_WAVE + lb * 64 + base);
+            if (lb < REWARD_SLOTS) sk = strict::sum_bodies(wave_lds + LDS_PARK + lb * 64 + base);
             const float s4[4] = {pull(sk, base), pull(sk, base + 1), pull(sk, base + 2), pull(sk, base + 3)};
             if (lb == 0 && live_env) strict::post_env(Z.b, Z.t, P, mid, t_new, e, s4, fell);
         }
@@ -2575,6 +2571,15 @@ __global__ __launch_bounds__(64 * LL_WPB, DIAG ? 2 : (BALL ? V2P_LL_WPS_BALL : (
     timeline();
 }
 }  // namespace V2P_LL_NS
+
+// run-time bools -> template arguments: f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...)
+template <typename Fn, typename... Cs>
+static void with_bools(Fn&& f, Cs... cs) { f(cs...); }
+template <typename Fn, typename... Rest>
+static void with_bools(Fn&& f, bool b, Rest... rest) {
+    if (b) with_bools(f, rest..., std::true_type{});
+    else with_bools(f, rest..., std::false_type{});
+}
 
 int V2P_LL_LAUNCHER(v2p_env* env, hipStream_t s, float* actions, int* fused_post) {
     const unsigned blocks = (unsigned)((env->n + 2 * LL_WPB - 1) / (2 * LL_WPB));
@@ -2595,27 +2600,23 @@ int V2P_LL_LAUNCHER(v2p_env* env, hipStream_t s, float* actions, int* fused_post
     // nothing handed over): "substep jobs are invisible" holds by construction - two instantiations of the template are two
     // compilations, and under -fassociative-math nothing makes them round alike
     if (launch.diag) {
+        // the diagnostic kernel is the one fixed instantiation: the headline configuration, whole control steps per workgroup
         hipLaunchKernelGGL((physics_ll_kernel<true, false, false, true, false, false, false>), grid, block, lds, s, a);
     } else {
+        // The production instantiations, from the batch's configuration.  The rules, once:
+        //   JOBS is always on, DIAG always off
+        //   BALL or LIMITS imply CONTACT (their rows are solved in the contact sweep)
+        //   TGS and VFRIC (friction_frame = velocity) exist only with CONTACT: a batch without contacts has no rows
+        // which makes 2 (MULTI) x (1 without contacts + 16 with: TGS x BALL x LIMITS x VFRIC) = 34 kernels per build.
+        const bool ball = env->ball != nullptr, lim = env->p.joint_limits != 0;
+        const bool con = env->p.enable_contact != 0 || ball || lim;
         const bool multi = env->num_shapes > 1;  // per-env shapes: hull vertices come from the shape tables instead of the LDS copy
-        const bool tgs = env->p.solver_type == 1, lim = env->p.joint_limits != 0, ball = env->ball != nullptr, con = env->p.enable_contact != 0;
-        const bool vfric = env->p.friction_frame == 1 && con;
-#define V2P_LL_LAUNCH(C, T, B, L) do { \
-            if (vfric && C) { \
-                if (multi) hipLaunchKernelGGL((physics_ll_kernel<C, true, T, false, B, true, L, C>), grid, block, lds, s, a); \
-                else hipLaunchKernelGGL((physics_ll_kernel<C, false, T, false, B, true, L, C>), grid, block, lds, s, a); \
-            } else if (multi) hipLaunchKernelGGL((physics_ll_kernel<C, true, T, false, B, true, L>), grid, block, lds, s, a); \
-            else hipLaunchKernelGGL((physics_ll_kernel<C, false, T, false, B, true, L>), grid, block, lds, s, a); } while (0)
-        if (lim && ball && tgs) V2P_LL_LAUNCH(true, true, true, true);
-        else if (lim && ball) V2P_LL_LAUNCH(true, false, true, true);
-        else if (lim && tgs) V2P_LL_LAUNCH(true, true, false, true);
-        else if (lim) V2P_LL_LAUNCH(true, false, false, true);
-        else if (ball && tgs) V2P_LL_LAUNCH(true, true, true, false);
-        else if (ball) V2P_LL_LAUNCH(true, false, true, false);
-        else if (con && tgs) V2P_LL_LAUNCH(true, true, false, false);
-        else if (con) V2P_LL_LAUNCH(true, false, false, false);
-        else V2P_LL_LAUNCH(false, false, false, false);
-#undef V2P_LL_LAUNCH
+        const bool tgs = env->p.solver_type == 1 && con;
+        const bool vfric = env->p.friction_frame == 1 && env->p.enable_contact != 0;
+        with_bools([&](auto C, auto M, auto T, auto B, auto L, auto V) {
+            if constexpr (C() || !(T() || B() || L() || V()))
+                hipLaunchKernelGGL((physics_ll_kernel<C(), M(), T(), false, B(), true, L(), V()>), grid, block, lds, s, a);
+        }, con, multi, tgs, ball, lim, vfric);
     }
     ll_launch_done(env);
     return check_hip(hipGetLastError(), "physics_ll_kernel");

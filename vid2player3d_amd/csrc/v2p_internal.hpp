@@ -205,7 +205,7 @@ struct v2p_env {
     float* ws = {};                // SoA [WS_SLOTS][N] physics workspace
     int32_t* contact_ids = {};     // [N,24,4] debug
     int32_t* contact_ids_sub = {}; // [N,nsub,24,4] debug, every substep (v2p_sim_cfg.debug_substep_contacts), else NULL
-    long long* prof = {};          // [8] phase cycle counters when V2P_PHASE_TIMING is set (device), else NULL
+    long long* prof = {};          // [PROF_COUNT] cycle counters (enum Prof, phys_common.hpp) when V2P_PHASE_TIMING is set (device), else NULL
     long long* wave_times = {};    // [waves][4] per-wave wall-clock stamps of the last launch when V2P_WAVE_TIMES=<file> is set
     v2p::LlSchedule sched = {};    // pairing, substep jobs, kernel build: the launch policy of the link-per-lane schedule (ll_schedule.hpp)
     int substeps_per_sim = {};     // substeps of one simulate() call
@@ -237,7 +237,19 @@ inline int64_t job_wave_slots(int64_t n) { return (n + 2 * V2P_LL_WPB - 1) / (2 
 
 // state SoA slots
 constexpr int ST_ROOT_POS = 0, ST_ROOT_QUAT = 3, ST_JQUAT = 7, ST_VEL = 7 + 4 * NJ, STATE_SLOTS = 7 + 4 * NJ + 6 + 3 * NJ;  // 174
-constexpr int HAND_FLOATS = 224;  // 56 chunks of 4 floats: chunk 2b, 2b+1 = joint b (quaternion | rate), 0, 1, 48, 49 = root (49 also: residual force), 50 .. 53 = the ball (state 13 | aerodynamic force 3), 54 = residual torque
+// The hand-over record: what one substep job of the link-per-lane kernel hands to the next, per env (PhysArgs::job_hand; read in the
+// kernel's prologue, written in its epilogue).  56 chunks of 4 floats (16-byte write-through stores / loads):
+//   hand_link(b), + 1        joint b: quaternion | rate (the fourth float unused).  Link 0 is the root: quaternion | position, vx
+//   HAND_ROOT_VEL, + 1       the rest of the root's velocity: vy, vz, wx, wy | wz; behind wz, from float HAND_FORCE_AT of that chunk on,
+//                            the residual force of the fused step, while a later job still holds the wrench
+//   HAND_BALL .. + 3         the ball: the first 16 floats of its LDS block (state 13 | aerodynamic force 3)
+//   HAND_TORQUE              the residual torque (the fourth float unused)
+// (chunk 55 is unused)
+constexpr int HAND_FLOATS = 224;
+constexpr int hand_link(int b) { return 2 * b; }  // the first of link b's two chunks
+constexpr int HAND_ROOT_VEL = 48, HAND_FORCE_AT = 1, HAND_BALL = 50, HAND_BALL_CHUNKS = 4, HAND_TORQUE = 54;
+static_assert(hand_link(NB - 1) + 1 < HAND_ROOT_VEL && HAND_ROOT_VEL + 1 < HAND_BALL && HAND_BALL + HAND_BALL_CHUNKS <= HAND_TORQUE, "hand-over chunks overlap");
+static_assert(HAND_TORQUE < HAND_FLOATS / 4, "the hand-over record's last chunk lies outside it");
 constexpr int CT_PD = 0, CT_FORCE = NDOF, CT_TORQUE = NDOF + 3, CTRL_SLOTS = NDOF + 6;
 // physics outputs (SoA): rigid-body state 24x13, dof_pos 69, contact force 72, dof force 69
 constexpr int OUT_RB = 0, OUT_DOF_POS = NB * 13, OUT_CONTACT = OUT_DOF_POS + NDOF, OUT_DOF_FORCE = OUT_CONTACT + NB * 3,
