@@ -629,6 +629,68 @@ int v2p_tennis_task_step(const v2p_tennis_cfg* cfg, int64_t n, const v2p_tennis_
 int v2p_tennis_task_obs(const v2p_tennis_cfg* cfg, int64_t num_envs, const v2p_tennis_buffers* buffers, const int64_t* env_ids, int64_t n_ids,
                         void* stream);
 
+/* ---- the MotionVAE motion generator of a control step (vid2player/players/mvae_player.py `MVAEPlayer.step` / `reset` around
+ * motion_vae/model.py:186-252 `MixedDecoder.forward`): the gate, the three expert-blended layers and the player's state update
+ * (`_update_mvae_state`) in ONE launch, without a host synchronisation or an allocation.  The decoder computes every expert and blends
+ * the results, out = sum_e c_e (x W_e + b_e) - the same function as the reference's per-env blended weights - on the fp32-input MFMA,
+ * fp32 throughout.  Only the shipped architecture is built: frame 288, latent 32, hidden 256, 6 experts, gate 64, 1 condition frame,
+ * 1 prediction, predicted phase; the feature layout is root pos 0:3, root vel 3:6, joint pos 6:75, joint vel 75:144, rot6d 144:288.
+ * Stateless like v2p_tennis_task_step: every buffer is the caller's. */
+enum { V2P_MVAE_PLAYER_DJOKOVIC = 0, V2P_MVAE_PLAYER_FEDERER = 1, V2P_MVAE_PLAYER_NADAL = 2 };
+#define V2P_MVAE_FRAME 288
+#define V2P_MVAE_LATENT 32
+#define V2P_MVAE_HIDDEN 256
+#define V2P_MVAE_EXPERTS 6
+#define V2P_MVAE_GATE 64
+typedef struct {
+    int32_t frame_size, latent_size, hidden_size, num_experts, gate_hidden_size; /* 288, 32, 256, 6, 64: anything else is refused */
+    int32_t num_condition_frames, num_future_predictions, predict_phase;         /* 1, 1, 1 */
+    int32_t player;            /* V2P_MVAE_PLAYER_*: whose residual-DoF windows and base angles (mvae_player.py:306-408) */
+    int32_t righthand;         /* the playing hand: elbow / wrist of the residual, the swing-type numbers, the racket's FK chain */
+    int32_t is_train;          /* 0: residuals outside swings are zeroed, and joint_rot is written */
+    int32_t add_residual_dof;  /* 1 ('euler'): v2p_mvae_step takes a residual */
+} v2p_mvae_cfg;
+/* DEVICE pointers.  The matrices are REPACKED (vid2player3d_amd/mvae.py `pack_matrix`): a stack W[E][K][N] (y = x W) becomes
+ * [E][ceil(N/32)][K/8][64][4], element q of lane l of column tile t, k-group g being W[e][8g + 2q + (l>>5)][32t + (l&31)] (0 past column
+ * N) - what lane l feeds to four consecutive 32x32x2 MFMAs as one 16-byte load; biases are padded with zeros to a multiple of 32
+ * columns.  The gate's three Linear layers (torch weight [out,in]) are packed as one-expert stacks of their transposes. */
+typedef struct {
+    const float *w0, *b0;            /* [6][320][256] packed, [6][256] */
+    const float *w1, *b1;            /* [6][288][256] packed, [6][256] */
+    const float *w2, *b2;            /* [6][288][290] packed (10 tiles), [6][320] */
+    const float *gate_w0, *gate_b0;  /* [1][320][64] packed, [64] */
+    const float *gate_w1, *gate_b1;  /* [1][64][64] packed, [64] */
+    const float *gate_w2, *gate_b2;  /* [1][64][6] packed (1 tile), [32] */
+    const float *avg, *std;          /* [288] */
+} v2p_mvae_weights;
+typedef struct {                     /* DEVICE buffers: the player's state under the reference's names */
+    float* conditions;               /* [N,1,288] normalized */
+    float* root_pos;                 /* [N,3] */
+    float* root_vel;                 /* [N,3] */
+    float* joint_rot6d;              /* [N,24,6] */
+    float* joint_rotmat;             /* [N,24,3,3] */
+    float* joint_rot;                /* [N,24,3] angle-axis; written when not training (nullable with is_train) */
+    float* racket_pos;               /* [N,3] written by reset only */
+    float* racket_normal;            /* [N,3] written by reset only */
+    float* phase_pred;               /* [N] */
+    int64_t* swing_type;             /* [N] */
+    int64_t* swing_type_cycle;       /* [N] */
+} v2p_mvae_buffers;
+/* `MVAEPlayer.step(latents, residual)` for envs 0 .. n-1 (:184-190, 221-223, 254-422 with init=False).  residual [n,3] is nullable (no
+ * residual rule then), and refused without add_residual_dof; latents and residual are only read.  Refused before any HIP call
+ * (V2P_ERR_INVALID, a message that names the call): a null struct or required pointer, n < 0, another architecture, an unknown player.
+ * n = 0 is a no-op. */
+int v2p_mvae_step(const v2p_mvae_cfg* cfg, int64_t n, const v2p_mvae_weights* weights, const v2p_mvae_buffers* buffers, const float* latents /*[n,32]*/,
+                  const float* residual /*[n,3], nullable*/, void* stream);
+/* `MVAEPlayer.reset(env_ids)` (:160-165, 212-252, 424-431 with init=True) for env_ids [n_ids] (device; ids outside 0 .. num_envs-1 are
+ * skipped): swing types -1, the condition from init_feature (row i belongs to env_ids[i]), the root position with xy = root_xy (the
+ * caller's draw), rot6d -> rotmat (-> joint_rot when not training), racket head position and normal by the 9-joint FK chain of
+ * utils/racket.py:183-203, 235-269 over joint_pos_bind_rel with the eastern racket vectors (the player builds its Racket without a
+ * grip).  Only avg and std of `weights` are read.  Refusals as v2p_mvae_step. */
+int v2p_mvae_reset(const v2p_mvae_cfg* cfg, int64_t num_envs, const v2p_mvae_weights* weights, const v2p_mvae_buffers* buffers, const int64_t* env_ids,
+                   int64_t n_ids, const float* init_feature /*[n_ids,288]*/, const float* root_xy /*[n_ids,2]*/, const float* joint_pos_bind_rel /*[24,3]*/,
+                   void* stream);
+
 /* measurement: HIP events around every launch of the physics kernel (the dominant kernel of the step), recorded on the launch stream
  * by v2p_env_step / v2p_env_physics between _begin and _end (at most max_launches of them).  _end synchronises the events and returns
  * the summed kernel time in milliseconds and the number of launches measured.  bench.py's roofline.kernel_ms comes from here, from

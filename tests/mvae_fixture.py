@@ -1,0 +1,128 @@
+"""What the motion-generator tests share: the decoder's weights, built from a seed (at 5.7 MB they are not stored), the fixture
+tests/golden/mvae_player.npz (recorded from the reference by tools/gen_golden_mvae_player.py) and the tolerance rule.
+
+The weights come from numpy's PCG64 through `bit_generator.random_raw`, a stream numpy guarantees across versions: 53 bits of every raw
+word make a float64 in [0, 1).  They are scaled so that every layer's pre-activation has a spread near 1 and the gate is peaked (the
+default Kaiming init of a 3-d tensor gives outputs near 0.06 and a flat gate, which would test nothing of the blend).  The fixture carries
+the sha256 of the arrays.
+
+Tolerances are measured, not chosen: the fixture stores, for every compared quantity, `scatter/...` = max |reference in float32 -
+reference in float64|.  The kernel (and the numpy statement) sum the 6 x K products of a layer in another order than the reference does;
+their allowance is ORDER_ALLOWANCE x that scatter - an allowance for ordering, not for precision.  Integers must match exactly.
+"""
+import hashlib
+import math
+import os
+
+import numpy as np
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mvae_player.npz")
+ORDER_ALLOWANCE = 8.0
+WEIGHT_SEED = 20311
+FRAME, LATENT, HIDDEN, EXPERTS, GATE = 288, 32, 256, 6, 64
+VARIANTS = ("A", "B", "C", "D")
+PLAYER_NAMES = ("djokovic", "federer", "nadal")
+FLOAT_STATE = ("conditions", "root_pos", "root_vel", "joint_rot6d", "joint_rotmat", "joint_rot", "phase_pred")
+INT_STATE = ("swing_type", "swing_type_cycle")
+
+
+class _Stream:
+    def __init__(self, seed):
+        self.bits = np.random.PCG64(seed)
+
+    def uniform(self, shape, lo, hi):
+        raw = self.bits.random_raw(int(np.prod(shape)))
+        u = (raw >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+        return (lo + (hi - lo) * u).reshape(shape).astype(np.float32)
+
+
+def seeded_state_dict(seed=WEIGHT_SEED):
+    """A `PoseMixtureVAE` decoder's state dict (float32 arrays under the reference's keys) and avg / std, from a seed."""
+    s = _Stream(seed)
+    sd = {}
+    for i, (K, N) in enumerate(((LATENT + FRAME, HIDDEN), (LATENT + HIDDEN, HIDDEN), (LATENT + HIDDEN, FRAME + 2))):
+        a = 1.3 * math.sqrt(3.0 / K)
+        sd["decoder.w%d" % i] = s.uniform((EXPERTS, K, N), -a, a)
+        sd["decoder.b%d" % i] = s.uniform((EXPERTS, N), -0.2, 0.2)
+    # (the two phase columns listen to the latent four times as much: a latent can then steer the phase into every window of the residual rule)
+    sd["decoder.w2"][:, :LATENT, FRAME:] *= np.float32(4.0)
+    for i, (K, N, gain) in enumerate(((LATENT + FRAME, GATE, 1.0), (GATE, GATE, 1.5), (GATE, EXPERTS, 4.0))):
+        a = gain * math.sqrt(3.0 / K)
+        sd["decoder.gate.%d.weight" % (2 * i)] = s.uniform((N, K), -a, a)
+        sd["decoder.gate.%d.bias" % (2 * i)] = s.uniform((N,), -0.1, 0.1)
+    avg = s.uniform((FRAME,), -0.5, 0.5)
+    avg[0:3] = [0.0, -12.0, 0.9]
+    std = s.uniform((FRAME,), 0.5, 1.5)
+    std[3:6] = s.uniform((3,), 0.02, 0.05)  # (a root velocity per frame: the player stays near the baseline)
+    return sd, avg, std
+
+
+def weights_sha256(sd, avg, std):
+    h = hashlib.sha256()
+    for k in sorted(sd):
+        h.update(k.encode() + b"\0" + np.ascontiguousarray(sd[k], dtype=np.float32).tobytes())
+    h.update(np.ascontiguousarray(avg, dtype=np.float32).tobytes() + np.ascontiguousarray(std, dtype=np.float32).tobytes())
+    return h.hexdigest()
+
+
+_cache = {}
+
+
+def golden():
+    if "g" not in _cache:
+        with np.load(GOLDEN) as z:
+            _cache["g"] = {k: z[k] for k in z.files}
+    return _cache["g"]
+
+
+def weights():
+    """(weights dict under the names of v2p_mvae_weights, avg, std), built once."""
+    if "w" not in _cache:
+        from vid2player3d_amd import mvae
+
+        sd, avg, std = seeded_state_dict()
+        _cache["w"] = (mvae.weights_from_state_dict(sd), avg, std)
+    return _cache["w"]
+
+
+def settings(g, v):
+    """player_settings of variant v: `<v>/settings` = [player, righthand, is_train]."""
+    from vid2player3d_amd import mvae
+
+    p, rh, train = (int(x) for x in g[v + "/settings"])
+    return mvae.player_settings({"player": PLAYER_NAMES[p], "righthand": bool(rh), "add_residual_dof": "euler"}, bool(train))
+
+
+def state_before(g, v, t):
+    """The player's state before step t of variant v (what the step reads; the tensors it only writes are absent)."""
+    return {k: g["%s/traj/%s" % (v, k)][t] for k in ("conditions", "root_pos", "swing_type", "swing_type_cycle")}
+
+
+def state_after(g, v, t):
+    o = {k: g["%s/traj/%s" % (v, k)][t + 1] for k in ("conditions", "root_pos", "swing_type", "swing_type_cycle")}
+    o.update({k: g["%s/post/%s" % (v, k)][t] for k in ("root_vel", "joint_rot6d", "joint_rotmat", "phase_pred")})
+    if ("%s/post/joint_rot" % v) in g:
+        o["joint_rot"] = g["%s/post/joint_rot" % v][t]
+    return o
+
+
+def assert_state(got, want, scatter, what, rows=None):
+    """Every float array of `want` within ORDER_ALLOWANCE x its scatter of `got`, every integer array equal; prints each figure first."""
+    for k, w in want.items():
+        a = np.asarray(got[k]).reshape(np.asarray(w).shape)
+        if rows is not None:
+            a, w = a[rows], w[rows]
+        if np.asarray(w).dtype.kind in "iub":
+            assert np.array_equal(a, w), "%s: %s differs: %s != %s" % (what, k, a.ravel()[:16], np.asarray(w).ravel()[:16])
+            continue
+        tol = ORDER_ALLOWANCE * float(scatter[k])
+        err = float(np.abs(a.astype(np.float64) - np.asarray(w, dtype=np.float64)).max()) if a.size else 0.0
+        print("%s: %s max |difference| %.3g, allowance %.3g" % (what, k, err, tol))
+        assert np.isfinite(a).all(), "%s: %s is not finite" % (what, k)
+        assert err <= tol, "%s: %s differs by %.3g > %g x scatter %.3g" % (what, k, err, ORDER_ALLOWANCE, float(scatter[k]))
+
+
+def scatter_of(g, kind):
+    """The recorded scatter of every quantity: kind 'step' (one teacher-forced step), 'free' (the free-running sequence) or 'reset'."""
+    p = "scatter/%s/" % kind
+    return {k[len(p):]: float(v) for k, v in g.items() if k.startswith(p)}

@@ -110,6 +110,25 @@ class TennisBuffers(C.Structure):
     _fields_ = [(k, vp) for k in TENNIS_BUFFER_NAMES]
 
 
+class MvaeCfg(C.Structure):
+    """v2p_mvae_cfg: sizes and switches of the MotionVAE motion generator (v2p_mvae_step / _reset)."""
+    _fields_ = [(k, C.c_int32) for k in ("frame_size", "latent_size", "hidden_size", "num_experts", "gate_hidden_size", "num_condition_frames", "num_future_predictions",
+                                         "predict_phase", "player", "righthand", "is_train", "add_residual_dof")]
+
+
+MVAE_WEIGHT_NAMES = ("w0", "b0", "w1", "b1", "w2", "b2", "gate_w0", "gate_b0", "gate_w1", "gate_b1", "gate_w2", "gate_b2", "avg", "std")
+MVAE_BUFFER_NAMES = ("conditions", "root_pos", "root_vel", "joint_rot6d", "joint_rotmat", "joint_rot", "racket_pos", "racket_normal", "phase_pred", "swing_type",
+                     "swing_type_cycle")
+
+
+class MvaeWeights(C.Structure):
+    _fields_ = [(k, vp) for k in MVAE_WEIGHT_NAMES]
+
+
+class MvaeBuffers(C.Structure):
+    _fields_ = [(k, vp) for k in MVAE_BUFFER_NAMES]
+
+
 class ContextTransform(C.Structure):
     _fields_ = [("num_ops", C.c_int32), ("ops", C.c_int32 * 3), ("mask_joints", C.c_uint32), ("noise_prob", C.c_float), ("noise_std", C.c_float),
                 ("conf_std", C.c_float), ("min_conf", C.c_float), ("drop_prob", C.c_float)]
@@ -180,6 +199,8 @@ def load():
         "v2p_ball_rollout": [C.POINTER(BallSim), C.c_int64, vp, vp, vp, C.POINTER(BallRolloutOut), vp],
         "v2p_tennis_task_step": [C.POINTER(TennisCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(C.c_char_p), vp],
         "v2p_tennis_task_obs": [C.POINTER(TennisCfg), C.c_int64, C.POINTER(TennisBuffers), vp, C.c_int64, vp],
+        "v2p_mvae_step": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, vp, vp],
+        "v2p_mvae_reset": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, C.c_int64, vp, vp, vp, vp],
         "v2p_env_profile_begin": [vp, C.c_int64],
         "v2p_env_profile_begin_sampled": [vp, C.c_int64, C.c_int32, C.c_int32],
         "v2p_env_profile_end": [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)],
@@ -199,7 +220,7 @@ def load():
 EXPORTED_SYMBOLS = (
     "v2p_model_create", "v2p_model_destroy", "v2p_mlib_create", "v2p_mlib_destroy", "v2p_motion_state", "v2p_reward", "v2p_reset_flags",
     "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_obs_imitation_packed_w", "v2p_policy_head_w", "v2p_policy_head_record_w", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_set_context_transform", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
-    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_last_error", "v2p_abi_version",
+    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_mvae_step", "v2p_mvae_reset", "v2p_last_error", "v2p_abi_version",
 )
 
 

@@ -7,6 +7,7 @@
 
 #include <new>
 
+#include "mvae_player.hpp"
 #include "tennis_task.hpp"
 #include "v2p_internal.hpp"
 
@@ -293,6 +294,48 @@ int v2p_tennis_task_obs(const v2p_tennis_cfg* c, int64_t num_envs, const v2p_ten
     if (num_envs < 0 || (n_ids > 0 && !env_ids)) { set_error("v2p_tennis_task_obs: num_envs %lld < 0 or null env_ids", (long long)num_envs); return V2P_ERR_INVALID; }
     if (n_ids == 0 || num_envs == 0) return V2P_OK;
     return launch_tennis_task_obs(*c, num_envs, *b, env_ids, n_ids, (hipStream_t)stream);
+}
+
+// what both motion-generator entry points refuse; `step`: the decoder's weights are required too
+static int mvae_check(const char* fn, const v2p_mvae_cfg* c, int64_t n, const v2p_mvae_weights* w, const v2p_mvae_buffers* b, bool step) {
+    if (!c || !w || !b) { set_error("%s: null cfg / weights / buffers", fn); return V2P_ERR_INVALID; }
+    if (n < 0) { set_error("%s: n %lld < 0", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (c->frame_size != V2P_MVAE_FRAME || c->latent_size != V2P_MVAE_LATENT || c->hidden_size != V2P_MVAE_HIDDEN || c->num_experts != V2P_MVAE_EXPERTS ||
+        c->gate_hidden_size != V2P_MVAE_GATE || c->num_condition_frames != 1 || c->num_future_predictions != 1 || c->predict_phase != 1) {
+        set_error("%s: only the shipped architecture is built (frame 288, latent 32, hidden 256, 6 experts, gate 64, 1 condition frame, 1 prediction, predicted phase); "
+                  "got frame %d, latent %d, hidden %d, %d experts, gate %d, %d condition frames, %d predictions, predict_phase %d", fn, c->frame_size, c->latent_size,
+                  c->hidden_size, c->num_experts, c->gate_hidden_size, c->num_condition_frames, c->num_future_predictions, c->predict_phase);
+        return V2P_ERR_INVALID;
+    }
+    if (c->player < V2P_MVAE_PLAYER_DJOKOVIC || c->player > V2P_MVAE_PLAYER_NADAL) { set_error("%s: unknown player %d", fn, c->player); return V2P_ERR_INVALID; }
+    bool ok = w->avg && w->std && b->conditions && b->root_pos && b->root_vel && b->joint_rot6d && b->joint_rotmat && b->phase_pred && b->swing_type && b->swing_type_cycle &&
+              (c->is_train || b->joint_rot);
+    if (step) ok = ok && w->w0 && w->b0 && w->w1 && w->b1 && w->w2 && w->b2 && w->gate_w0 && w->gate_b0 && w->gate_w1 && w->gate_b1 && w->gate_w2 && w->gate_b2;
+    else ok = ok && b->racket_pos && b->racket_normal;
+    if (!ok) { set_error("%s: null weight / buffer", fn); return V2P_ERR_INVALID; }
+    return V2P_OK;
+}
+
+int v2p_mvae_step(const v2p_mvae_cfg* c, int64_t n, const v2p_mvae_weights* w, const v2p_mvae_buffers* b, const float* latents, const float* residual, void* stream) {
+    const int rc = mvae_check("v2p_mvae_step", c, n, w, b, true);
+    if (rc != V2P_OK) return rc;
+    if (n > 0 && !latents) { set_error("v2p_mvae_step: null latents"); return V2P_ERR_INVALID; }
+    if (residual && !c->add_residual_dof) { set_error("v2p_mvae_step: a residual without add_residual_dof"); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    return launch_mvae_step(*c, n, *w, *b, latents, residual, (hipStream_t)stream);
+}
+
+int v2p_mvae_reset(const v2p_mvae_cfg* c, int64_t num_envs, const v2p_mvae_weights* w, const v2p_mvae_buffers* b, const int64_t* env_ids, int64_t n_ids,
+                   const float* init_feature, const float* root_xy, const float* joint_pos_bind_rel, void* stream) {
+    const int rc = mvae_check("v2p_mvae_reset", c, n_ids, w, b, false);
+    if (rc != V2P_OK) return rc;
+    if (num_envs < 0) { set_error("v2p_mvae_reset: num_envs %lld < 0", (long long)num_envs); return V2P_ERR_INVALID; }
+    if (n_ids > 0 && (!env_ids || !init_feature || !root_xy || !joint_pos_bind_rel)) {
+        set_error("v2p_mvae_reset: null env_ids / init_feature / root_xy / joint_pos_bind_rel");
+        return V2P_ERR_INVALID;
+    }
+    if (n_ids == 0 || num_envs == 0) return V2P_OK;
+    return launch_mvae_reset(*c, num_envs, *w, *b, env_ids, n_ids, init_feature, root_xy, joint_pos_bind_rel, (hipStream_t)stream);
 }
 
 int v2p_env_reset(v2p_env* e, const int64_t* env_ids, int64_t n, const float* motion_times, void* stream) {

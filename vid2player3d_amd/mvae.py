@@ -1,0 +1,405 @@
+"""The MotionVAE motion generator on the device (vid2player/players/mvae_player.py `MVAEPlayer`, around the mixture-of-experts decoder
+of vid2player/motion_vae/model.py:186-252).
+
+One control step - the gate, the three expert-blended layers and the player's state update (`_update_mvae_state`) - is ONE kernel launch,
+`v2p_mvae_step` (csrc/mvae_player.hip); `reset(env_ids)` is `v2p_mvae_reset`.  The decoder computes every expert and blends the results,
+out = sum_e c_e (x W_e + b_e), which is the function the reference computes by blending the weights per env; fp32 throughout (the
+reference runs the decoder under autocast on CUDA - a reduced-precision path is not built).  Only the shipped architecture
+is built: frame 288, latent 32, hidden 256, 6 experts, gate 64, one condition frame, one prediction, predicted phase; dual mode is not.
+
+`mvae_step_reference` / `mvae_reset_reference` are the numpy statement of the same two calls on arrays - the checker of the tests, as
+`tennis_controller.task_step_reference` is for the task step; the product never calls them.  There is no CPU path: a CPU device or a
+missing library is a RuntimeError.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+FRAME, LATENT, HIDDEN, EXPERTS, GATE = 288, 32, 256, 6, 64
+OUT = FRAME + 2  # the feature and the two phase numbers
+NUM_JOINTS = 24
+COL_ROOT_VEL, COL_JOINT_POS, COL_ROT6D = 3, 6, 144  # mvae_player.py:77-90 with the full root position
+PLAYERS = {"djokovic": 0, "federer": 1, "nadal": 2}
+LELBOW, RELBOW, LWRIST, RWRIST = 18, 19, 20, 21  # utils/pose.py
+RACKET_CHAIN = {True: (0, 3, 6, 9, 14, 17, 19, 21, 23), False: (0, 3, 6, 9, 13, 16, 18, 20, 22)}  # utils/racket.py:152-161
+RACKET_LENGTHS = (0.2, 0.15, 0.15)  # handle, shaft, head radius of the eastern tennis racket (utils/racket.py:10-19)
+STATE_NAMES = _lib.MVAE_BUFFER_NAMES
+WEIGHT_KEYS = ("w0", "b0", "w1", "b1", "w2", "b2", "gate_w0", "gate_b0", "gate_w1", "gate_b1", "gate_w2", "gate_b2")
+# the residual-DoF rule (mvae_player.py:306-408).  A row: (swing type, lo, hi, lo inclusive, {base angle: value}); envs of that swing
+# type whose phase lies in (lo, hi) get the base angles, rows applied in order.  "swings": the forehand and backhand windows outside of
+# which a residual is zeroed when not training.  Angles in units of pi: elbow twist, wrist twist, wrist shake, wrist swing.
+RESIDUAL_RULES = {
+    "djokovic": dict(rows=((1, 2.0, 3.2, False, {"elbow": -0.75}), (1, 2.0, 3.1, False, {"swing": -0.25}), (1, 3.1, 3.2, True, {"swing": 0.25}),
+                           (2, 2.0, 3.2, False, {"elbow": -0.25}), (2, 2.0, 3.0, False, {"swing": 0.1})), swings=((2.0, 3.2), (2.0, 3.2))),
+    "federer": dict(rows=((1, 2.0, 3.2, False, {"elbow": -0.5}), (1, 2.0, 3.1, False, {"swing": -0.25}), (1, 3.1, 3.2, True, {"swing": 0.25}),
+                          (2, 2.0, 3.5, False, {"twist": -0.25, "shake": 0.15}), (3, 2.0, 3.5, False, {"twist": -0.1}),
+                          (0, 2.0, 3.3, False, {"twist": -0.5, "shake": 0.1, "elbow": -0.25}), (0, 2.0, 3.0, False, {"swing": -0.5})), swings=((2.0, 3.2), (2.0, 3.5))),
+    "nadal": dict(rows=((1, 2.5, 3.2, False, {"elbow": -0.75, "swing": 0.25}), (2, 2.0, 3.5, False, {"twist": -0.4}), (2, 2.0, 3.0, False, {"swing": -0.25})),
+                  swings=((2.5, 3.2), (2.0, 3.5))),
+}
+
+
+def player_settings(cfg, is_train):
+    """What both the kernel's v2p_mvae_cfg and the numpy statement are made from.  cfg: the reference's cfg_v2p keys `player`, `righthand`,
+    `add_residual_dof` (and, refused when they ask for what is not built: `dual_mode`, `predict_phase`, the sizes of another option set)."""
+    cfg = dict(cfg)
+    if cfg.get("dual_mode"):
+        raise NotImplementedError("MotionVAEPlayer: dual_mode is not built")
+    if cfg.get("player") not in PLAYERS:
+        raise ValueError("MotionVAEPlayer: cfg player %r is none of %s" % (cfg.get("player"), sorted(PLAYERS)))
+    if cfg.get("add_residual_dof") not in (None, False, "euler"):
+        raise ValueError("MotionVAEPlayer: add_residual_dof %r (only 'euler' exists)" % (cfg.get("add_residual_dof"),))
+    sizes = dict(frame_size=FRAME, latent_size=LATENT, hidden_size=HIDDEN, num_experts=EXPERTS, gate_hidden_size=GATE, num_condition_frames=1,
+                 num_future_predictions=1, predict_phase=True)
+    for k, v in sizes.items():
+        if cfg.get(k, v) != v:
+            raise NotImplementedError("MotionVAEPlayer: only the shipped architecture is built (%s); got %s = %r" % (", ".join("%s %s" % kv for kv in sizes.items()), k, cfg[k]))
+    return dict(player=cfg["player"], righthand=bool(cfg.get("righthand", True)), is_train=bool(is_train), add_residual_dof=bool(cfg.get("add_residual_dof")))
+
+
+def cfg_struct(st):
+    return _lib.MvaeCfg(frame_size=FRAME, latent_size=LATENT, hidden_size=HIDDEN, num_experts=EXPERTS, gate_hidden_size=GATE, num_condition_frames=1,
+                        num_future_predictions=1, predict_phase=1, player=PLAYERS[st["player"]], righthand=int(st["righthand"]), is_train=int(st["is_train"]),
+                        add_residual_dof=int(st["add_residual_dof"]))
+
+
+# ------------------------------------------------------------------------------------------------------------------ weights
+def weights_from_state_dict(sd):
+    """The decoder's arrays out of a `PoseMixtureVAE` state dict (a mapping of names to tensors or arrays; no pickle of reference classes
+    is read): decoder.w0..w2 [6,K,N], decoder.b0..b2 [6,N], decoder.gate.{0,2,4}.{weight,bias}.  Returns a dict of float32 arrays under the
+    names of v2p_mvae_weights, in the reference's layouts."""
+    def get(k):
+        if k not in sd:
+            raise KeyError("weights_from_state_dict: the state dict has no %r" % k)
+        v = sd[k]
+        return np.ascontiguousarray((v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)), dtype=np.float32)
+
+    w = {}
+    shapes = {"w0": (EXPERTS, LATENT + FRAME, HIDDEN), "w1": (EXPERTS, LATENT + HIDDEN, HIDDEN), "w2": (EXPERTS, LATENT + HIDDEN, OUT), "b0": (EXPERTS, HIDDEN),
+              "b1": (EXPERTS, HIDDEN), "b2": (EXPERTS, OUT), "gate_w0": (GATE, LATENT + FRAME), "gate_b0": (GATE,), "gate_w1": (GATE, GATE), "gate_b1": (GATE,),
+              "gate_w2": (EXPERTS, GATE), "gate_b2": (EXPERTS,)}
+    for i in range(3):
+        w["w%d" % i], w["b%d" % i] = get("decoder.w%d" % i), get("decoder.b%d" % i)
+        w["gate_w%d" % i], w["gate_b%d" % i] = get("decoder.gate.%d.weight" % (2 * i)), get("decoder.gate.%d.bias" % (2 * i))
+    for k, shape in shapes.items():
+        if w[k].shape != shape:
+            raise ValueError("weights_from_state_dict: %s has shape %s, the shipped architecture needs %s" % (k, w[k].shape, shape))
+    return w
+
+
+def pack_matrix(W):
+    """A stack W[E,K,N] (y = x W) in the layout the kernel reads (v2p_rollout.h, v2p_mvae_weights): [E, ceil(N/32), K/8, 64, 4]."""
+    W = np.asarray(W, dtype=np.float32)
+    E, K, N = W.shape
+    T = (N + 31) // 32
+    P = np.zeros((E, K, T * 32), np.float32)
+    P[:, :, :N] = W
+    # k = 8g + 2q + h, column = 32t + c, lane = 32h + c  ->  [e, t, g, h, c, q]
+    P = P.reshape(E, K // 8, 4, 2, T, 32).transpose(0, 4, 1, 3, 5, 2)
+    return np.ascontiguousarray(P).reshape(E, T, K // 8, 64, 4)
+
+
+def pack_bias(b):
+    b = np.atleast_2d(np.asarray(b, dtype=np.float32))
+    out = np.zeros((b.shape[0], (b.shape[1] + 31) // 32 * 32), np.float32)
+    out[:, :b.shape[1]] = b
+    return out
+
+
+def pack_weights(w, avg, std, device):
+    """Device tensors under the names of v2p_mvae_weights, made once at load time."""
+    t = {}
+    for i in range(3):
+        t["w%d" % i], t["b%d" % i] = pack_matrix(w["w%d" % i]), pack_bias(w["b%d" % i])
+        t["gate_w%d" % i], t["gate_b%d" % i] = pack_matrix(np.asarray(w["gate_w%d" % i], dtype=np.float32).T[None]), pack_bias(w["gate_b%d" % i])
+    t["avg"], t["std"] = np.asarray(avg, dtype=np.float32).reshape(FRAME), np.asarray(std, dtype=np.float32).reshape(FRAME)
+    return {k: torch.from_numpy(np.ascontiguousarray(v)).to(device).contiguous() for k, v in t.items()}
+
+
+# ------------------------------------------------------------------------------------------------------------------ the checker
+def _elu(x):
+    return np.where(x > 0, x, np.expm1(np.minimum(x, 0)))
+
+
+def decoder_reference(w, z, c, dt=np.float32, probes=None):
+    """`MixedDecoder.forward(z, c)` in the form the kernel computes: every expert, then the blend.  Returns [n, 290]."""
+    A = lambda k: np.asarray(w[k], dtype=dt)
+    z, c = np.asarray(z, dtype=dt), np.asarray(c, dtype=dt)
+    x = np.concatenate([z, c], 1)
+    g = _elu(x @ A("gate_w0").T + A("gate_b0"))
+    g = _elu(g @ A("gate_w1").T + A("gate_b1"))
+    g = g @ A("gate_w2").T + A("gate_b2")
+    ex = np.exp(g - g.max(1, keepdims=True))
+    coef = ex / ex.sum(1, keepdims=True)
+    h = c
+    for i in range(3):
+        x = np.concatenate([z, h], 1)
+        W, b = A("w%d" % i), A("b%d" % i)
+        y = np.zeros((len(x), W.shape[2]), dt)
+        for e in range(EXPERTS):
+            y = y + coef[:, e:e + 1] * (x @ W[e] + b[e])
+        if probes is not None:
+            probes["pre%d" % i] = y
+        h = _elu(y) if i < 2 else y
+    if probes is not None:
+        probes["coef"] = coef
+    return h.astype(dt)
+
+
+def _norm(v):
+    return np.sqrt((v * v).sum(-1))
+
+
+def rot6d_to_rotmat_reference(r6, dt=np.float32, probes=None):
+    """rot6d_to_rotmat (utils/torch_transform.py:221-235): [..., 6] -> [..., 3, 3], columns b1 b2 b3."""
+    r6 = np.asarray(r6, dtype=dt)
+    a1, a2 = r6[..., :3].copy(), r6[..., 3:].copy()
+    small = _norm(a1) < dt(1e-8)
+    if probes is not None:
+        probes.setdefault("rot6d_norm", []).append(_norm(a1).ravel())
+    a1[small] = np.array([1, 0, 0], dt)
+    b1 = a1 / np.maximum(_norm(a1), dt(1e-9))[..., None]
+    u = a2 - (b1 * a2).sum(-1)[..., None] * b1
+    b2 = u / np.maximum(_norm(u), dt(1e-9))[..., None]
+    small = _norm(b2) < dt(1e-8)
+    if probes is not None:
+        probes.setdefault("rot6d_norm", []).append(_norm(u).ravel())
+    b2[small] = np.array([0, 1, 0], dt)
+    return np.stack([b1, b2, np.cross(b1, b2)], -1)
+
+
+def _szd(num, den, dt):
+    den = np.where(np.abs(den) < dt(1e-6), den + dt(1e-6), den)
+    return num / den
+
+
+def rotmat_to_angle_axis_reference(m, dt=np.float32, probes=None):
+    """rotation_matrix_to_angle_axis (utils/konia_transform.py:631-655, through the wxyz quaternion): [..., 3, 3] -> [..., 3]."""
+    m = np.asarray(m, dtype=dt)
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = [m[..., i, j] for i in range(3) for j in range(3)]
+    one, two, eps = dt(1), dt(2), dt(1e-6)
+    trace = m00 + m11 + m22
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sq = np.sqrt(np.maximum(trace + one, eps)) * two
+        c0 = np.stack([dt(0.25) * sq, _szd(m21 - m12, sq, dt), _szd(m02 - m20, sq, dt), _szd(m10 - m01, sq, dt)], -1)
+        sq = np.sqrt(np.maximum(one + m00 - m11 - m22, eps)) * two
+        c1 = np.stack([_szd(m21 - m12, sq, dt), dt(0.25) * sq, _szd(m01 + m10, sq, dt), _szd(m02 + m20, sq, dt)], -1)
+        sq = np.sqrt(np.maximum(one + m11 - m00 - m22, eps)) * two
+        c2 = np.stack([_szd(m02 - m20, sq, dt), _szd(m01 + m10, sq, dt), dt(0.25) * sq, _szd(m12 + m21, sq, dt)], -1)
+        sq = np.sqrt(np.maximum(one + m22 - m00 - m11, eps)) * two
+        c3 = np.stack([_szd(m10 - m01, sq, dt), _szd(m02 + m20, sq, dt), _szd(m12 + m21, sq, dt), dt(0.25) * sq], -1)
+        q = np.where((trace > 0)[..., None], c0, np.where(((m00 > m11) & (m00 > m22))[..., None], c1, np.where((m11 > m22)[..., None], c2, c3)))
+        w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+        s2 = x * x + y * y + z * z
+        s = np.sqrt(np.maximum(s2, eps))
+        two_theta = two * np.where(w < 0, np.arctan2(-s, -w), np.arctan2(s, w))  # (s >= 1e-3: torch_safe_atan2 never shifts)
+        k = np.where(s2 > 0, _szd(two_theta, s, dt), two)
+    if probes is not None:
+        tp = trace <= 0
+        probes.setdefault("trace", []).append(trace.ravel())
+        probes.setdefault("diagonal", []).extend([(m00 - m11)[tp].ravel(), (m00 - m22)[tp].ravel(), (m11 - m22)[tp].ravel()])
+        probes.setdefault("quat_w", []).append(w.ravel())
+        probes.setdefault("sin2", []).append(s2.ravel())
+    return (q[..., 1:] * k[..., None]).astype(dt)
+
+
+def angle_axis_to_rotmat_reference(aa, dt=np.float32, probes=None):
+    """angle_axis_to_rotation_matrix (utils/konia_transform.py:282-333): [..., 3] -> [..., 3, 3]."""
+    aa = np.asarray(aa, dtype=dt)
+    rx, ry, rz = aa[..., 0], aa[..., 1], aa[..., 2]
+    theta2 = rx * rx + ry * ry + rz * rz
+    eps, one = dt(1e-6), dt(1)
+    theta = np.sqrt(np.maximum(theta2, eps))
+    wx, wy, wz = rx / (theta + eps), ry / (theta + eps), rz / (theta + eps)
+    c, s = np.cos(theta), np.sin(theta)
+    t = one - c
+    normal = np.stack([c + wx * wx * t, wx * wy * t - wz * s, wy * s + wx * wz * t, wz * s + wx * wy * t, c + wy * wy * t, -wx * s + wy * wz * t,
+                       -wy * s + wx * wz * t, wx * s + wy * wz * t, c + wz * wz * t], -1)
+    o = np.ones_like(rx)
+    taylor = np.stack([o, -rz, ry, rz, o, -rx, -ry, rx, o], -1)
+    if probes is not None:
+        probes.setdefault("theta2", []).append(theta2.ravel())
+    return np.where((theta2 > eps)[..., None], normal, taylor).reshape(aa.shape[:-1] + (3, 3)).astype(dt)
+
+
+def _residual_bases(st, phase, swing, dt):
+    rule = RESIDUAL_RULES[st["player"]]
+    base = {k: np.zeros(len(phase), dt) for k in ("elbow", "twist", "shake", "swing")}
+    for s, lo, hi, ge, values in rule["rows"]:
+        m = (swing == s) & ((phase >= dt(lo)) if ge else (phase > dt(lo))) & (phase < dt(hi))
+        for k, v in values.items():
+            base[k][m] = dt(v)
+    (f0, f1), (b0, b1) = rule["swings"]
+    swings = ((swing == 1) & (phase > dt(f0)) & (phase < dt(f1))) | ((swing == 2) & (phase > dt(b0)) & (phase < dt(b1)))
+    return base, swings
+
+
+def mvae_step_reference(st, w, avg, std, s, latents, residual=None, dt=np.float32, probes=None):
+    """`MVAEPlayer.step(latents, residual)` on arrays: the decoder, then `_update_mvae_state(init=False)` (mvae_player.py:184-190, 221-223,
+    254-422).  st: player_settings(...); s: the state before the step under the names of v2p_mvae_buffers.  Returns a dict with every
+    array the step writes; nothing in `s` is modified.  dt = numpy.float64 evaluates the same statement in double precision; `probes`
+    (a dict) receives the floats that are compared with a threshold."""
+    avg, std = np.asarray(avg, dtype=dt).reshape(FRAME), np.asarray(std, dtype=dt).reshape(FRAME)
+    n = len(latents)
+    cond = np.asarray(s["conditions"], dtype=dt).reshape(n, FRAME)
+    out = decoder_reference(w, latents, cond, dt, probes)
+    norm, ph2 = out[:, :FRAME], out[:, FRAME:]
+    feat = norm * std + avg
+    o = {}
+    vel = feat[:, COL_ROOT_VEL:COL_ROOT_VEL + 3]
+    root = np.asarray(s["root_pos"], dtype=dt) + vel
+    cond = norm.copy()
+    cond[:, :3] = (root - avg[:3]) / std[:3]
+    r6 = feat[:, COL_ROT6D:].reshape(n, NUM_JOINTS, 6).copy()
+    rotmat = rot6d_to_rotmat_reference(r6, dt, probes)
+    phase = np.arctan2(ph2[:, 0], ph2[:, 1])
+    if probes is not None:
+        probes["atan2"] = phase.copy()
+    phase = np.where(phase < 0, phase + dt(math.pi * 2), phase).astype(dt)
+    swing, cycle = np.array(s["swing_type"], dtype=np.int64), np.array(s["swing_type_cycle"], dtype=np.int64)
+    wrist_x = feat[:, COL_JOINT_POS + (RWRIST - 1) * 3]  # the RIGHT wrist, whatever the hand
+    a, b = (1, 2) if st["righthand"] else (2, 1)
+    swing = np.where((swing == -1) & (phase > dt(2.0)) & (phase < dt(3.5)), np.where(wrist_x > 0, a, b), swing)
+    swing = np.where((swing != -1) & (phase > dt(3.5)), -1, swing)
+    cycle = np.where(swing != -1, swing, cycle)
+    if probes is not None:
+        probes["phase"], probes["wrist_x"] = phase, wrist_x
+    if residual is not None and len(residual):
+        res = np.clip(np.asarray(residual, dtype=dt) * dt(0.25), dt(-0.25), dt(0.25))
+        base, swings = _residual_bases(st, phase, swing, dt)
+        if not st["is_train"]:
+            res[~swings] = 0
+        joints = [RELBOW, RWRIST] if st["righthand"] else [LELBOW, LWRIST]
+        aa = rotmat_to_angle_axis_reference(rotmat[:, joints], dt, probes)
+        pi = dt(math.pi)
+        aa[:, 0, 0] = (base["elbow"] + res[:, 0]) * pi
+        aa[:, 1, 0] = base["twist"] * pi
+        aa[:, 1, 1] = (base["shake"] + res[:, 1]) * pi
+        aa[:, 1, 2] = (base["swing"] + res[:, 2]) * pi
+        rotmat[:, joints] = angle_axis_to_rotmat_reference(aa, dt, probes)
+        r6[:, joints] = np.concatenate([rotmat[:, joints][..., 0], rotmat[:, joints][..., 1]], -1)
+    o.update(conditions=cond.reshape(n, 1, FRAME), root_pos=root, root_vel=vel.copy(), joint_rot6d=r6, joint_rotmat=rotmat, phase_pred=phase, swing_type=swing,
+             swing_type_cycle=cycle)
+    if not st["is_train"]:
+        o["joint_rot"] = rotmat_to_angle_axis_reference(rot6d_to_rotmat_reference(r6, dt, probes), dt, probes)
+    return {k: (v.astype(dt) if v.dtype.kind == "f" else v) for k, v in o.items()}
+
+
+def mvae_reset_reference(st, avg, std, s, env_ids, init_feature, root_xy, joint_pos_bind_rel, dt=np.float32, probes=None):
+    """`MVAEPlayer.reset(env_ids)` on arrays (mvae_player.py:160-165, 212-252, 424-431): returns the whole state after the reset, rows of
+    ids outside the batch untouched.  init_feature [len(env_ids), 288], root_xy [len(env_ids), 2] (the caller's draw)."""
+    avg, std = np.asarray(avg, dtype=dt).reshape(FRAME), np.asarray(std, dtype=dt).reshape(FRAME)
+    o = {k: np.array(s[k]) for k in STATE_NAMES if s.get(k) is not None}
+    n = len(o["root_pos"])
+    o["conditions"] = o["conditions"].reshape(n, 1, FRAME)
+    ids = np.asarray(env_ids, dtype=np.int64)
+    keep = (ids >= 0) & (ids < n)
+    ids, f, xy = ids[keep], np.asarray(init_feature, dtype=dt)[keep], np.asarray(root_xy, dtype=dt)[keep]
+    bind = np.asarray(joint_pos_bind_rel, dtype=dt).reshape(NUM_JOINTS, 3)
+    root = np.concatenate([xy, f[:, 2:3]], 1)
+    cond = (f - avg) / std
+    cond[:, :3] = (root - avg[:3]) / std[:3]
+    r6 = f[:, COL_ROT6D:].reshape(-1, NUM_JOINTS, 6)
+    rotmat = rot6d_to_rotmat_reference(r6, dt, probes)
+    # the racket: the chain of transforms Pelvis .. Wrist (utils/racket.py:235-269), the eastern vectors in the wrist's frame
+    chain = RACKET_CHAIN[st["righthand"]]
+    R, p = rotmat[:, chain[0]], np.broadcast_to(bind[chain[0]], (len(ids), 3)).astype(dt)
+    for j in chain[1:8]:
+        p = (R * bind[j]).sum(-1) + p
+        R = R @ rotmat[:, j]
+    direction, normal = -R[:, :, 0], R[:, :, 1]
+    pos = p + root
+    for length in RACKET_LENGTHS:
+        pos = pos + direction * dt(length)
+    o["swing_type"][ids], o["swing_type_cycle"][ids] = -1, -1
+    o["conditions"][ids, 0], o["root_pos"][ids], o["root_vel"][ids] = cond, root, f[:, COL_ROOT_VEL:COL_ROOT_VEL + 3]
+    o["joint_rot6d"][ids], o["joint_rotmat"][ids], o["racket_pos"][ids], o["racket_normal"][ids] = r6, rotmat, pos, normal
+    if not st["is_train"]:
+        o["joint_rot"][ids] = rotmat_to_angle_axis_reference(rotmat, dt, probes)
+    return o
+
+
+# ------------------------------------------------------------------------------------------------------------------ the player
+class MotionVAEPlayer:
+    """`MVAEPlayer` on the device, single player.  Attribute names are the reference's.  cfg: `player`, `righthand`, `add_residual_dof`,
+    `test_mode`; weights: weights_from_state_dict(...); avg, std [288]; init_data [M,1,288] or [M,288] (`vae_init_conditions`: fewer rows
+    than envs repeat the first row, as the reference does); joint_pos_bind_rel [24,3] of the player's SMPL body."""
+
+    def __init__(self, cfg, num_envs, weights, avg, std, init_data, joint_pos_bind_rel, is_train, device):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("MotionVAEPlayer: the motion generator is a HIP kernel - it must live on a GPU (no CPU fallback)")
+        _lib.load()
+        self.cfg, self.num_envs, self.device, self._is_train = dict(cfg), int(num_envs), dev, bool(is_train)
+        self.settings = player_settings(cfg, is_train)
+        self._predict_phase = True
+        n = self.num_envs
+        f, i64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.long, device=dev)
+        self._weights = pack_weights(weights, avg, std, dev)
+        self._avg, self._std = self._weights["avg"], self._weights["std"]
+        init = torch.as_tensor(np.asarray(init_data, dtype=np.float32) if not torch.is_tensor(init_data) else init_data).to(**f)
+        init = init.reshape(len(init), -1, FRAME)[:, -1]
+        self._init_data = (init[:1].repeat(n, 1) if len(init) < n else init[:n]).contiguous()
+        self._joint_pos_bind_rel = torch.as_tensor(np.asarray(joint_pos_bind_rel, dtype=np.float32)).to(**f).reshape(NUM_JOINTS, 3).contiguous()
+        self._conditions = torch.zeros((n, 1, FRAME), **f)
+        self._root_pos, self._root_vel = torch.zeros((n, 3), **f), torch.zeros((n, 3), **f)
+        self._joint_rot6d, self._joint_rotmat = torch.zeros((n, NUM_JOINTS, 6), **f), torch.zeros((n, NUM_JOINTS, 3, 3), **f)
+        self._joint_rot = torch.zeros((n, NUM_JOINTS, 3), **f)
+        self._racket_pos, self._racket_normal = torch.zeros((n, 3), **f), torch.zeros((n, 3), **f)
+        self._phase_pred = torch.zeros(n, **f)
+        self._swing_type = torch.full((n,), -1, **i64)
+        self._swing_type_cycle = self._swing_type.clone()
+        self._latents = None
+        self._cfg_struct = cfg_struct(self.settings)
+        self._weights_struct = _lib.MvaeWeights(**{k: self._weights[k].data_ptr() for k in _lib.MVAE_WEIGHT_NAMES})
+
+    def _buffers(self):
+        # (built per call: `_swing_type_cycle` may have become another task's tensor, TennisControllerTask.attach_motion_generator)
+        t = {k: getattr(self, "_" + k) for k in _lib.MVAE_BUFFER_NAMES}
+        for k, v in t.items():
+            if not v.is_cuda or not v.is_contiguous():
+                raise RuntimeError("MotionVAEPlayer: state tensor _%s must be a contiguous GPU tensor" % k)
+        return _lib.MvaeBuffers(**{k: v.data_ptr() for k, v in t.items()})
+
+    def state_arrays(self):
+        return {k: getattr(self, "_" + k).detach().cpu().numpy().copy() for k in _lib.MVAE_BUFFER_NAMES}
+
+    def draw_root_xy(self, count):
+        """The start of a player near the baseline's centre (mvae_player.py:230-236): a draw, or the centre when evaluating in a test mode
+        other than `random`."""
+        if self._is_train or self.cfg.get("test_mode", "random") == "random":
+            return (torch.rand((count, 2), device=self.device) - 0.5) * torch.tensor([2.0, 1.5], device=self.device) + torch.tensor([0.0, -13.0], device=self.device)
+        return torch.tensor([0.0, -13.0], device=self.device).repeat(count, 1)
+
+    def reset(self, env_ids, root_xy=None):
+        ids = torch.as_tensor(env_ids, device=self.device, dtype=torch.long).contiguous()
+        if ids.numel() == 0:
+            return
+        xy = self.draw_root_xy(ids.numel()) if root_xy is None else torch.as_tensor(root_xy, dtype=torch.float32, device=self.device)
+        xy = xy.to(torch.float32).reshape(ids.numel(), 2).contiguous()
+        feature = self._init_data[ids.clamp(0, self.num_envs - 1)].contiguous()
+        b = self._buffers()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().v2p_mvae_reset(C.byref(self._cfg_struct), self.num_envs, C.byref(self._weights_struct), C.byref(b), _lib.ptr(ids), int(ids.numel()),
+                                                  _lib.ptr(feature), _lib.ptr(xy), _lib.ptr(self._joint_pos_bind_rel), _lib.current_stream(self.device)), "v2p_mvae_reset")
+
+    def step(self, latents, residual=None):
+        if not latents.is_cuda or latents.shape != (self.num_envs, LATENT):
+            raise RuntimeError("MotionVAEPlayer.step: latents must be a GPU tensor [%d, %d]" % (self.num_envs, LATENT))
+        self._latents = latents
+        z = latents.to(torch.float32).contiguous()
+        r = None
+        if residual is not None and len(residual) != 0:
+            if not self.settings["add_residual_dof"]:
+                raise RuntimeError("MotionVAEPlayer.step: a residual needs cfg add_residual_dof = 'euler'")
+            if residual.shape != (self.num_envs, 3):
+                raise RuntimeError("MotionVAEPlayer.step: residual must be [%d, 3]" % self.num_envs)
+            r = residual.to(device=self.device, dtype=torch.float32).contiguous()
+        b = self._buffers()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().v2p_mvae_step(C.byref(self._cfg_struct), self.num_envs, C.byref(self._weights_struct), C.byref(b), _lib.ptr(z), _lib.ptr(r),
+                                                 _lib.current_stream(self.device)), "v2p_mvae_step")
