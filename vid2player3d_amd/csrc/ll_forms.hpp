@@ -60,6 +60,20 @@ struct LlForms {
     // kernels missed their bounds by 1 % and 5 % - cause not found, see docs/NOTES.md B 2026-10-19
     static constexpr bool UPMASK = !LIMITS && !TGS;
 
+    // LAMX: a level of the Lambda recursion by blocks - Lam.B = P Gb - E Gc, M1 = P Ga - E Gb^T, Lam.A = Di + M1 P - Lam.B E^T with
+    // P = aug Di - every entry once, as aug (Di . G) - E . G in seven fused multiply-adds, of the symmetric Lam.A the upper triangle, and
+    // the parent's blocks shifted to the link's origin in fused chains as well.  The earlier form went through H1, H2 = Lam.B^T (the
+    // same nine entries a second time) and all nine entries of t, averaged: 308 float instructions per level against 210.  It does
+    // not keep the earlier form's float32 rounding; every instantiation of both builds runs it: none gains scratch or loses a wave
+    // per SIMD with it (docs/NOTES.md B, 2026-10-20, the arithmetic of the level loops).
+    static constexpr bool LAMX = true;
+
+    // P2SHIFT: pass 2 shifts cA to the parent's origin through the cB it has just formed, two crosses per entry of the upper triangle
+    // instead of t1, t1^T and t2 (274 -> 261 float instructions per level; float32 rounding moves).  The TGS kernels with a ball keep the
+    // earlier form: with BOTH new forms one TGS test of the mixed racket + ball batches missed its position bound by 5 % (each form
+    // alone stays inside it) - cause not found, docs/NOTES.md B, 2026-10-20, the arithmetic of the level loops
+    static constexpr bool P2SHIFT = !(TGS && BALL);
+
     // DIAGX: the split of the sweep's remainder (counters CLOSE_MOVE .. SWEEP_SETUP: closing move, closing pass, head and tail of a visit,
     // set-up) is timed in the default build's diagnostic kernel only: in the register build's it costs 12 B of scratch per lane
     static constexpr bool DIAGX = REGS ? false : DIAG;

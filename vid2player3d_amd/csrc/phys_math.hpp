@@ -13,6 +13,22 @@ __device__ __forceinline__ V3 mul(const Sym3& s, V3 v) {
 }
 __device__ __forceinline__ V3 row(const M3& m, int i) { return V3{m.m[3 * i], m.m[3 * i + 1], m.m[3 * i + 2]}; }
 __device__ __forceinline__ V3 col(const M3& m, int j) { return V3{m.m[j], m.m[3 + j], m.m[6 + j]}; }
+__device__ __forceinline__ V3 row(const Sym3& s, int i) { return i == 0 ? V3{s.xx, s.xy, s.xz} : (i == 1 ? V3{s.xy, s.yy, s.yz} : V3{s.xz, s.yz, s.zz}); }
+// c + s (a.b) - d.e in fused multiply-adds in this written order - two chains of three and the FMA that joins them, seven
+// instructions (six for c = 0) - whatever the relaxed-math flags make of the code around it.  The scale goes on the finished dot: s a
+// rounded entry by entry first costs up to three times the error where the dot cancels (tests/test_lambda_blocks.py)
+__device__ __forceinline__ float scaled_dot_minus_dot(float c, float s, V3 a, V3 b, V3 d, V3 e) {
+    const float t = __builtin_fmaf(-d.z, e.z, __builtin_fmaf(-d.y, e.y, __builtin_fmaf(-d.x, e.x, c)));
+    return __builtin_fmaf(s, __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x)), t);
+}
+__device__ __forceinline__ float scaled_dot_minus_dot(float s, V3 a, V3 b, V3 d, V3 e) {
+    const float t = __builtin_fmaf(-d.z, e.z, __builtin_fmaf(-d.y, e.y, -(d.x * e.x)));
+    return __builtin_fmaf(s, __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x)), t);
+}
+// c + (a x b)_k, two fused multiply-adds
+__device__ __forceinline__ float cross_at_plus(float c, V3 a, V3 b, int k) {
+    return k == 0 ? __builtin_fmaf(a.y, b.z, __builtin_fmaf(-a.z, b.y, c)) : (k == 1 ? __builtin_fmaf(a.z, b.x, __builtin_fmaf(-a.x, b.z, c)) : __builtin_fmaf(a.x, b.y, __builtin_fmaf(-a.y, b.x, c)));
+}
 
 // inverse of a symmetric positive definite 3x3
 __device__ __forceinline__ Sym3 inv(const Sym3& a) {

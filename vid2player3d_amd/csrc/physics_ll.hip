@@ -1049,11 +1049,18 @@ __global__ __launch_bounds__(64 * LL_WPB, (LlForms<LL_BUILD, TGS, DIAG, BALL, LI
                 cB.m[0] = Ba.m[0] + s0.x; cB.m[1] = Ba.m[1] + s1.x; cB.m[2] = Ba.m[2] + s2.x;
                 cB.m[3] = Ba.m[3] + s0.y; cB.m[4] = Ba.m[4] + s1.y; cB.m[5] = Ba.m[5] + s2.y;
                 cB.m[6] = Ba.m[6] + s0.z; cB.m[7] = Ba.m[7] + s1.z; cB.m[8] = Ba.m[8] + s2.z;
-                V3 t10 = cross(r, row(Ba, 0)), t11 = cross(r, row(Ba, 1)), t12 = cross(r, row(Ba, 2));
-                V3 sr0{s0.x, s1.x, s2.x}, sr1{s0.y, s1.y, s2.y}, sr2{s0.z, s1.z, s2.z};
-                V3 t20 = cross(r, sr0), t21 = cross(r, sr1), t22 = cross(r, sr2);
-                cA = Sym3{Aa.xx + 2.f * t10.x + t20.x, Aa.xy + t10.y + t11.x + t20.y, Aa.xz + t10.z + t12.x + t20.z,
-                          Aa.yy + 2.f * t11.y + t21.y, Aa.yz + t11.z + t12.y + t21.z, Aa.zz + 2.f * t12.z + t22.z};
+                if constexpr (F::P2SHIFT) {
+                    // cA = Aa + [r]x Ba^T + cB^T [r]x^T:  cA_ij = Aa_ij + (r x row_i(Ba))_j + (r x row_j(cB))_i, upper triangle; the second
+                    // cross carries [r]x Ca [r]x^T through the cB formed above
+                    auto shifted = [&](float aa, int i, int j) { return cross_at_plus(cross_at_plus(aa, r, row(Ba, i), j), r, row(cB, j), i); };
+                    cA = Sym3{shifted(Aa.xx, 0, 0), shifted(Aa.xy, 0, 1), shifted(Aa.xz, 0, 2), shifted(Aa.yy, 1, 1), shifted(Aa.yz, 1, 2), shifted(Aa.zz, 2, 2)};
+                } else {
+                    V3 t10 = cross(r, row(Ba, 0)), t11 = cross(r, row(Ba, 1)), t12 = cross(r, row(Ba, 2));
+                    V3 sr0{s0.x, s1.x, s2.x}, sr1{s0.y, s1.y, s2.y}, sr2{s0.z, s1.z, s2.z};
+                    V3 t20 = cross(r, sr0), t21 = cross(r, sr1), t22 = cross(r, sr2);
+                    cA = Sym3{Aa.xx + 2.f * t10.x + t20.x, Aa.xy + t10.y + t11.x + t20.y, Aa.xz + t10.z + t12.x + t20.z,
+                              Aa.yy + 2.f * t11.y + t21.y, Aa.yz + t11.z + t12.y + t21.z, Aa.zz + 2.f * t12.z + t22.z};
+                }
                 cC = Ca;
                 cn = pan + cross(r, paf);
                 cf = paf;
@@ -1414,53 +1421,80 @@ __global__ __launch_bounds__(64 * LL_WPB, (LlForms<LL_BUILD, TGS, DIAG, BALL, LI
                         // G = X Lp X^T: Ga = La ; Gb = La [r]x + Lb ; Gc = Lc - [r]x Lb + Gb^T [r]x
                         V3 la0{Lp.A.xx, Lp.A.xy, Lp.A.xz}, la1{Lp.A.xy, Lp.A.yy, Lp.A.yz}, la2{Lp.A.xz, Lp.A.yz, Lp.A.zz};
                         M3 Gb;
-                        {
-                            V3 g0 = cross(la0, r) + row(Lp.B, 0), g1 = cross(la1, r) + row(Lp.B, 1), g2 = cross(la2, r) + row(Lp.B, 2);
-                            Gb.m[0] = g0.x; Gb.m[1] = g0.y; Gb.m[2] = g0.z; Gb.m[3] = g1.x; Gb.m[4] = g1.y; Gb.m[5] = g1.z; Gb.m[6] = g2.x; Gb.m[7] = g2.y; Gb.m[8] = g2.z;
-                        }
                         Sym3 Gc;
-                        {
-                            V3 q0 = cross(col(Gb, 0), r), q1 = cross(col(Gb, 1), r), q2 = cross(col(Gb, 2), r);
-                            V3 n0 = cross(r, col(Lp.B, 0)), n1 = cross(r, col(Lp.B, 1)), n2 = cross(r, col(Lp.B, 2));
-                            Gc.xx = Lp.C.xx + q0.x - n0.x;
-                            Gc.xy = Lp.C.xy + q0.y - n1.x;
-                            Gc.xz = Lp.C.xz + q0.z - n2.x;
-                            Gc.yy = Lp.C.yy + q1.y - n1.y;
-                            Gc.yz = Lp.C.yz + q1.z - n2.y;
-                            Gc.zz = Lp.C.zz + q2.z - n2.z;
+                        if constexpr (F::LAMX) {
+                            // (every entry two / four fused multiply-adds on the parent's entry: Gc_kj = Lc_kj + (col_k(Gb) x r)_j + (col_j(Lb) x r)_k)
+#pragma unroll
+                            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                                for (int j = 0; j < 3; ++j) Gb.m[3 * i + j] = cross_at_plus(Lp.B.m[3 * i + j], i == 0 ? la0 : (i == 1 ? la1 : la2), r, j);
+                            auto gc = [&](float c, int k, int j) { return cross_at_plus(cross_at_plus(c, col(Gb, k), r, j), col(Lp.B, j), r, k); };
+                            Gc = Sym3{gc(Lp.C.xx, 0, 0), gc(Lp.C.xy, 0, 1), gc(Lp.C.xz, 0, 2), gc(Lp.C.yy, 1, 1), gc(Lp.C.yz, 1, 2), gc(Lp.C.zz, 2, 2)};
+                        } else {
+                            {
+                                V3 g0 = cross(la0, r) + row(Lp.B, 0), g1 = cross(la1, r) + row(Lp.B, 1), g2 = cross(la2, r) + row(Lp.B, 2);
+                                Gb.m[0] = g0.x; Gb.m[1] = g0.y; Gb.m[2] = g0.z; Gb.m[3] = g1.x; Gb.m[4] = g1.y; Gb.m[5] = g1.z; Gb.m[6] = g2.x; Gb.m[7] = g2.y; Gb.m[8] = g2.z;
+                            }
+                            {
+                                V3 q0 = cross(col(Gb, 0), r), q1 = cross(col(Gb, 1), r), q2 = cross(col(Gb, 2), r);
+                                V3 n0 = cross(r, col(Lp.B, 0)), n1 = cross(r, col(Lp.B, 1)), n2 = cross(r, col(Lp.B, 2));
+                                Gc.xx = Lp.C.xx + q0.x - n0.x;
+                                Gc.xy = Lp.C.xy + q0.y - n1.x;
+                                Gc.xz = Lp.C.xz + q0.z - n2.x;
+                                Gc.yy = Lp.C.yy + q1.y - n1.y;
+                                Gc.yz = Lp.C.yz + q1.z - n2.y;
+                                Gc.zz = Lp.C.zz + q2.z - n2.z;
+                            }
                         }
                         // Lambda_b = [Di 0; 0 0] + T^T G T,  T = [aug Di, 0; -E^T, 1]
-                        M3 DiM;
-                        DiM.m[0] = Di.xx; DiM.m[1] = Di.xy; DiM.m[2] = Di.xz; DiM.m[3] = Di.xy; DiM.m[4] = Di.yy; DiM.m[5] = Di.yz; DiM.m[6] = Di.xz; DiM.m[7] = Di.yz; DiM.m[8] = Di.zz;
-                        M3 H1, H2;
+                        // By blocks, with P = aug Di (symmetric) and Ga = Lp.A:  H1 = Ga P - Gb E^T ( = M1^T, M1 = P Ga - E Gb^T ),
+                        // Lam.B = P Gb - E Gc,  Lam.A = Di + M1 P - Lam.B E^T,  Lam.C = Gc.
+                        M3 H1;  // (the joint-limit block below reads it)
+                        if constexpr (F::LAMX) {
+                            // every entry once: aug (Di . G) - E . G in fused multiply-adds, the scale on the finished dot (scaled_dot_minus_dot);
+                            // of the symmetric Lam.A the upper triangle
 #pragma unroll
-                        for (int i = 0; i < 3; ++i) {
-                            V3 gai = i == 0 ? la0 : (i == 1 ? la1 : la2);
-                            V3 gbi = row(Gb, i);
-                            V3 gbti = col(Gb, i);
-                            V3 gci = i == 0 ? V3{Gc.xx, Gc.xy, Gc.xz} : (i == 1 ? V3{Gc.xy, Gc.yy, Gc.yz} : V3{Gc.xz, Gc.yz, Gc.zz});
+                            for (int i = 0; i < 3; ++i)
 #pragma unroll
-                            for (int j = 0; j < 3; ++j) {
-                                V3 dj = col(DiM, j);
-                                V3 ej = row(E, j);
-                                H1.m[3 * i + j] = aug * dot(gai, dj) - dot(gbi, ej);
-                                H2.m[3 * i + j] = aug * dot(gbti, dj) - dot(gci, ej);
+                                for (int j = 0; j < 3; ++j) {
+                                    H1.m[3 * j + i] = scaled_dot_minus_dot(aug, row(Di, i), j == 0 ? la0 : (j == 1 ? la1 : la2), row(E, i), row(Gb, j));
+                                    Lam.B.m[3 * i + j] = scaled_dot_minus_dot(aug, row(Di, i), col(Gb, j), row(E, i), row(Gc, j));
+                                }
+                            auto lam_a = [&](float di, int i, int j) { return scaled_dot_minus_dot(di, aug, col(H1, i), row(Di, j), row(Lam.B, i), row(E, j)); };
+                            Lam.A = Sym3{lam_a(Di.xx, 0, 0), lam_a(Di.xy, 0, 1), lam_a(Di.xz, 0, 2), lam_a(Di.yy, 1, 1), lam_a(Di.yz, 1, 2), lam_a(Di.zz, 2, 2)};
+                        } else {
+                            M3 DiM;
+                            DiM.m[0] = Di.xx; DiM.m[1] = Di.xy; DiM.m[2] = Di.xz; DiM.m[3] = Di.xy; DiM.m[4] = Di.yy; DiM.m[5] = Di.yz; DiM.m[6] = Di.xz; DiM.m[7] = Di.yz; DiM.m[8] = Di.zz;
+                            M3 H2;
+#pragma unroll
+                            for (int i = 0; i < 3; ++i) {
+                                V3 gai = i == 0 ? la0 : (i == 1 ? la1 : la2);
+                                V3 gbi = row(Gb, i);
+                                V3 gbti = col(Gb, i);
+                                V3 gci = i == 0 ? V3{Gc.xx, Gc.xy, Gc.xz} : (i == 1 ? V3{Gc.xy, Gc.yy, Gc.yz} : V3{Gc.xz, Gc.yz, Gc.zz});
+#pragma unroll
+                                for (int j = 0; j < 3; ++j) {
+                                    V3 dj = col(DiM, j);
+                                    V3 ej = row(E, j);
+                                    H1.m[3 * i + j] = aug * dot(gai, dj) - dot(gbi, ej);
+                                    H2.m[3 * i + j] = aug * dot(gbti, dj) - dot(gci, ej);
+                                }
                             }
+                            M3 t;
+#pragma unroll
+                            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                                for (int j = 0; j < 3; ++j) t.m[3 * i + j] = aug * dot(row(DiM, i), col(H1, j)) - dot(row(E, i), col(H2, j));
+                            Lam.A = Sym3{Di.xx + t.m[0], Di.xy + 0.5f * (t.m[1] + t.m[3]), Di.xz + 0.5f * (t.m[2] + t.m[6]), Di.yy + t.m[4],
+                                         Di.yz + 0.5f * (t.m[5] + t.m[7]), Di.zz + t.m[8]};
+#pragma unroll
+                            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                                for (int j = 0; j < 3; ++j) {
+                                    V3 gcj = j == 0 ? V3{Gc.xx, Gc.xy, Gc.xz} : (j == 1 ? V3{Gc.xy, Gc.yy, Gc.yz} : V3{Gc.xz, Gc.yz, Gc.zz});
+                                    Lam.B.m[3 * i + j] = aug * dot(row(DiM, i), col(Gb, j)) - dot(row(E, i), gcj);
+                                }
                         }
-                        M3 t;
-#pragma unroll
-                        for (int i = 0; i < 3; ++i)
-#pragma unroll
-                            for (int j = 0; j < 3; ++j) t.m[3 * i + j] = aug * dot(row(DiM, i), col(H1, j)) - dot(row(E, i), col(H2, j));
-                        Lam.A = Sym3{Di.xx + t.m[0], Di.xy + 0.5f * (t.m[1] + t.m[3]), Di.xz + 0.5f * (t.m[2] + t.m[6]), Di.yy + t.m[4],
-                                     Di.yz + 0.5f * (t.m[5] + t.m[7]), Di.zz + t.m[8]};
-#pragma unroll
-                        for (int i = 0; i < 3; ++i)
-#pragma unroll
-                            for (int j = 0; j < 3; ++j) {
-                                V3 gcj = j == 0 ? V3{Gc.xx, Gc.xy, Gc.xz} : (j == 1 ? V3{Gc.xy, Gc.yy, Gc.yz} : V3{Gc.xz, Gc.yz, Gc.zz});
-                                Lam.B.m[3 * i + j] = aug * dot(row(DiM, i), col(Gb, j)) - dot(row(E, i), gcj);
-                            }
                         Lam.C = Gc;
                         if (LIMITS && limact) {
                             const Sym3 K{Lam.A.xx - 2.f * H1.m[0] + Lp.A.xx, Lam.A.xy - H1.m[1] - H1.m[3] + Lp.A.xy, Lam.A.xz - H1.m[2] - H1.m[6] + Lp.A.xz,
