@@ -691,6 +691,64 @@ int v2p_mvae_reset(const v2p_mvae_cfg* cfg, int64_t num_envs, const v2p_mvae_wei
                    int64_t n_ids, const float* init_feature /*[n_ids,288]*/, const float* root_xy /*[n_ids,2]*/, const float* joint_pos_bind_rel /*[24,3]*/,
                    void* stream);
 
+/* ---- the imitation target from the motion generator's pose (vid2player/env/tasks/humanoid_smpl_im_mvae.py): what turns the root
+ * position and the 24 local joint matrices that v2p_mvae_step writes into the packed target row [331] (layout of v2p_env_buffers.target)
+ * that the low-level policy's humanoid tracks.  Stateless like v2p_mvae_step: every buffer is the caller's, no allocation, no host
+ * synchronisation, one launch per call.  The SMPL tree and the order of the engine's bodies come in with the cfg (the task knows them
+ * from the body names): joint s of SMPL is the engine's body b with smpl_of_body[b] = s (`_smpl_2_mujoco`, :218-237). */
+enum { V2P_PD_BASE_TARGET_POS = 0, V2P_PD_BASE_CURRENT_POS = 1, V2P_PD_BASE_NONE = 2 };
+typedef struct {
+    float dt;                       /* the control step (> 0): velocities are differences against the previous target over dt */
+    int32_t fix_head_orientation;   /* cfg_v2p fix_head_orientation: turn Head and Neck towards the ball (:605-634) */
+    int32_t head_body;              /* the engine's body index of Head */
+    int32_t smpl_head, smpl_neck;   /* SMPL joints Head (15) and Neck (12) */
+    int32_t key_bodies[4];          /* engine body indices whose rb_pos make key_pos */
+    int32_t smpl_parents[24];       /* the SMPL tree: [0] = -1, 0 <= parents[s] < s */
+    int32_t smpl_of_body[24];       /* a permutation of 0..23 with smpl_of_body[0] = 0 */
+    int32_t num_shapes;             /* rows of joint_pos_bind (>= 1) */
+    int32_t pd_target_base;         /* V2P_PD_BASE_*: v2p_mvae_target_actions only */
+    int32_t no_scale_action;        /* 1: the action is added unscaled (v2p_mvae_target_actions only) */
+} v2p_mvae_target_cfg;
+typedef struct {                    /* DEVICE buffers */
+    const float* root_pos;          /* [N,3] the player's `_root_pos` */
+    float* joint_rotmat;            /* [N,24,3,3] the player's `_joint_rotmat`; Head and Neck are WRITTEN by the head rule of the step */
+    const float* residual_root;     /* [N,3] nullable: `_res_root_actions`, already scaled (add_residual_root, :602-603) */
+    const float* ball_state;        /* [N,13] the ball's root state (position read); required by the head rule */
+    const float* joint_pos_bind;    /* [num_shapes,24,3] rest joints of the SMPL bodies, SMPL order */
+    const int32_t* env_shape_id;    /* [N] nullable (= shape 0): row of joint_pos_bind of an env */
+    float* target;                  /* [N,331] the row that is written */
+    const float* prev_target;       /* [N,331] the previous target (root_pos and rb_rot are read); step only; must not alias target */
+    float* root_states;             /* [N,13]    step: nullable, unused.  reset: nullable, the ids' rows are written (pose, zero velocities) */
+    float* dof_state;               /* [N,69,2]  reset: as root_states.  actions with V2P_PD_BASE_CURRENT_POS: the current dof_pos is read */
+    float* rb_state;                /* [N,24,13] step: body 0's position is the simulated root of the head rule's miss test (required by it);
+                                     * reset: as root_states */
+    int64_t* hold_reset;            /* [N] nullable, step only: zeroed - the wrapped imitation task's own episode bookkeeping (its clip */
+    int64_t* hold_progress;         /* [N] nullable      clock against the clip's length, progress against its episode length) must not end */
+    float* hold_cur_time;           /* [N] nullable      an episode the controller owns, nor mask its actions */
+    const float* pd_action_scale;   /* [69] actions only, unless no_scale_action */
+    const float* pd_action_offset;  /* [69] actions only, with V2P_PD_BASE_NONE */
+} v2p_mvae_target_buffers;
+/* `_set_target_motion_state` (:600-661) for envs 0 .. n-1: the target root = root_pos (+ residual_root); with fix_head_orientation the
+ * head rule (:605-634) on a first forward-kinematics pass, Head and Neck written back into joint_rotmat; then `_smpl_to_sim` /
+ * `_forward_kinematics` (:897-946, utils/hybrik.py:598-652 batch_rigid_transform): dof_pos = angle-axis of the local matrices, rb_pos /
+ * rb_rot by the chain of transforms over the env's row of joint_pos_bind, velocities against prev_target (root_ang_vel divided by dt
+ * twice, as the reference has it, :919).  Refused before any HIP call (V2P_ERR_INVALID, a message that names the call): a null struct or
+ * required pointer, n < 0, dt <= 0, a body / key-body / joint index outside 0..23, a tree or body order that is none, target ==
+ * prev_target.  n = 0 is a no-op. */
+int v2p_mvae_target_step(const v2p_mvae_target_cfg* cfg, int64_t n, const v2p_mvae_target_buffers* buffers, void* stream);
+/* `_reset_actors` + `_set_env_state` (:463-501) for env_ids [n_ids] (device; ids outside 0 .. num_envs-1 are skipped): `_smpl_to_sim`
+ * without a previous pose - no head rule, every velocity zero - into rows env_ids of `target` (the caller names the buffer that holds the
+ * PREVIOUS target: the reference stores the init pose as `_prev_target_*`, :492-494) and, where given, of root_states, dof_state and
+ * rb_state (v2p_env_push_state with_rb_state = 1 then puts the humanoid there).  Rows of other envs are not touched.  Refusals as the step. */
+int v2p_mvae_target_reset(const v2p_mvae_target_cfg* cfg, int64_t num_envs, const v2p_mvae_target_buffers* buffers, const int64_t* env_ids, int64_t n_ids,
+                          void* stream);
+/* `_action_to_pd_targets` (:693-703) before its clamp, for envs 0 .. n-1: actions_out[:, :69] = base + (no_scale_action ? 1 :
+ * pd_action_scale[c]) * actions_in[:, :69], base = target's dof_pos / dof_state's dof_pos / pd_action_offset by pd_target_base; columns
+ * 69..74 are copied.  The clamp to dof_pos +- pi/2 (:705-707) is the engine's pre-physics clamp with pd_tar_lim = pi/2.  actions_out may
+ * be actions_in.  Refused: as the step, and an unknown pd_target_base. */
+int v2p_mvae_target_actions(const v2p_mvae_target_cfg* cfg, int64_t n, const float* actions_in /*[n,75]*/, const v2p_mvae_target_buffers* base_buffers,
+                            float* actions_out /*[n,75]*/, void* stream);
+
 /* measurement: HIP events around every launch of the physics kernel (the dominant kernel of the step), recorded on the launch stream
  * by v2p_env_step / v2p_env_physics between _begin and _end (at most max_launches of them).  _end synchronises the events and returns
  * the summed kernel time in milliseconds and the number of launches measured.  bench.py's roofline.kernel_ms comes from here, from

@@ -1,0 +1,487 @@
+"""Golden data of the imitation target from the motion generator's pose, recorded from the reference itself:
+tests/golden/mvae_target.npz.
+
+`HumanoidSMPLIMMVAE` (vid2player/env/tasks/humanoid_smpl_im_mvae.py) is imported on the CPU through oracle/ref_shim.  An object made with
+`__new__` gets its attributes set by hand - `_smpl` a namespace with `joint_pos_bind` and `parents`, `_mvae_player` a namespace with
+`_root_pos` and `_joint_rotmat`, synthetic simulation tensors - and the reference's OWN methods run on it: `_reset_actors` (its
+`_smpl_to_sim` and `_set_env_state`) once, then T consecutive `post_mvae_step`s (`_set_target_motion_state` with the head rule, and
+`_compute_observations`) with `_save_prev_target_motion_state` between them; `_action_to_pd_targets` for the three bases and both
+`no_scale_action` values.  Two variants: H - head rule on, two body shapes, a residual root; P - head rule off, one shape.
+
+Poses are constructed: a moderate base pose per env with small per-step increments; upright roots near the 120 degree base rotation
+(trace ~ 0 of the quaternion function); three envs carry a joint turned by ~165 degrees about x, y, z (the other three branches on local
+matrices, `cos_theta < 0`); env 0 does not move between steps 2 and 3 (the masked branch of `quat_to_angle_axis`); the ball is placed
+left and right of the gaze, across both +-pi wraps, and into each of the two miss conditions.  The generator asserts that each occurs.
+
+Scatter.  The same run in float64 gives `scatter/<kind>/<name>` = max |float32 - float64| per quantity: `step` (one teacher-forced step
+from the recorded float32 state), `free` (the free-running sequence), `reset`, `actions`.  Margin.  Every float that picks a branch -
+the trace and the diagonal comparisons, `cos_theta`, the 1e-5 mask, the +-pi wraps, the two miss tests; from the numpy statement in
+float32 and float64 - stays MARGIN x its own scatter from the threshold; a pose that violates it is re-drawn alone (a small offset of its own on every joint,
+a new place of the ball), the count of re-drawn poses is printed, more than 5 % of the poses fail.  (The static env has no margin at the mask and needs none: its difference quaternion is the identity up to rounding, on
+either side of the mask the velocity is 2 |xyz| / dt ~ 1e-5, far inside every allowance.)  Only arrays are stored.  Run where the
+reference exists:
+    python tools/gen_golden_mvae_target.py
+"""
+import math
+import os
+import sys
+import types
+
+sys.dont_write_bytecode = True  # never leave __pycache__ in the read-only reference mount
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+sys.path.insert(0, os.path.join(REPO, "oracle"))
+sys.path.insert(0, REPO)
+
+from ref_shim.install import REFERENCE_ROOT, _Sink, install  # noqa: E402
+
+install()
+for absent in ("players", "players.mvae_player", "env.utils.player_builder", "smpl_visualizer", "smpl_visualizer.vis_sport", "tqdm"):
+    try:
+        __import__(absent)
+    except Exception:
+        sys.modules[absent] = _Sink(absent)
+sys.path.insert(0, os.path.join(REFERENCE_ROOT, "vid2player"))
+
+import torch  # noqa: E402
+
+torch.set_num_threads(1)
+torch.Tensor.get_device = lambda self: self.device
+
+import env.tasks.humanoid_smpl_im_mvae as ref_task  # noqa: E402
+
+from vid2player3d_amd import mvae_target as mt  # noqa: E402
+from vid2player3d_amd.model import load_baked_model  # noqa: E402
+
+ref_task.pdb = types.SimpleNamespace(set_trace=lambda *a, **k: None)
+
+OUT = os.path.join(REPO, "tests", "golden", "mvae_target.npz")
+N, T, MARGIN, DT = 12, 6, 100.0, 1.0 / 30.0
+KEY_BODIES = ("R_Ankle", "L_Ankle", "L_Hand", "R_Hand")
+VARIANTS = {"H": dict(fix_head=True, shapes=2, residual=True), "P": dict(fix_head=False, shapes=1, residual=False)}
+PIECES = ("root_pos", "root_rot", "dof_pos", "root_vel", "root_ang_vel", "dof_vel", "rb_pos", "rb_rot")
+BIG = {1: (4, (-2.9, 0.05, 0.03)), 2: (5, (0.04, 2.85, 0.02)), 3: (18, (0.03, -0.05, -2.95))}  # env: (SMPL joint, angle-axis)
+GAZE = {4: -2.9, 5: 2.9}  # envs whose gaze starts next to -pi / +pi
+MISS_Y, MISS_X, STATIC = 6, 7, 0
+BASE = np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])  # the 120 degree rotation about (1, 1, 1): SMPL's y-up to z-up
+
+
+def rodrigues(aa):
+    aa = np.asarray(aa, dtype=np.float64)
+    th = np.linalg.norm(aa)
+    if th < 1e-12:
+        return np.eye(3)
+    k = aa / th
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + math.sin(th) * K + (1 - math.cos(th)) * K @ K
+
+
+def rot_z(a):
+    return np.array([[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]])
+
+
+def draw_env(v, e, attempts):
+    """The pose sequence of one env: T + 1 poses (the first is the reset's), float64; yaw 0 (set afterwards).  attempts [T + 1]: how often
+    each pose has been re-drawn - a re-drawn pose gets a small offset of its own on every joint and on the root's tilt, and its step a new
+    place of the ball; the other poses of the env stay as they were."""
+    rng = np.random.default_rng([20411, "HP".index(v), e])
+    base = rng.uniform(-0.5, 0.5, (24, 3))
+    inc = rng.choice([-1.0, 1.0], (24, 3)) * rng.uniform(0.015, 0.04, (24, 3))  # (no joint stands still: the mask of quat_to_angle_axis is the static env's)
+    if e in BIG:
+        j, aa = BIG[e]
+        base[j] = np.asarray(aa) + rng.uniform(-0.02, 0.02, 3)
+        inc[j] *= 0.5
+    tilt, tilt_inc = rng.uniform(-0.12, 0.12, 3), rng.uniform(-0.01, 0.01, 3)
+    yaw_inc = rng.choice([-1.0, 1.0]) * rng.uniform(0.015, 0.03)
+    root0 = np.array([rng.uniform(-0.5, 0.5), -12.0 + rng.uniform(-0.5, 0.5), 0.9 + rng.uniform(-0.03, 0.03)])
+    root_inc = np.array([rng.uniform(-0.02, 0.02), rng.uniform(-0.03, 0.03), rng.uniform(-0.005, 0.005)])
+    residual, delta, yaw = rng.uniform(-0.02, 0.02, (T, 3)), rng.uniform(0.3, 0.9, T), rng.uniform(-0.4, 0.4)
+    local, root_rot, root = np.zeros((T + 1, 24, 3, 3)), np.zeros((T + 1, 3, 3)), np.zeros((T + 1, 3))
+    for k in range(T + 1):
+        kk = source_pose(e, k)
+        off, tilt_off = np.zeros((24, 3)), np.zeros(3)
+        if attempts[kk] > 0:
+            again = np.random.default_rng([20411, "HP".index(v), e, kk, int(attempts[kk])])
+            off, tilt_off = again.uniform(-0.006, 0.006, (24, 3)), again.uniform(-0.006, 0.006, 3)
+            if k > 0 and attempts[k] > 0:
+                delta[k - 1] = np.random.default_rng([20411, "HP".index(v), e, k, int(attempts[k]), 1]).uniform(0.3, 0.9)
+        for j in range(1, 24):
+            local[k, j] = rodrigues(base[j] + kk * inc[j] + off[j])
+        root_rot[k] = rot_z(kk * yaw_inc) @ BASE @ rodrigues(tilt + kk * tilt_inc + tilt_off)
+        root[k] = root0 + kk * root_inc
+    if e == STATIC:
+        residual[3] = residual[2]
+    # (the pose the yaw of a GAZE env is worked out from: step 0's without its offset, so that a re-drawn pose does not turn the others)
+    plain = np.stack([np.eye(3)] + [rodrigues(base[j] + inc[j]) for j in range(1, 24)])
+    plain[0] = rot_z(yaw_inc) @ BASE @ rodrigues(tilt + tilt_inc)
+    return dict(local=local, root_rot=root_rot, root=root, residual=residual, delta=delta, yaw=yaw, plain=plain)
+
+
+def source_pose(e, k):
+    """pose k of the static env's step 3 is its pose of step 2 (pose k belongs to step k - 1)"""
+    return k - 1 if (e == STATIC and k == 4) else k
+
+
+def settings(v, model):
+    keys = [list(model.body_names).index(b) for b in KEY_BODIES]
+    return mt.target_settings({"fix_head_orientation": VARIANTS[v]["fix_head"], "add_residual_root": VARIANTS[v]["residual"]}, {}, DT, model.body_names,
+                              model.parents, keys)
+
+
+def bind_rows(model, shapes):
+    rest = np.zeros((24, 3))
+    for b in range(24):
+        p = int(model.parents[b])
+        rest[b] = np.asarray(model.local_pos[b], dtype=np.float64) + (rest[p] if p >= 0 else 0.0)
+    rest = rest[[list(model.body_names).index(nm) for nm in mt.SMPL_JOINT_NAMES]]
+    rows = [rest]
+    for s in range(1, shapes):  # another body: 7 % taller, limbs a little longer still
+        other = rest * 1.07
+        other[16:] = other[16:] * 1.02
+        rows.append(other)
+    return np.stack(rows).astype(np.float32)
+
+
+def assemble(v, st, bind, shape_id, draws):
+    """Inputs of the whole run from the envs' draws: the yaw that puts the gaze where it is wanted, then ball and simulated root."""
+    n = len(draws)
+    rotmat, root = np.zeros((T + 1, n, 24, 3, 3)), np.zeros((T + 1, n, 3))
+    for e, d in enumerate(draws):
+        yaw = d["yaw"]
+        if e in GAZE:  # the gaze's angle of step 0 with yaw 0, then the yaw that moves it to GAZE[e] (a rotation about z shifts it by the yaw)
+            o = mt.smpl_to_sim_reference(st, d["root"][1][None], d["plain"][None], bind[shape_id[e]][None].astype(np.float64), dt=np.float64)
+            yaw = GAZE[e] - gaze_angle(o, st)[0]
+        for k in range(T + 1):
+            rotmat[k, e] = d["local"][k]
+            rotmat[k, e, 0] = rot_z(yaw) @ d["root_rot"][k]
+            root[k, e] = d["root"][k]
+    rotmat, root = rotmat.astype(np.float32), root.astype(np.float32)
+    residual = np.stack([d["residual"] for d in draws], 1).astype(np.float32) if VARIANTS[v]["residual"] else None
+    ball, sim_root = np.zeros((T, n, 3), np.float32), np.zeros((T, n, 3), np.float32)
+    b64 = bind[shape_id].astype(np.float64)
+    for t in range(T):
+        tr = root[t + 1].astype(np.float64) + (residual[t] if residual is not None else 0.0)
+        o = mt.smpl_to_sim_reference(st, tr, rotmat[t + 1], b64, dt=np.float64)
+        gaze, head = gaze_angle(o, st), o["rb_pos"][:, st["head_body"]]
+        for e, d in enumerate(draws):
+            sign = 1.0 if (e + t) % 2 == 0 else -1.0
+            if e in GAZE:
+                sign = -1.0 if GAZE[e] < 0 else 1.0  # across the wrap
+            ang, r = gaze[e] + sign * d["delta"][t], 3.0
+            ang = (ang + math.pi) % (2 * math.pi) - math.pi
+            if e == MISS_X and t % 2 == 0:
+                ang, r = (0.0 if t % 4 == 0 else math.pi), 6.0
+            ball[t, e] = [head[e, 0] + r * math.cos(ang), head[e, 1] + r * math.sin(ang), 1.0 + 0.1 * t]
+            miss_y = e == MISS_Y and t % 2 == 1
+            sim_root[t, e] = [tr[e, 0] + 0.01, ball[t, e, 1] + (1.5 if miss_y else -1.0), tr[e, 2]]
+    return dict(rotmat=rotmat, root=root, residual=residual, ball=ball, sim_root=sim_root)
+
+
+def gaze_angle(o, st):
+    q = o["rb_rot"][:, st["head_body"]].astype(np.float64)
+    x, y, z, w = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    return np.arctan2(2 * (y * z - x * w), 2 * (x * z + y * w))
+
+
+def numpy_run(st, bind, shape_id, inp, dt, free=True, prev_rows=None):
+    """The numpy statement over the run; returns (rows [T+1,n,331], probes of the steps, probes of the reset, applied head angles)."""
+    n = inp["root"].shape[1]
+    pr, pr0 = {}, {}
+    zero = np.zeros((n, mt.ROW), dt)
+    rows = [mt.target_reset_reference(st, dict(root_pos=inp["root"][0], joint_rotmat=inp["rotmat"][0], joint_pos_bind=bind, env_shape_id=shape_id, target=zero),
+                                      np.arange(n), dt, pr0)["target"]]
+    applied = []
+    for t in range(T):
+        s = dict(root_pos=inp["root"][t + 1], joint_rotmat=inp["rotmat"][t + 1], residual_root=None if inp["residual"] is None else inp["residual"][t],
+                 ball_pos=inp["ball"][t], sim_root_pos=inp["sim_root"][t], joint_pos_bind=bind, env_shape_id=shape_id,
+                 prev_target=rows[-1] if free else prev_rows[t])
+        o = mt.target_step_reference(st, s, dt, pr)
+        rows.append(o["target"])
+        applied.append(pr.get("angle_diff_applied", np.zeros(n)))
+    return np.stack(rows), pr, pr0, np.stack(applied)
+
+
+def flat(p, n):
+    """{name: [n, k]} of a probes dict (lists of raveled arrays whose leading dimension was the env)."""
+    out = {}
+    for k, v in p.items():
+        if isinstance(v, dict):
+            for kk, vv in flat(v, n).items():
+                out[k + "/" + kk] = vv
+        elif isinstance(v, list) and k != "branch":
+            out[k] = np.concatenate([np.asarray(x, dtype=np.float64).reshape(n, -1) for x in v], 1)
+    return out
+
+
+THRESHOLDS = {"trace": (0.0,), "diagonal": (0.0,), "cos_theta": (0.0,), "sin_theta": (1e-5,), "angle_diff": (-math.pi, math.pi), "miss_y": (0.0,), "miss_x": (0.0,)}
+
+
+def chunks(p, n):
+    """{name: list of [n, k]} of a probes dict, in the order the statement appended them"""
+    out = {}
+    for k, v in p.items():
+        if isinstance(v, dict):
+            for kk, vv in chunks(v, n).items():
+                out[k + "/" + kk] = vv
+        elif isinstance(v, list) and k != "branch":
+            out[k] = [np.asarray(x, dtype=np.float64).reshape(n, -1) for x in v]
+    return out
+
+
+def violators(p32, p64, n, steps):
+    """[n, steps]: the (env, step) pairs with a branch-picking float within MARGIN x its own scatter of the threshold.  The probes of a
+    run of `steps` steps come in step order, the same number of pieces per step."""
+    a, b = chunks(p32, n), chunks(p64, n)
+    bad = np.zeros((n, steps), bool)
+    for k in a:
+        name = k.split("/")[-1]
+        if name not in THRESHOLDS:
+            continue
+        per = len(a[k]) // steps
+        assert per * steps == len(a[k])
+        for i, (x, y) in enumerate(zip(a[k], b[k])):
+            fin = np.isfinite(x) & np.isfinite(y)
+            if name == "sin_theta":  # (the static env's identity differences: see the module's docstring)
+                fin &= ~((x < 1e-3) & (y < 1e-3) & (np.arange(n)[:, None] == STATIC))
+            with np.errstate(invalid="ignore"):
+                own = np.maximum(np.where(fin, np.abs(x - y), 0.0), 1.2e-7)  # every value against its own scatter, at least an ulp of 1
+            if name == "sin_theta":  # (sqrt(1 - w^2) next to w = 1: one rounding of w moves it by 6e-8 / sin_theta)
+                own = np.maximum(own, 6e-8 / np.maximum(np.where(fin, x, 1.0), 1e-4))
+            dist = np.min(np.abs(np.where(fin, x, np.inf)[..., None] - np.asarray(THRESHOLDS[name])), axis=-1)
+            bad[:, i // per] |= (dist < MARGIN * own).any(axis=1)
+    return bad
+
+
+# ------------------------------------------------------------------------------------------------------------------ the reference
+def make_object(st, bind, shape_id, n, dtype, fix_head, residual):
+    o = ref_task.HumanoidSMPLIMMVAE.__new__(ref_task.HumanoidSMPLIMMVAE)
+    f = dict(dtype=dtype)
+    o.device, o.num_envs, o.dt = "cpu", n, DT
+    o.cfg = {"env": {}}
+    o.cfg_v2p = {"fix_head_orientation": fix_head, "add_residual_root": residual}
+    o._build_mujoco_smpl_transform()
+    assert o._smpl_2_mujoco == st["smpl_of_body"]
+    o._smpl = types.SimpleNamespace(joint_pos_bind=torch.from_numpy(bind[shape_id]).to(**f), parents=torch.tensor(st["smpl_parents"], dtype=torch.long))
+    o._mvae_player = types.SimpleNamespace(_root_pos=torch.zeros((n, 3), **f), _joint_rotmat=torch.zeros((n, 24, 3, 3), **f))
+    o._controller = types.SimpleNamespace(_res_root_actions=torch.zeros((n, 3), **f))
+    o._head_body_id, o._num_humanoid_bodies, o._num_dof = st["head_body"], 24, 69
+    o._humanoid_root_states = torch.zeros((n, 13), **f)
+    for k in ("_rigid_body_pos", "_rigid_body_vel", "_rigid_body_ang_vel", "_prev_rigid_body_ang_vel"):
+        setattr(o, k, torch.zeros((n, 24, 3), **f))
+    o._rigid_body_rot = torch.zeros((n, 24, 4), **f)
+    o._dof_pos, o._dof_vel, o._pd_target_dof_pos = torch.zeros((n, 69), **f), torch.zeros((n, 69), **f), torch.zeros((n, 69), **f)
+    o._prev_target_root_pos, o._prev_target_rb_rot = torch.zeros((n, 3), **f), torch.zeros((n, 24, 4), **f)
+    o._root_pos, o._root_vel, o._target_root_pos = torch.zeros((n, 3), **f), torch.zeros((n, 3), **f), torch.zeros((n, 3), **f)
+    o._ball_pos = torch.zeros((n, 3), **f)
+    o._reset_ref_motion_bodies = torch.zeros((n, 11), **f)
+    o._reset_ref_motion_bodies[:, 0] = 1
+    o._reset_ref_motion_bodies[:, 1:] = torch.linspace(-0.5, 0.5, 10, **f)
+    o.obs_type, o._local_root_obs, o._root_height_obs = "joint_pos_and_angle", True, True
+    o.obs_buf = torch.zeros((n, mt.NUM_OBS_IM), **f)
+    return o
+
+
+def in_dtype(dtype, fn):
+    """run fn with torch's default dtype (and the head rule's `torch.FloatTensor([0, 0, 1])`) in `dtype`"""
+    if dtype == torch.float32:
+        return fn()
+    keep = torch.FloatTensor
+    torch.set_default_dtype(torch.float64)
+    torch.FloatTensor = torch.DoubleTensor
+    try:
+        return fn()
+    finally:
+        torch.FloatTensor = keep
+        torch.set_default_dtype(torch.float32)
+
+
+def pieces_of(o, prefix):
+    return {k: getattr(o, prefix + k).detach().numpy().copy().reshape(o.num_envs, -1) for k in PIECES}
+
+
+def reference_run(st, bind, shape_id, inp, sim, dtype, v, forced_rows=None):
+    """The reference's own methods over the run.  forced_rows: the recorded float32 rows - every step starts from them (teacher-forced)."""
+    n = inp["root"].shape[1]
+    cfgv = VARIANTS[v]
+    o = make_object(st, bind, shape_id, n, dtype, cfgv["fix_head"], cfgv["residual"])
+    T_ = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype).clone()  # (the head rule writes into the player's tensor)
+    out = dict(reset={}, steps=[])
+
+    def run():
+        o._mvae_player._root_pos[:] = T_(inp["root"][0])
+        o._mvae_player._joint_rotmat[:] = T_(inp["rotmat"][0])
+        o._reset_actors(torch.arange(n))
+        out["reset"] = dict(root_states=o._humanoid_root_states.numpy().copy(), dof_pos=o._dof_pos.numpy().copy(), dof_vel=o._dof_vel.numpy().copy(),
+                            rb_pos=o._rigid_body_pos.numpy().copy(), rb_rot=o._rigid_body_rot.numpy().copy(), prev_root_pos=o._prev_target_root_pos.numpy().copy(),
+                            prev_rb_rot=o._prev_target_rb_rot.numpy().copy())
+        assert not o._rigid_body_vel.any() and not o._rigid_body_ang_vel.any() and not o._dof_vel.any() and not o._humanoid_root_states[:, 7:].any()
+        # the simulated state the observation reads: static over the run
+        o._rigid_body_pos, o._rigid_body_rot = T_(sim["rb_state"][..., 0:3]), T_(sim["rb_state"][..., 3:7])
+        o._rigid_body_vel, o._rigid_body_ang_vel = T_(sim["rb_state"][..., 7:10]), T_(sim["rb_state"][..., 10:13])
+        o._dof_pos, o._dof_vel = T_(sim["dof_state"][..., 0]), T_(sim["dof_state"][..., 1])
+        for t in range(T):
+            if forced_rows is not None:
+                prev = mt.unpack_row(forced_rows[t])
+                o._prev_target_root_pos, o._prev_target_rb_rot = T_(prev["root_pos"]), T_(prev["rb_rot"]).view(n, 24, 4)
+            o._mvae_player._root_pos = T_(inp["root"][t + 1])
+            o._mvae_player._joint_rotmat = T_(inp["rotmat"][t + 1])
+            if inp["residual"] is not None:
+                o._controller._res_root_actions = T_(inp["residual"][t])
+            o._ball_pos, o._root_pos = T_(inp["ball"][t]), T_(inp["sim_root"][t])
+            o.post_mvae_step()
+            step = pieces_of(o, "_target_")
+            step["joint_rotmat"] = o._mvae_player._joint_rotmat.numpy().copy()
+            step["obs"] = o.obs_buf.numpy().copy()
+            out["steps"].append(step)
+            o._save_prev_target_motion_state()
+
+    in_dtype(dtype, run)
+    return out, o
+
+
+def row_of(st, step):
+    o = {k: step[k] for k in PIECES}
+    o["rb_pos"] = o["rb_pos"].reshape(len(o["rb_pos"]), 24, 3)
+    return mt.pack_row(st, o, step["root_pos"].dtype.type)
+
+
+def reset_row(st, r):
+    n = len(r["dof_pos"])
+    o = dict(root_pos=r["root_states"][:, 0:3], root_rot=r["root_states"][:, 3:7], dof_pos=r["dof_pos"], root_vel=np.zeros((n, 3)), root_ang_vel=np.zeros((n, 3)),
+             dof_vel=np.zeros((n, 69)), rb_pos=r["rb_pos"], rb_rot=r["rb_rot"])
+    return mt.pack_row(st, {k: np.asarray(x, dtype=r["dof_pos"].dtype) for k, x in o.items()}, r["dof_pos"].dtype.type)
+
+
+def worst(scat, kind, name, a, b):
+    d = float(np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64)).max())
+    scat[kind][name] = max(scat[kind].get(name, 0.0), d)
+
+
+def run_variant(v, model, out, scat, counts):
+    cfgv = VARIANTS[v]
+    st = settings(v, model)
+    bind = bind_rows(model, cfgv["shapes"])
+    shape_id = (np.arange(N) % cfgv["shapes"]).astype(np.int32)
+    attempts = np.zeros((N, T + 1), int)  # re-draws of every pose (pose k is step k - 1's, pose 0 the reset's)
+    for _ in range(40):
+        draws = [draw_env(v, e, attempts[e]) for e in range(N)]
+        inp = assemble(v, st, bind, shape_id, draws)
+        rows32, p32, r32, applied = numpy_run(st, bind, shape_id, inp, np.float32)
+        rows64, p64, r64, _ = numpy_run(st, bind, shape_id, inp, np.float64)
+        bad = np.concatenate([violators(r32, r64, N, 1), violators(p32, p64, N, T)], 1)
+        if not bad.any():
+            break
+        for e, k in zip(*np.nonzero(bad)):
+            attempts[e, source_pose(e, k)] += 1
+    else:
+        raise AssertionError("variant %s: no draw satisfies the margins" % v)
+    counts[0] += int(attempts.sum())  # poses re-drawn (a pose re-drawn twice counts twice)
+    counts[1] += N * (T + 1)          # poses
+    # ---- coverage, from the numpy statement
+    br_local = np.concatenate([np.ravel(x) for x in p32["local"]["branch"]] + [np.ravel(x) for x in r32["local"]["branch"]])
+    br_global = np.concatenate([np.ravel(x) for x in p32["global"]["branch"]])
+    for name, br in (("local", br_local), ("global", br_global)):
+        assert set(br.tolist()) == {0, 1, 2, 3}, "variant %s: %s matrices take only the branches %s of rotation_matrix_to_quaternion" % (v, name, sorted(set(br.tolist())))
+    fl = flat(p32, N)
+    assert (fl["local/cos_theta"] < 0).any(), "no cos_theta < 0"
+    root_trace = fl["global/trace"].reshape(N, -1, 24)[:, :, 0]
+    facing = [e for e in range(N) if e not in GAZE]  # (the two envs of the wraps are turned away from the net to put their gaze next to +-pi)
+    assert np.abs(root_trace[facing]).max() < 0.6 and (root_trace > 0).any() and (root_trace < 0).any(), "the roots' traces do not straddle 0"
+    sin_theta = fl["sin_theta"].reshape(N, T, 24)
+    assert (sin_theta[STATIC, 3] < 1e-3).sum() >= 20 and (sin_theta[1:] > 1e-3).all(), "the static env does not reach the masked branch (or another env does)"
+    if cfgv["fix_head"]:
+        raw = fl["angle_diff"]
+        assert (raw > math.pi).any() and (raw < -math.pi).any(), "the +-pi wraps are not both taken"
+        assert (fl["miss_y"] < 0).any() and (fl["miss_x"] > 0).any(), "a miss condition is not taken"
+        assert (fl["miss_y"][fl["miss_x"] > 0] > 0).all(), "the x miss never decides alone"
+        assert (applied > 0.2).any() and (applied < -0.2).any(), "the ball is not on both sides of the gaze"
+    # ---- the reference, float32 and float64
+    rng = np.random.default_rng([20412, "HP".index(v)])
+    base = mt.unpack_row(rows32[0])
+    rb = np.zeros((N, 24, 13), np.float32)
+    rb[..., 0:3] = base["rb_pos"].reshape(N, 24, 3) + rng.uniform(-0.03, 0.03, (N, 24, 3))
+    rb[..., 3:7] = base["rb_rot"].reshape(N, 24, 4)
+    rb[..., 7:13] = rng.uniform(-1.0, 1.0, (N, 24, 6))
+    dof = np.stack([base["dof_pos"] + rng.uniform(-0.05, 0.05, (N, 69)), rng.uniform(-2.0, 2.0, (N, 69))], -1).astype(np.float32)
+    sim = dict(rb_state=rb, dof_state=dof)
+    ref32, obj32 = reference_run(st, bind, shape_id, inp, sim, torch.float32, v)
+    rows = np.stack([reset_row(st, ref32["reset"])] + [row_of(st, s) for s in ref32["steps"]]).astype(np.float32)
+    free64, _ = reference_run(st, bind, shape_id, inp, sim, torch.float64, v)
+    step64, _ = reference_run(st, bind, shape_id, inp, sim, torch.float64, v, forced_rows=rows)
+    assert np.array_equal(ref32["reset"]["prev_root_pos"], ref32["reset"]["root_states"][:, :3]) and np.array_equal(ref32["reset"]["prev_rb_rot"], ref32["reset"]["rb_rot"])
+    worst(scat, "reset", "target", rows[0], reset_row(st, free64["reset"]))
+    for t in range(T):
+        for kind, r64 in (("step", step64), ("free", free64)):
+            worst(scat, kind, "target", rows[t + 1], row_of(st, r64["steps"][t]))
+            for k in PIECES + ("joint_rotmat", "obs"):
+                worst(scat, kind, k, ref32["steps"][t][k], r64["steps"][t][k])
+        if not cfgv["fix_head"]:
+            assert np.array_equal(ref32["steps"][t]["joint_rotmat"], inp["rotmat"][t + 1])
+        else:
+            others = [j for j in range(24) if j not in (st["smpl_head"], st["smpl_neck"])]
+            assert np.array_equal(ref32["steps"][t]["joint_rotmat"][:, others], inp["rotmat"][t + 1][:, others])
+    p = v + "/"
+    out[p + "settings"] = np.array([int(cfgv["fix_head"]), cfgv["shapes"], int(cfgv["residual"])], np.int32)
+    out[p + "joint_pos_bind"], out[p + "env_shape_id"] = bind, shape_id
+    out[p + "in/root_pos"], out[p + "in/joint_rotmat"] = inp["root"], inp["rotmat"]
+    if inp["residual"] is not None:
+        out[p + "in/residual_root"] = inp["residual"]
+    out[p + "in/ball_pos"], out[p + "in/sim_root_pos"] = inp["ball"], inp["sim_root"]
+    out[p + "in/rb_state"], out[p + "in/dof_state"] = rb, dof
+    out[p + "target"] = rows
+    hn = [st["smpl_head"], st["smpl_neck"]]
+    out[p + "out/head_neck_rotmat"] = np.stack([s["joint_rotmat"][:, hn] for s in ref32["steps"]]).astype(np.float32)
+    out[p + "out/obs"] = np.stack([s["obs"] for s in ref32["steps"]]).astype(np.float32)
+    if v == "H":
+        record_actions(st, rows[2], out, scat)
+
+
+def record_actions(st, row, out, scat):
+    """`_action_to_pd_targets` for the three bases and both scalings, the clamp never active: the recorded pd_tar is the sum before it."""
+    rng = np.random.default_rng(20413)
+    actions = rng.uniform(-1.0, 1.0, (N, 75)).astype(np.float32)
+    scale = rng.uniform(0.4, 1.2, 69).astype(np.float32)
+    offset = rng.uniform(-0.2, 0.2, 69).astype(np.float32)
+    tdof = mt.unpack_row(row)["dof_pos"]
+    cur = (tdof + rng.uniform(-0.05, 0.05, (N, 69))).astype(np.float32)
+    out["actions/in"], out["actions/pd_action_scale"], out["actions/pd_action_offset"], out["actions/target"] = actions, scale, offset, row
+    out["actions/dof_pos"] = cur
+    for base in ("target_pos", "current_pos", "none"):
+        for no_scale in (False, True):
+            res = {}
+            for dtype in (torch.float32, torch.float64):
+                o = ref_task.HumanoidSMPLIMMVAE.__new__(ref_task.HumanoidSMPLIMMVAE)
+                o.cfg, o.no_scale_action = {"env": {"pd_target_base": base}}, no_scale
+                c = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
+                o._target_dof_pos, o._dof_pos, o._pd_action_offset, o._pd_action_scale = c(tdof), c(cur), c(offset), c(scale)
+                clamp_around = c(cur if base != "none" else np.broadcast_to(offset, (N, 69)) + 0.0)
+                if base == "none":  # (the clamp is around `_dof_pos`: the object of this base sits at the offsets)
+                    o._dof_pos = clamp_around
+                pd = o._action_to_pd_targets(c(actions[:, :69]))
+                assert ((pd > o._dof_pos - np.pi / 2 + 1e-3) & (pd < o._dof_pos + np.pi / 2 - 1e-3)).all(), "the clamp is active"
+                res[dtype] = pd.numpy().copy()
+            name = "%s/%d" % (base, int(no_scale))
+            out["actions/out/" + name] = res[torch.float32]
+            worst(scat, "actions", name, res[torch.float32], res[torch.float64])
+
+
+def main():
+    model = load_baked_model()
+    out, scat, counts = {}, {"step": {}, "free": {}, "reset": {}, "actions": {}}, [0, 0]
+    for v in VARIANTS:
+        run_variant(v, model, out, scat, counts)
+    print("re-drawn: %d poses on a threshold, of %d poses" % (counts[0], counts[1]))
+    assert counts[0] <= 0.05 * counts[1], "more than 5 % of the poses were re-drawn"
+    for kind, d in scat.items():
+        for k, x in sorted(d.items()):
+            out["scatter/%s/%s" % (kind, k)] = np.float64(x)
+            print("scatter/%s/%s = %.3g" % (kind, k, x))
+    np.savez_compressed(OUT, **{k: (x if np.ndim(x) == 0 else np.ascontiguousarray(x)) for k, x in out.items()})
+    print("wrote %s (%d bytes)" % (OUT, os.path.getsize(OUT)))
+
+
+if __name__ == "__main__":
+    main()

@@ -129,6 +129,22 @@ class MvaeBuffers(C.Structure):
     _fields_ = [(k, vp) for k in MVAE_BUFFER_NAMES]
 
 
+class MvaeTargetCfg(C.Structure):
+    """v2p_mvae_target_cfg: settings of the imitation target from the motion generator's pose (v2p_mvae_target_step / _reset / _actions)."""
+    _fields_ = [("dt", C.c_float), ("fix_head_orientation", C.c_int32), ("head_body", C.c_int32), ("smpl_head", C.c_int32), ("smpl_neck", C.c_int32),
+                ("key_bodies", C.c_int32 * 4), ("smpl_parents", C.c_int32 * 24), ("smpl_of_body", C.c_int32 * 24), ("num_shapes", C.c_int32),
+                ("pd_target_base", C.c_int32), ("no_scale_action", C.c_int32)]
+
+
+MVAE_TARGET_BUFFER_NAMES = ("root_pos", "joint_rotmat", "residual_root", "ball_state", "joint_pos_bind", "env_shape_id", "target", "prev_target", "root_states",
+                            "dof_state", "rb_state", "hold_reset", "hold_progress", "hold_cur_time", "pd_action_scale", "pd_action_offset")
+PD_TARGET_BASES = {"target_pos": 0, "current_pos": 1, "none": 2}  # V2P_PD_BASE_*
+
+
+class MvaeTargetBuffers(C.Structure):
+    _fields_ = [(k, vp) for k in MVAE_TARGET_BUFFER_NAMES]
+
+
 class ContextTransform(C.Structure):
     _fields_ = [("num_ops", C.c_int32), ("ops", C.c_int32 * 3), ("mask_joints", C.c_uint32), ("noise_prob", C.c_float), ("noise_std", C.c_float),
                 ("conf_std", C.c_float), ("min_conf", C.c_float), ("drop_prob", C.c_float)]
@@ -201,6 +217,9 @@ def load():
         "v2p_tennis_task_obs": [C.POINTER(TennisCfg), C.c_int64, C.POINTER(TennisBuffers), vp, C.c_int64, vp],
         "v2p_mvae_step": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, vp, vp],
         "v2p_mvae_reset": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, C.c_int64, vp, vp, vp, vp],
+        "v2p_mvae_target_step": [C.POINTER(MvaeTargetCfg), C.c_int64, C.POINTER(MvaeTargetBuffers), vp],
+        "v2p_mvae_target_reset": [C.POINTER(MvaeTargetCfg), C.c_int64, C.POINTER(MvaeTargetBuffers), vp, C.c_int64, vp],
+        "v2p_mvae_target_actions": [C.POINTER(MvaeTargetCfg), C.c_int64, vp, C.POINTER(MvaeTargetBuffers), vp, vp],
         "v2p_env_profile_begin": [vp, C.c_int64],
         "v2p_env_profile_begin_sampled": [vp, C.c_int64, C.c_int32, C.c_int32],
         "v2p_env_profile_end": [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)],
@@ -220,7 +239,7 @@ def load():
 EXPORTED_SYMBOLS = (
     "v2p_model_create", "v2p_model_destroy", "v2p_mlib_create", "v2p_mlib_destroy", "v2p_motion_state", "v2p_reward", "v2p_reset_flags",
     "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_obs_imitation_packed_w", "v2p_policy_head_w", "v2p_policy_head_record_w", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_set_context_transform", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
-    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_mvae_step", "v2p_mvae_reset", "v2p_last_error", "v2p_abi_version",
+    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_mvae_step", "v2p_mvae_reset", "v2p_mvae_target_step", "v2p_mvae_target_reset", "v2p_mvae_target_actions", "v2p_last_error", "v2p_abi_version",
 )
 
 

@@ -8,6 +8,7 @@
 #include <new>
 
 #include "mvae_player.hpp"
+#include "mvae_target.hpp"
 #include "tennis_task.hpp"
 #include "v2p_internal.hpp"
 
@@ -336,6 +337,67 @@ int v2p_mvae_reset(const v2p_mvae_cfg* c, int64_t num_envs, const v2p_mvae_weigh
     }
     if (n_ids == 0 || num_envs == 0) return V2P_OK;
     return launch_mvae_reset(*c, num_envs, *w, *b, env_ids, n_ids, init_feature, root_xy, joint_pos_bind_rel, (hipStream_t)stream);
+}
+
+// what the three imitation-target entry points refuse (cfg and buffers common to them); `fn` names the call
+static int mvae_target_check(const char* fn, const v2p_mvae_target_cfg* c, int64_t n, const v2p_mvae_target_buffers* b) {
+    if (!c || !b) { set_error("%s: null cfg / buffers", fn); return V2P_ERR_INVALID; }
+    if (n < 0) { set_error("%s: n %lld < 0", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (!(c->dt > 0.f)) { set_error("%s: dt %g <= 0", fn, (double)c->dt); return V2P_ERR_INVALID; }
+    if (c->head_body < 0 || c->head_body >= NB || c->smpl_head < 0 || c->smpl_head >= NB || c->smpl_neck < 0 || c->smpl_neck >= NB) {
+        set_error("%s: head body %d / SMPL head %d / SMPL neck %d outside 0..%d", fn, c->head_body, c->smpl_head, c->smpl_neck, NB - 1);
+        return V2P_ERR_INVALID;
+    }
+    for (int k = 0; k < 4; ++k)
+        if (c->key_bodies[k] < 0 || c->key_bodies[k] >= NB) { set_error("%s: key body %d outside 0..%d", fn, c->key_bodies[k], NB - 1); return V2P_ERR_INVALID; }
+    unsigned seen = 0;
+    for (int s = 0; s < NB; ++s) {
+        const int par = c->smpl_parents[s], body = c->smpl_of_body[s];
+        if (s == 0 ? par != -1 : (par < 0 || par >= s)) { set_error("%s: smpl_parents[%d] = %d is no tree with parents before children", fn, s, par); return V2P_ERR_INVALID; }
+        if (body < 0 || body >= NB || (seen >> body & 1u)) { set_error("%s: smpl_of_body[%d] = %d: not a permutation of 0..%d", fn, s, body, NB - 1); return V2P_ERR_INVALID; }
+        seen |= 1u << body;
+    }
+    if (c->smpl_of_body[0] != 0) { set_error("%s: smpl_of_body[0] = %d: body 0 must be the root joint", fn, c->smpl_of_body[0]); return V2P_ERR_INVALID; }
+    if (c->smpl_of_body[c->head_body] != c->smpl_head) { set_error("%s: head body %d is not SMPL joint %d", fn, c->head_body, c->smpl_head); return V2P_ERR_INVALID; }
+    if (c->num_shapes < 1) { set_error("%s: num_shapes %d < 1", fn, c->num_shapes); return V2P_ERR_INVALID; }
+    return V2P_OK;
+}
+
+int v2p_mvae_target_step(const v2p_mvae_target_cfg* c, int64_t n, const v2p_mvae_target_buffers* b, void* stream) {
+    const int rc = mvae_target_check("v2p_mvae_target_step", c, n, b);
+    if (rc != V2P_OK) return rc;
+    if (!b->root_pos || !b->joint_rotmat || !b->joint_pos_bind || !b->target || !b->prev_target) {
+        set_error("v2p_mvae_target_step: null root_pos / joint_rotmat / joint_pos_bind / target / prev_target");
+        return V2P_ERR_INVALID;
+    }
+    if (b->target == b->prev_target) { set_error("v2p_mvae_target_step: target and prev_target are the same buffer"); return V2P_ERR_INVALID; }
+    if (c->fix_head_orientation && (!b->ball_state || !b->rb_state)) { set_error("v2p_mvae_target_step: fix_head_orientation needs ball_state and rb_state"); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    return launch_mvae_target_step(*c, n, *b, (hipStream_t)stream);
+}
+
+int v2p_mvae_target_reset(const v2p_mvae_target_cfg* c, int64_t num_envs, const v2p_mvae_target_buffers* b, const int64_t* env_ids, int64_t n_ids, void* stream) {
+    const int rc = mvae_target_check("v2p_mvae_target_reset", c, n_ids, b);
+    if (rc != V2P_OK) return rc;
+    if (num_envs < 0) { set_error("v2p_mvae_target_reset: num_envs %lld < 0", (long long)num_envs); return V2P_ERR_INVALID; }
+    if (!b->root_pos || !b->joint_rotmat || !b->joint_pos_bind || !b->target) { set_error("v2p_mvae_target_reset: null root_pos / joint_rotmat / joint_pos_bind / target"); return V2P_ERR_INVALID; }
+    if (n_ids > 0 && !env_ids) { set_error("v2p_mvae_target_reset: null env_ids"); return V2P_ERR_INVALID; }
+    if (n_ids == 0 || num_envs == 0) return V2P_OK;
+    return launch_mvae_target_reset(*c, num_envs, *b, env_ids, n_ids, (hipStream_t)stream);
+}
+
+int v2p_mvae_target_actions(const v2p_mvae_target_cfg* c, int64_t n, const float* actions_in, const v2p_mvae_target_buffers* b, float* actions_out, void* stream) {
+    const int rc = mvae_target_check("v2p_mvae_target_actions", c, n, b);
+    if (rc != V2P_OK) return rc;
+    if (c->pd_target_base != V2P_PD_BASE_TARGET_POS && c->pd_target_base != V2P_PD_BASE_CURRENT_POS && c->pd_target_base != V2P_PD_BASE_NONE) {
+        set_error("v2p_mvae_target_actions: unknown pd_target_base %d", c->pd_target_base);
+        return V2P_ERR_INVALID;
+    }
+    const void* base = c->pd_target_base == V2P_PD_BASE_TARGET_POS ? (const void*)b->target : (c->pd_target_base == V2P_PD_BASE_CURRENT_POS ? (const void*)b->dof_state : (const void*)b->pd_action_offset);
+    if (!base || (!c->no_scale_action && !b->pd_action_scale)) { set_error("v2p_mvae_target_actions: null base buffer / pd_action_scale"); return V2P_ERR_INVALID; }
+    if (n > 0 && (!actions_in || !actions_out)) { set_error("v2p_mvae_target_actions: null actions"); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    return launch_mvae_target_actions(*c, n, actions_in, *b, actions_out, (hipStream_t)stream);
 }
 
 int v2p_env_reset(v2p_env* e, const int64_t* env_ids, int64_t n, const float* motion_times, void* stream) {

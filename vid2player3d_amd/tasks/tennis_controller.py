@@ -10,8 +10,14 @@ freshly reset envs is `v2p_tennis_task_obs`.  The racket hit at more than 2 subs
 The MVAE motion generator is `vid2player3d_amd.mvae.MotionVAEPlayer` (one more launch per control step, `v2p_mvae_step`).  Attached with
 `attach_motion_generator(player)`, it is stepped by `pre_physics_step(actions)` and reset where the reference resets it, and
 `post_physics_step()` reads the swing phase and the swing type from it.  Without one, they come in as tensors from whoever drives the
-step (`post_physics_step(phase_pred, swing_type, swing_type_cycle)`).  What turns the generator's kinematic pose into the imitation
-target of the low-level policy (`post_mvae_step` / `_smpl_to_sim`) is not built yet.
+step (`post_physics_step(phase_pred, swing_type, swing_type_cycle)`).
+
+What turns the generator's kinematic pose into the imitation target of the low-level policy (`post_mvae_step` / `_smpl_to_sim`) is
+`vid2player3d_amd.mvae_target.ImitationTarget` (one more launch, `v2p_mvae_target_step`, and the imitation observation).  Attached with
+`attach_imitation_target(target)`, `pre_physics_step` ends with `post_mvae_step()`, the reset puts the humanoid into the generator's
+pose, and `physics_step(ll_actions)` steps the wrapped task on the PD targets of the low-level policy's actions: `pre_physics_step` ->
+`physics_step` -> `post_physics_step` is vid2player's control step.  Without one, every path is as before.  Not built: the dual
+controller, `random_walk_in_recovery`, `optimize_two_hand_backhand`, `update_mvae_from_sim`, the low-level policy network itself.
 
 `task_step_reference` is a numpy statement of the same step on arrays - the checker of the tests, as `ball_traj.resample_reference`
 and `body_shapes` have theirs; the product never calls it.  There is no CPU path: a CPU device or a missing library is a RuntimeError.
@@ -345,6 +351,9 @@ class TennisControllerTask:
         self._wrist_link = (wl.to(**i64) if torch.is_tensor(wl) else torch.full((n,), int(wl), **i64)).contiguous()
         self._has_init = False
         self._mvae_player = None
+        self._imitation_target = None
+        self._num_res_root_action = 0
+        self._res_root_actions = None
 
     # ------------------------------------------------------------------ the motion generator
     def attach_motion_generator(self, player):
@@ -353,37 +362,77 @@ class TennisControllerTask:
         (physics_mvae_controller.py:223) reaches the player."""
         if player.num_envs != self.num_envs or torch.device(player.device) != self.device:
             raise ValueError("attach_motion_generator: the player has %d envs on %s, the task %d on %s" % (player.num_envs, player.device, self.num_envs, self.device))
-        for key in ("random_walk_in_recovery", "add_residual_root"):
-            if self.cfg_v2p.get(key):
-                raise NotImplementedError("TennisControllerTask: %s is not built" % key)
+        self._refuse_unbuilt()
         if bool(self.cfg_v2p.get("add_residual_dof")) != player.settings["add_residual_dof"]:
             raise ValueError("attach_motion_generator: cfg v2p.add_residual_dof and the player's disagree")
+        if self._imitation_target is not None and self._imitation_target.player is not player:
+            raise ValueError("attach_motion_generator: the attached imitation target belongs to another player")
         self._mvae_player = player
         self._phase_pred, self._swing_type, self._swing_type_cycle = player._phase_pred, player._swing_type, player._swing_type_cycle
         self._num_mvae_action, self._num_res_dof_action = LATENT, 3 if player.settings["add_residual_dof"] else 0
 
+    def _refuse_unbuilt(self):
+        """(`add_residual_root` moves the target's root: it needs an imitation target, attached before the step - or before the generator)"""
+        if self.cfg_v2p.get("random_walk_in_recovery"):
+            raise NotImplementedError("TennisControllerTask: random_walk_in_recovery is not built")
+        if self.cfg_v2p.get("add_residual_root") and self._imitation_target is None:
+            raise NotImplementedError("TennisControllerTask: add_residual_root is not built without an imitation target (attach_imitation_target)")
+
+    def attach_imitation_target(self, target):
+        """Make `target` (an `ImitationTarget` around the wrapped task and the motion generator of this batch) the physics player's task
+        side of `post_mvae_step` (:264-269), of the pose reset and of the PD targets.  With cfg v2p.add_residual_root attach it before the
+        motion generator; its three action columns follow the latent and the residual DoFs."""
+        if target.task is not self.task:
+            raise ValueError("attach_imitation_target: the target wraps another task")
+        if self._mvae_player is not None and target.player is not self._mvae_player:
+            raise ValueError("attach_imitation_target: the target belongs to another player than the attached motion generator")
+        if bool(self.cfg_v2p.get("add_residual_root")) != target.settings["add_residual_root"]:
+            raise ValueError("attach_imitation_target: cfg v2p.add_residual_root and the target's disagree")
+        self._imitation_target = target
+        self._num_res_root_action = 3 if target.settings["add_residual_root"] else 0
+
     def get_action_size(self):
         if self._mvae_player is None:
             raise RuntimeError("TennisControllerTask: no motion generator is attached")
-        return self._num_mvae_action + self._num_res_dof_action
+        return self._num_mvae_action + self._num_res_dof_action + self._num_res_root_action
 
     def pre_physics_step(self, actions):
         """pre_physics_step (:247-263): the latent and the residual-DoF part of the policy's actions, scaled, drive one step of the motion
-        generator.  (`post_mvae_step`, which hands the pose to the physics task, is not built.)"""
+        generator; with an imitation target attached `post_mvae_step()` then hands the pose to the physics task (:264-269)."""
         if self._mvae_player is None:
             raise RuntimeError("TennisControllerTask.pre_physics_step: no motion generator is attached (attach_motion_generator)")
-        for key in ("random_walk_in_recovery", "add_residual_root"):
-            if self.cfg_v2p.get(key):
-                raise NotImplementedError("TennisControllerTask: %s is not built" % key)
-        nz, nr = self._num_mvae_action, self._num_res_dof_action
-        if actions.dim() != 2 or actions.shape[0] != self.num_envs or actions.shape[1] < nz + nr:
-            raise ValueError("pre_physics_step: actions must be [%d, >= %d]" % (self.num_envs, nz + nr))
+        self._refuse_unbuilt()
+        nz, nr, nroot = self._num_mvae_action, self._num_res_dof_action, self._num_res_root_action
+        if actions.dim() != 2 or actions.shape[0] != self.num_envs or actions.shape[1] < nz + nr + nroot:
+            raise ValueError("pre_physics_step: actions must be [%d, >= %d]" % (self.num_envs, nz + nr + nroot))
         self._actions = actions.clone()
         self._mvae_actions = actions[:, :nz].clone() * self.cfg_v2p.get("vae_action_scale", 1.0)
         self._res_dof_actions = torch.empty(0, device=self.device)
         if nr:
             self._res_dof_actions = actions[:, nz:nz + nr].clone() * self.cfg_v2p.get("residual_dof_scale", 0.1)
         self._mvae_player.step(self._mvae_actions, self._res_dof_actions)
+        if self._imitation_target is not None:
+            self._res_root_actions = None
+            if nroot:
+                self._res_root_actions = actions[:, nz + nr:nz + nr + nroot].clone() * self._imitation_target.settings["residual_root_scale"]
+            self.post_mvae_step()
+
+    def post_mvae_step(self):
+        """`HumanoidSMPLIMMVAE.post_mvae_step` (humanoid_smpl_im_mvae.py:593-598): the new imitation target and the low-level policy's
+        observation (`_imitation_target.obs_buf`)."""
+        if self._imitation_target is None:
+            raise RuntimeError("TennisControllerTask.post_mvae_step: no imitation target is attached (attach_imitation_target)")
+        if self._num_res_root_action and self._res_root_actions is None:
+            raise RuntimeError("TennisControllerTask.post_mvae_step: add_residual_root needs the actions of a pre_physics_step first")
+        self._imitation_target.step(self._res_root_actions)
+        self._imitation_target.compute_observations()
+
+    def physics_step(self, ll_actions):
+        """The physics player's control step on the low-level policy's actions [N,75]: `_action_to_pd_targets` (the engine clamps), then
+        the wrapped task's step."""
+        if self._imitation_target is None:
+            raise RuntimeError("TennisControllerTask.physics_step: no imitation target is attached (attach_imitation_target)")
+        self.task.step(self._imitation_target.actions(ll_actions))
 
     # ------------------------------------------------------------------ sizes
     def get_actor_obs_size(self):
@@ -431,6 +480,8 @@ class TennisControllerTask:
             self._reset_env_tensors(env_ids)
             if self._mvae_player is not None:
                 self._mvae_player.reset(env_ids)  # (:182-183)
+                if self._imitation_target is not None:
+                    self._imitation_target.reset(env_ids)  # (`_reset_actors` of the physics player's task, :186)
             self._num_reset[env_ids] += 1
         if len(reaction_ids) > 0:
             new_traj = self.task.reset_balls(reaction_ids)
