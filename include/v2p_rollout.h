@@ -629,6 +629,58 @@ int v2p_tennis_task_step(const v2p_tennis_cfg* cfg, int64_t n, const v2p_tennis_
 int v2p_tennis_task_obs(const v2p_tennis_cfg* cfg, int64_t num_envs, const v2p_tennis_buffers* buffers, const int64_t* env_ids, int64_t n_ids,
                         void* stream);
 
+/* ---- the two-player rally (vid2player/env/tasks/physics_mvae_controller_dual.py: PhysicsMVAEControllerDual; envs 2k and 2k+1 are
+ * opponents, utils/common.py:111-115): the task step with the dual reset law, and the ball hand-over that turns one player's hit into
+ * the other's incoming ball (humanoid_smpl_im_mvae_dual.py:65-79 `_reset_balls`, utils/tennis_ball_in_estimator.py:48-79 `estimate`).
+ * Both reuse v2p_tennis_cfg / v2p_tennis_buffers; what the hand-over writes of buffers that the step only reads comes again, writable,
+ * in v2p_tennis_dual_buffers (the same memory). */
+typedef struct {
+    float grip_normal[2][3];        /* racket normal in the wrist frame of even / odd envs (the reference's `grip` list,
+                                     * humanoid_smpl_im_mvae.py:839-842); v2p_tennis_cfg.grip_normal is not read */
+    /* the in-estimator: grids as (lo, hi, step) in the order HEIGHT, VEL_X, VEL_Y, VSPIN (tennis_ball_in_estimator.py:10-14) and the
+     * shape of its table [B,F,2] (distance along the launch direction, height) */
+    double in_grid[4][3];
+    int64_t in_rows;                /* B */
+    int32_t in_frames;              /* F, 1..100 */
+} v2p_tennis_dual_cfg;
+typedef struct {                    /* DEVICE buffers of the hand-over */
+    const float* traj_in;           /* [B,F,2] read only */
+    const float* target_draw;       /* [N] read only: the caller's uniform draws of the three-way target (use_random_ball_target), else nullable */
+    float* ball_state;              /* [N,13] */
+    uint8_t* has_bounce;            /* [N] */
+    float* bounce_pos;              /* [N,3] */
+    int64_t* tar_action;            /* [N] */
+    float* target_bounce_pos;       /* [N,3] (use_random_ball_target) */
+    float* ball_traj;               /* [N,100,3] (nullable with use_history_ball_obs: the window is then not kept) */
+    int64_t* num_reset_reaction;    /* [N] */
+} v2p_tennis_dual_buffers;
+/* One control step of the task for the n (even) envs of a two-player batch: v2p_tennis_task_step - counters, racket-hit rule,
+ * _update_state, reward, observation, window advance - with three differences.  No out-estimator (physics_mvae_controller.py:73, 299):
+ * est_* and vel_x_overflow are neither read for a lookup nor written, traj_out_x / _y and cfg->grid are not read; return_w_estimate
+ * rewards with what est_* hold.  The racket normal uses dual->grip_normal[env & 1].  The reset law is the dual one (:96-121):
+ * reset_recovery = tar_action==1 & (hit | ball_y < root_y-1 | (has_bounce & ball_z < 0.05)); reset_reaction = the opponent's
+ * reset_recovery; terminate = (reset_recovery & ~hit) | (tar_action==0 & has_bounce & ~bounce_in), OR-ed over the pair; terminated envs
+ * get reset = 1 and both flags 0; reset is otherwise left alone, `terminate`, tar_time_total, court_min / _max, max_episode_length and
+ * enable_early_termination are not used.  No host synchronisation (the reference has terminate.sum() > 0).
+ * Refused before any HIP call (V2P_ERR_INVALID, a message that names the call): odd n, null dual, and what v2p_tennis_task_step refuses
+ * of what is read here. */
+int v2p_tennis_dual_step(const v2p_tennis_cfg* cfg, const v2p_tennis_dual_cfg* dual, int64_t n, const v2p_tennis_buffers* buffers,
+                         const char** sub_rewards_names, void* stream);
+/* The flag-driven half of the dual `_reset_envs` (:42-64, training mode) for all n / 2 pairs in one launch, without an id list, a host
+ * synchronisation or an allocation; one wavefront per pair.  For every env whose reset_reaction is set, in the reference's order: the
+ * in-estimator on the OPPONENT's ball state; the table row's F frames, transformed and mirrored, become frames 0..F-1 of the env's
+ * ball_traj in front of frames F..99 of its current window, traj_cursor = 0; ball_state = ball_states_in, the opponent's =
+ * ball_states_out (where both react, out wins, and - the reference sorts its opponent list, utils/common.py:111-115 - each flies the
+ * table row of its OWN state); has_bounce, bounce_pos, has_racket_contact cleared, prev_ball_vy = the new vy.  Then
+ * _reset_recovery_tasks of envs with reset_recovery (tar_action = 0, has_bounce, bounce_pos cleared), the dual _reset_reaction_tasks
+ * (tar_time = 0, tar_action = 1, num_reset_reaction += 1, bounce_in = 0, est_* = 0 with return_w_estimate, the history fill with
+ * use_history_ball_obs, target_bounce_pos from target_draw: < 0.33 left, > 0.67 right, else middle) and the observation row of the
+ * reacting envs (history roll, racket_pos, racket_normal included).  The flags are read, not cleared.  Envs without a flag in their
+ * pair keep every bit.  Refused before any HIP call: odd n, null dual / dual_buffers or a null required pointer, F outside 1..100, a
+ * table without rows, a grid that is not (lo < hi, step > 0), use_random_ball_target without target_draw. */
+int v2p_tennis_dual_handover(const v2p_tennis_cfg* cfg, const v2p_tennis_dual_cfg* dual, int64_t n, const v2p_tennis_buffers* buffers,
+                             const v2p_tennis_dual_buffers* dual_buffers, void* stream);
+
 /* ---- the MotionVAE motion generator of a control step (vid2player/players/mvae_player.py `MVAEPlayer.step` / `reset` around
  * motion_vae/model.py:186-252 `MixedDecoder.forward`): the gate, the three expert-blended layers and the player's state update
  * (`_update_mvae_state`) in ONE launch, without a host synchronisation or an allocation.  The decoder computes every expert and blends

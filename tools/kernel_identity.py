@@ -12,11 +12,13 @@ consecutive numbers) moves by the same amount: these are the block numbers throu
 unrolled loop, and they move when source lines that compile to nothing in a kernel (the cycle counters of the diagnostic
 instantiation) add blocks in front of it.  (A constant of another meaning inside that range that moved by the same amount would pass
 too; the range is a few numbers wide.)
+The kernels of tennis_task.hip are known too (tennis_task_kernel<STEP, DUAL>, tennis_handover_kernel).  A kernel that only
+the new listing has is reported and does not count as a difference; one that only the old listing has does.
 usage: tools/kernel_identity.py <old.s>[,<old2.s>...] <new.s>[,<new2.s>...]   (a kernel is looked up in every listing of its side)"""
 import re
 import sys
 
-KERNELS = re.compile(r"^(_ZN\w*?(physics_ll_kernelI\w+?EEv|env_pre_kernelE|pair_scatter_kernelE)\w*):")
+KERNELS = re.compile(r"^(_ZN\w*?(physics_ll_kernelI\w+?EEv|env_pre_kernelE|pair_scatter_kernelE|tennis_task_kernelI\w+?EEv|tennis_handover_kernelE)\w*):")
 # the enclosing namespaces: v2p, v2p::ll_lds, v2p::ll_regs, or v2p itself renamed with a suffix (how the register object was built
 # before the kernel had a namespace per build): _ZN3v2p17..., _ZN3v2p6ll_lds17..., _ZN3v2p7ll_regs17... -> _ZN@17...
 NAMESPACES = re.compile(r"_ZN\d+v2p(?:_[a-z]+)?(?:\d+ll_[a-z]+)?")
@@ -42,6 +44,8 @@ def kernels(paths):
             name = m.group(2)
             if name.startswith("physics_ll_kernel"):  # template flags CONTACT MULTI TGS DIAG BALL JOBS LIMITS VFRIC
                 name = "physics_ll_kernel<" + "".join(re.findall(r"Lb([01])E", name)) + ">"
+            elif name.startswith("tennis_task_kernel"):  # template flags STEP DUAL (DUAL came later: a listing without it is DUAL = 0)
+                name = "tennis_task_kernel<" + "".join(re.findall(r"Lb([01])E", name)).ljust(2, "0") + ">"
             else:
                 name = name[:-1]
             # the code runs up to the kernel descriptor; the resource comments follow the function
@@ -49,7 +53,7 @@ def kernels(paths):
             body = [n for n in map(norm, lines[i + 1:end]) if n and not n.startswith((".file", ".loc", ".cfi"))]
             insts = [n for n in body if not n.endswith(":") and not n.startswith(".")]
             k = next(k for k in range(end, len(lines)) if lines[k].lstrip().startswith(".end_amdhsa_kernel"))
-            desc = [norm(n) for n in lines[end:k]]
+            desc = [norm(n.replace(m.group(1), "@KERNEL")) for n in lines[end:k]]  # (the symbol carries the template's parameter list)
             res = {}
             while len(res) < len(RESOURCES):
                 k += 1
@@ -94,7 +98,7 @@ bad = 0
 for name in sorted(set(old) | set(new)):
     if name not in old or name not in new:
         print("%-40s only in the %s listing" % (name, "old" if name in old else "new"))
-        bad += 1
+        bad += name in old
         continue
     (b0, n0, d0, r0), (b1, n1, d1, r1) = old[name], new[name]
     shift = None if b0 == b1 else dispatch_shift(b0, b1)

@@ -297,6 +297,61 @@ int v2p_tennis_task_obs(const v2p_tennis_cfg* c, int64_t num_envs, const v2p_ten
     return launch_tennis_task_obs(*c, num_envs, *b, env_ids, n_ids, (hipStream_t)stream);
 }
 
+// what both entry points of the two-player batch refuse
+static int tennis_dual_check(const char* fn, const v2p_tennis_cfg* c, const v2p_tennis_dual_cfg* dc, int64_t n, const v2p_tennis_buffers* b) {
+    if (!c || !dc || !b) { set_error("%s: null cfg / dual cfg / buffers", fn); return V2P_ERR_INVALID; }
+    if (n < 0) { set_error("%s: n %lld < 0", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (n % 2) { set_error("%s: n %lld is odd (envs 2k and 2k+1 are opponents)", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (c->obs_ball_traj_length < 1 || c->obs_ball_traj_length > V2P_TENNIS_TRAJ_FRAMES) {
+        set_error("%s: obs_ball_traj_length %d outside 1..%d", fn, c->obs_ball_traj_length, V2P_TENNIS_TRAJ_FRAMES);
+        return V2P_ERR_INVALID;
+    }
+    if (c->reward_type < V2P_TENNIS_REWARD_REACH || c->reward_type > V2P_TENNIS_REWARD_RETURN_W_ESTIMATE) {
+        set_error("%s: unknown reward type %d", fn, c->reward_type);
+        return V2P_ERR_INVALID;
+    }
+    if (n == 0) return V2P_OK;
+    // the observation's buffers, which both launches write
+    bool ok = b->rb_state && b->root_states && b->racket_state && b->ball_state && b->wrist_link && b->obs && b->racket_pos && b->racket_normal;
+    ok = ok && (c->use_history_ball_obs ? b->ball_obs != nullptr : (b->ball_traj && b->traj_cursor));
+    ok = ok && (!c->use_random_ball_target || b->target_bounce_pos);
+    ok = ok && b->reset_reaction && b->reset_recovery && b->has_racket_contact && b->tar_time && b->prev_ball_vy && b->bounce_in;
+    ok = ok && (c->reward_type != V2P_TENNIS_REWARD_RETURN_W_ESTIMATE || (b->est_bounce_pos && b->est_bounce_time && b->est_max_height && b->est_bounce_in));
+    if (!ok) { set_error("%s: null buffer", fn); return V2P_ERR_INVALID; }
+    return V2P_OK;
+}
+
+int v2p_tennis_dual_step(const v2p_tennis_cfg* c, const v2p_tennis_dual_cfg* dc, int64_t n, const v2p_tennis_buffers* b, const char** names, void* stream) {
+    const char* fn = "v2p_tennis_dual_step";
+    const int rc = tennis_dual_check(fn, c, dc, n, b);
+    if (rc != V2P_OK) return rc;
+    if (names) *names = c->reward_type == V2P_TENNIS_REWARD_REACH ? "pos_reward" : "pos_reward,ball_pos_reward";
+    if (n == 0) return V2P_OK;
+    bool ok = b->has_bounce && b->has_bounce_now && b->bounce_pos && b->phase_pred && b->tar_action && b->target_bounce_pos && b->has_racket_contact_now &&
+              b->progress && b->est_bounce_pos && b->est_bounce_time && b->est_max_height && b->est_bounce_in && b->distance && b->rew && b->sub_rewards && b->reset;
+    ok = ok && (c->reward_type == V2P_TENNIS_REWARD_RETURN_W_ESTIMATE ? b->swing_type_cycle != nullptr : b->swing_type != nullptr);
+    if (!ok) { set_error("%s: null buffer", fn); return V2P_ERR_INVALID; }
+    return launch_tennis_dual_step(*c, *dc, n, *b, (hipStream_t)stream);
+}
+
+int v2p_tennis_dual_handover(const v2p_tennis_cfg* c, const v2p_tennis_dual_cfg* dc, int64_t n, const v2p_tennis_buffers* b, const v2p_tennis_dual_buffers* db,
+                             void* stream) {
+    const char* fn = "v2p_tennis_dual_handover";
+    const int rc = tennis_dual_check(fn, c, dc, n, b);
+    if (rc != V2P_OK) return rc;
+    if (!db) { set_error("%s: null dual buffers", fn); return V2P_ERR_INVALID; }
+    if (dc->in_frames < 1 || dc->in_frames > V2P_TENNIS_TRAJ_FRAMES) { set_error("%s: in_frames %d outside 1..%d", fn, dc->in_frames, V2P_TENNIS_TRAJ_FRAMES); return V2P_ERR_INVALID; }
+    if (dc->in_rows < 1 || dc->in_rows > INT32_MAX) { set_error("%s: the in-estimator's table has %lld rows (1..2^31-1)", fn, (long long)dc->in_rows); return V2P_ERR_INVALID; }
+    for (int g = 0; g < 4; ++g)
+        if (!(dc->in_grid[g][2] > 0.0) || !(dc->in_grid[g][1] > dc->in_grid[g][0])) { set_error("%s: in_grid %d is not (lo < hi, step > 0)", fn, g); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    if (c->use_random_ball_target && !db->target_draw) { set_error("%s: use_random_ball_target needs target_draw", fn); return V2P_ERR_INVALID; }
+    bool ok = db->traj_in && db->ball_state && db->has_bounce && db->bounce_pos && db->tar_action && db->num_reset_reaction;
+    ok = ok && (c->use_history_ball_obs || db->ball_traj) && (!c->use_random_ball_target || db->target_bounce_pos);
+    if (!ok) { set_error("%s: null dual buffer", fn); return V2P_ERR_INVALID; }
+    return launch_tennis_dual_handover(*c, *dc, n, *b, *db, (hipStream_t)stream);
+}
+
 // what both motion-generator entry points refuse; `step`: the decoder's weights are required too
 static int mvae_check(const char* fn, const v2p_mvae_cfg* c, int64_t n, const v2p_mvae_weights* w, const v2p_mvae_buffers* b, bool step) {
     if (!c || !w || !b) { set_error("%s: null cfg / weights / buffers", fn); return V2P_ERR_INVALID; }

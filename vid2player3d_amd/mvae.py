@@ -5,7 +5,7 @@ One control step - the gate, the three expert-blended layers and the player's st
 `v2p_mvae_step` (csrc/mvae_player.hip); `reset(env_ids)` is `v2p_mvae_reset`.  The decoder computes every expert and blends the results,
 out = sum_e c_e (x W_e + b_e), which is the function the reference computes by blending the weights per env; fp32 throughout (the
 reference runs the decoder under autocast on CUDA - a reduced-precision path is not built).  Only the shipped architecture
-is built: frame 288, latent 32, hidden 256, 6 experts, gate 64, one condition frame, one prediction, predicted phase; dual mode is not.
+is built: frame 288, latent 32, hidden 256, 6 experts, gate 64, one condition frame, one prediction, predicted phase; of dual mode, `True` (`reset_dual`) is, `different` is not.
 
 `mvae_step_reference` / `mvae_reset_reference` are the numpy statement of the same two calls on arrays - the checker of the tests, as
 `tennis_controller.task_step_reference` is for the task step; the product never calls them.  There is no CPU path: a CPU device or a
@@ -45,9 +45,11 @@ RESIDUAL_RULES = {
 
 def player_settings(cfg, is_train):
     """What both the kernel's v2p_mvae_cfg and the numpy statement are made from.  cfg: the reference's cfg_v2p keys `player`, `righthand`,
-    `add_residual_dof` (and, refused when they ask for what is not built: `dual_mode`, `predict_phase`, the sizes of another option set)."""
+    `add_residual_dof` (and, refused when they ask for what is not built: `dual_mode: different` - two weight sets per batch -,
+    `predict_phase`, the sizes of another option set).  `dual_mode: True` (one generator for both sides of every pair) is the single
+    player's generator with two sets of initial frames, `reset_dual`."""
     cfg = dict(cfg)
-    if cfg.get("dual_mode"):
+    if cfg.get("dual_mode") and cfg["dual_mode"] is not True:
         raise NotImplementedError("MotionVAEPlayer: dual_mode is not built")
     if cfg.get("player") not in PLAYERS:
         raise ValueError("MotionVAEPlayer: cfg player %r is none of %s" % (cfg.get("player"), sorted(PLAYERS)))
@@ -323,13 +325,25 @@ def mvae_reset_reference(st, avg, std, s, env_ids, init_feature, root_xy, joint_
     return o
 
 
+def dual_reset_rows(reset_reaction_env_ids, reset_recovery_env_ids):
+    """Which envs `reset_dual` (mvae_player.py:167-182) resets and from which frame: (ids ascending, from_ready [len(ids)] bool - True:
+    the ready frame of a reaction id, False: the serve frame of a recovery id).  An id in both lists takes the serve frame, which the
+    reference writes last - and appears ONCE here, where the reference's `cat(...).sort()` keeps it twice (and draws two root positions for
+    it, the second of which stays).  The dual controller's `reset(ids)` never names an env on both sides."""
+    rea, rec = np.asarray(reset_reaction_env_ids, dtype=np.int64).reshape(-1), np.asarray(reset_recovery_env_ids, dtype=np.int64).reshape(-1)
+    ids = np.unique(np.concatenate([rea, rec]))
+    return ids, ~np.isin(ids, rec)
+
+
 # ------------------------------------------------------------------------------------------------------------------ the player
 class MotionVAEPlayer:
     """`MVAEPlayer` on the device, single player.  Attribute names are the reference's.  cfg: `player`, `righthand`, `add_residual_dof`,
     `test_mode`; weights: weights_from_state_dict(...); avg, std [288]; init_data [M,1,288] or [M,288] (`vae_init_conditions`: fewer rows
-    than envs repeat the first row, as the reference does); joint_pos_bind_rel [24,3] of the player's SMPL body."""
+    than envs repeat the first row, as the reference does); joint_pos_bind_rel [24,3] of the player's SMPL body.  With cfg `dual_mode: True`
+    init_data_ready and init_data_serve (`vae_init_conditions_ready` / `_serve`, mvae_player.py:122-128: the first row of each, for every
+    env) are required, and `reset_dual` resets whole pairs from them."""
 
-    def __init__(self, cfg, num_envs, weights, avg, std, init_data, joint_pos_bind_rel, is_train, device):
+    def __init__(self, cfg, num_envs, weights, avg, std, init_data, joint_pos_bind_rel, is_train, device, init_data_ready=None, init_data_serve=None):
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("MotionVAEPlayer: the motion generator is a HIP kernel - it must live on a GPU (no CPU fallback)")
@@ -344,6 +358,12 @@ class MotionVAEPlayer:
         init = torch.as_tensor(np.asarray(init_data, dtype=np.float32) if not torch.is_tensor(init_data) else init_data).to(**f)
         init = init.reshape(len(init), -1, FRAME)[:, -1]
         self._init_data = (init[:1].repeat(n, 1) if len(init) < n else init[:n]).contiguous()
+        self._init_data_ready = self._init_data_serve = None
+        if self.cfg.get("dual_mode"):
+            if init_data_ready is None or init_data_serve is None:
+                raise ValueError("MotionVAEPlayer: dual_mode needs init_data_ready and init_data_serve")
+            first = lambda d: torch.as_tensor(np.asarray(d, dtype=np.float32) if not torch.is_tensor(d) else d).to(**f).reshape(len(d), -1, FRAME)[:1, -1].repeat(n, 1).contiguous()
+            self._init_data_ready, self._init_data_serve = first(init_data_ready), first(init_data_serve)
         self._joint_pos_bind_rel = torch.as_tensor(np.asarray(joint_pos_bind_rel, dtype=np.float32)).to(**f).reshape(NUM_JOINTS, 3).contiguous()
         self._conditions = torch.zeros((n, 1, FRAME), **f)
         self._root_pos, self._root_vel = torch.zeros((n, 3), **f), torch.zeros((n, 3), **f)
@@ -371,7 +391,7 @@ class MotionVAEPlayer:
     def draw_root_xy(self, count):
         """The start of a player near the baseline's centre (mvae_player.py:230-236): a draw, or the centre when evaluating in a test mode
         other than `random`."""
-        if self._is_train or self.cfg.get("test_mode", "random") == "random":
+        if self._is_train or self.cfg.get("test_mode", "random") == "random" or self.cfg.get("dual_mode"):  # (the reference: `is not None`, mvae_player.py:230 - a cfg that says `dual_mode: False` keeps what it did here)
             return (torch.rand((count, 2), device=self.device) - 0.5) * torch.tensor([2.0, 1.5], device=self.device) + torch.tensor([0.0, -13.0], device=self.device)
         return torch.tensor([0.0, -13.0], device=self.device).repeat(count, 1)
 
@@ -379,9 +399,26 @@ class MotionVAEPlayer:
         ids = torch.as_tensor(env_ids, device=self.device, dtype=torch.long).contiguous()
         if ids.numel() == 0:
             return
+        self._reset_rows(ids, self._init_data[ids.clamp(0, self.num_envs - 1)].contiguous(), root_xy)
+
+    def reset_dual(self, reset_reaction_env_ids, reset_recovery_env_ids, root_xy=None):
+        """`reset_dual` (mvae_player.py:167-182) with `dual_mode: True`: the envs of both lists, in ascending order, start from the ready
+        frame (reaction ids: the receivers) or the serve frame (recovery ids: the servers) through the launch of `reset`.  root_xy
+        [len(both),2], in that ascending order, replaces the draw near the baseline's centre."""
+        if self._init_data_ready is None:
+            raise RuntimeError("MotionVAEPlayer.reset_dual: the player was not made with cfg dual_mode: True")
+        as_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else x
+        ids, from_ready = dual_reset_rows(as_np(reset_reaction_env_ids), as_np(reset_recovery_env_ids))
+        if len(ids) == 0:
+            return
+        ids = torch.from_numpy(ids).to(self.device)
+        rows = ids.clamp(0, self.num_envs - 1)
+        feature = torch.where(torch.from_numpy(from_ready).to(self.device).view(-1, 1), self._init_data_ready[rows], self._init_data_serve[rows])
+        self._reset_rows(ids.contiguous(), feature.contiguous(), root_xy)
+
+    def _reset_rows(self, ids, feature, root_xy):
         xy = self.draw_root_xy(ids.numel()) if root_xy is None else torch.as_tensor(root_xy, dtype=torch.float32, device=self.device)
         xy = xy.to(torch.float32).reshape(ids.numel(), 2).contiguous()
-        feature = self._init_data[ids.clamp(0, self.num_envs - 1)].contiguous()
         b = self._buffers()
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().v2p_mvae_reset(C.byref(self._cfg_struct), self.num_envs, C.byref(self._weights_struct), C.byref(b), _lib.ptr(ids), int(ids.numel()),

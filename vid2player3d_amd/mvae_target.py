@@ -52,7 +52,7 @@ def target_settings(cfg_v2p, cfg_env, control_dt, body_names, parents, key_body_
     """What both the kernel's v2p_mvae_target_cfg and the numpy statement are made from.  cfg_v2p: the reference's `fix_head_orientation`,
     `add_residual_root`, `residual_root_scale` (and `dual_mode`, refused); cfg_env: `pd_target_base`, `no_scale_action` (and `obs_type`)."""
     v2p, env = dict(cfg_v2p or {}), dict(cfg_env or {})
-    if v2p.get("dual_mode"):
+    if v2p.get("dual_mode") and v2p["dual_mode"] is not True:  # (`True`: both sides of a pair share one tree and one body - the single target)
         raise NotImplementedError("ImitationTarget: dual_mode is not built")
     if env.get("obs_type", "joint_pos_and_angle") != "joint_pos_and_angle":
         raise NotImplementedError("ImitationTarget: obs_type %r is not built (only joint_pos_and_angle)" % (env.get("obs_type"),))

@@ -16,8 +16,8 @@ What turns the generator's kinematic pose into the imitation target of the low-l
 `vid2player3d_amd.mvae_target.ImitationTarget` (one more launch, `v2p_mvae_target_step`, and the imitation observation).  Attached with
 `attach_imitation_target(target)`, `pre_physics_step` ends with `post_mvae_step()`, the reset puts the humanoid into the generator's
 pose, and `physics_step(ll_actions)` steps the wrapped task on the PD targets of the low-level policy's actions: `pre_physics_step` ->
-`physics_step` -> `post_physics_step` is vid2player's control step.  Without one, every path is as before.  Not built: the dual
-controller, `random_walk_in_recovery`, `optimize_two_hand_backhand`, `update_mvae_from_sim`, the low-level policy network itself.
+`physics_step` -> `post_physics_step` is vid2player's control step.  Without one, every path is as before.  The dual controller is
+`tasks.tennis_controller_dual.DualTennisControllerTask`.  Not built: `random_walk_in_recovery`, `optimize_two_hand_backhand`, `update_mvae_from_sim`, the low-level policy network itself.
 
 `task_step_reference` is a numpy statement of the same step on arrays - the checker of the tests, as `ball_traj.resample_reference`
 and `body_shapes` have theirs; the product never calls it.  There is no CPU path: a CPU device or a missing library is a RuntimeError.
@@ -293,8 +293,7 @@ class TennisControllerTask:
 
     def __init__(self, task, cfg, params=traj_out_params):
         env, v2p = dict(cfg.get("env") or {}), dict(cfg.get("v2p") or {})
-        if v2p.get("dual_mode") or getattr(task, "racket_players", None) is not None:
-            raise NotImplementedError("TennisControllerTask: dual_mode (the two-player controller and its ball hand-over) is not built")
+        self._check_mode(task, v2p)
         if not hasattr(task, "_ball_root_states"):
             raise TypeError("TennisControllerTask wraps a HumanoidSMPLIMRacketBall")
         dev = torch.device(task.device)
@@ -310,17 +309,14 @@ class TennisControllerTask:
         self.settings = task_settings(reward_type=v2p.get("reward_type", "return"), obs_ball_traj_length=v2p.get("obs_ball_traj_length", 100),
                                       use_history_ball_obs=v2p.get("use_history_ball_obs", False), use_random_ball_target=v2p.get("use_random_ball_target", False),
                                       contact_by_velocity=task.sim_params.substeps > 2, enable_early_termination=self._enable_early_termination,
-                                      max_episode_length=self._max_episode_length, grip=v2p.get("grip", "eastern"), court_min=v2p["court_min"], court_max=v2p["court_max"],
+                                      max_episode_length=self._max_episode_length, grip=self._grip(v2p), court_min=v2p["court_min"], court_max=v2p["court_max"],
                                       reward_scales=v2p.get("reward_scales"), reward_weights=v2p.get("reward_weights"), grids=grids_of(params))
         st = self.settings
         self._obs_ball_traj_length = st["L"]
         n = self.num_envs
         f, i64, bl = dict(dtype=torch.float32, device=dev), dict(dtype=torch.long, device=dev), dict(dtype=torch.bool, device=dev)
         load = lambda t: torch.from_numpy(np.load(t) if isinstance(t, str) else np.ascontiguousarray(t)).to(**f).contiguous()
-        self._ball_traj_out_x = load(v2p.get("ball_traj_out_x_file", "vid2player/data/ball_traj_out_x_v0.npy"))
-        self._ball_traj_out_y = load(v2p.get("ball_traj_out_y_file", "vid2player/data/ball_traj_out_y_v0.npy"))
-        if self._ball_traj_out_x.dim() != 2 or self._ball_traj_out_y.dim() != 3 or len(self._ball_traj_out_x) != len(self._ball_traj_out_y):
-            raise ValueError("the outgoing tables must be [B,nx] and [B,ny,2]")
+        self._load_tables(v2p, load)
         self.num_obs = obs_width(st)
         self.obs_buf = torch.zeros((n, self.num_obs), **f)
         self.rew_buf = torch.zeros(n, **f)
@@ -354,6 +350,23 @@ class TennisControllerTask:
         self._imitation_target = None
         self._num_res_root_action = 0
         self._res_root_actions = None
+
+    def _check_mode(self, task, v2p):
+        if v2p.get("dual_mode") or getattr(task, "racket_players", None) is not None:
+            raise NotImplementedError("TennisControllerTask: dual_mode (the two-player controller and its ball hand-over) is not built here: "
+                                      "tasks.tennis_controller_dual.DualTennisControllerTask")
+
+    def _grip(self, v2p):
+        return v2p.get("grip", "eastern")
+
+    def _load_tables(self, v2p, load):
+        self._ball_traj_out_x = load(v2p.get("ball_traj_out_x_file", "vid2player/data/ball_traj_out_x_v0.npy"))
+        self._ball_traj_out_y = load(v2p.get("ball_traj_out_y_file", "vid2player/data/ball_traj_out_y_v0.npy"))
+        if self._ball_traj_out_x.dim() != 2 or self._ball_traj_out_y.dim() != 3 or len(self._ball_traj_out_x) != len(self._ball_traj_out_y):
+            raise ValueError("the outgoing tables must be [B,nx] and [B,ny,2]")
+
+    def _launch_step(self):
+        return launch_step(self.settings, self._tensors(), self.num_envs)
 
     # ------------------------------------------------------------------ the motion generator
     def attach_motion_generator(self, player):
@@ -549,7 +562,7 @@ class TennisControllerTask:
             self._swing_type.copy_(swing_type)
         if swing_type_cycle is not None:
             self._swing_type_cycle.copy_(swing_type_cycle)
-        self._sub_rewards_names = launch_step(self.settings, self._tensors(), self.num_envs)
+        self._sub_rewards_names = self._launch_step()
         self.extras["terminate"] = self._terminate_buf
         self.extras["sub_rewards"] = self._sub_rewards
         self.extras["sub_rewards_names"] = self._sub_rewards_names
