@@ -743,6 +743,36 @@ int v2p_mvae_reset(const v2p_mvae_cfg* cfg, int64_t num_envs, const v2p_mvae_wei
                    int64_t n_ids, const float* init_feature /*[n_ids,288]*/, const float* root_xy /*[n_ids,2]*/, const float* joint_pos_bind_rel /*[24,3]*/,
                    void* stream);
 
+/* ---- the motion generator of a two-player batch (`MVAEPlayer` with cfg `dual_mode: different`, mvae_player.py:23-57, 167-199): env 2k
+ * is side 0 and env 2k+1 side 1; each side has its own decoder weights, normalisation statistics, playing hand and player rule, the
+ * state is one set of buffers.  A row's side is its parity: nothing is read back to the host. */
+typedef struct {             /* the ONE racket object of the batch (:56-57): the server's hand and grip, walked by every reset env */
+    int32_t righthand;       /* which arm the FK chain takes (utils/racket.py:152-161) */
+    float dir[3];            /* canonical racket direction in the wrist's frame: (-1, 0, 0) for both grips (utils/racket.py:10-32) */
+    float normal[3];         /* canonical racket normal: eastern (0, 1, 0), semi_western (0, 1, 1) normalised as F.normalize does */
+} v2p_mvae_racket;
+enum { V2P_MVAE_DUAL_MAP_PARITY = 0,   /* workgroup b serves side b & 1 */
+       V2P_MVAE_DUAL_MAP_HALVES = 1 }; /* the grid's first half serves side 0, its second half side 1: the mapping the player uses -
+                                        * 3.0 % faster at 8192 envs, 1.6 % slower at 1024 (profiles/r27a_mvae_dual_bench.log); both
+                                        * stay callable so that the choice can be measured again */
+/* `MVAEPlayer.step` under `_is_dual` for envs 0 .. n-1, n even, in ONE launch of 2 ceil(n / 64) workgroups, each of 32 envs of one
+ * side.  cfg[2], weights[2]: side 0, side 1 (is_train and add_residual_dof must agree).  Per side: the decoder's weights, avg and std of
+ * the unnormalised feature, righthand in the swing-type rule, the player's residual table and the elbow / wrist joints it rewrites.
+ * One quirk of the reference is reproduced: the root-position columns 0:3 of EVERY env's condition are normalised with side 1's avg and
+ * std (:254-262 writes all envs, and side 1's call runs last).  mapping: V2P_MVAE_DUAL_MAP_*; both give the same numbers, bit for bit.  Refusals as
+ * v2p_mvae_step, and: an odd n, cfgs that disagree on is_train or add_residual_dof, an unknown mapping. */
+int v2p_mvae_dual_step(const v2p_mvae_cfg* cfg /*[2]*/, int64_t n, const v2p_mvae_weights* weights /*[2]*/, const v2p_mvae_buffers* buffers,
+                       const float* latents /*[n,32]*/, const float* residual /*[n,3], nullable*/, int32_t mapping, void* stream);
+/* `reset_dual` under `_is_dual` (:167-180, 212-252, 424-431) for env_ids [n_ids] (device): whole pairs (2k, 2k+1), ascending - the
+ * reference splits the list by position, which is the env's parity only then; the caller sees to it.  A row is normalised with the
+ * statistics of its own side (env & 1), feature and root columns alike.  Every reset env walks `racket`'s arm chain.
+ * joint_pos_bind_rel [bind_rows,24,3]: `infer_with_fk` reads joint_pos_bind_rel[:batch] of a side's sub-list, so the pair at list
+ * positions 2i, 2i+1 reads row i, NOT the env's own row; bind_rows = 1 is one row for all, otherwise 2 bind_rows >= n_ids is required.
+ * Rows outside the list are not touched; ids outside 0 .. num_envs-1 are skipped.  Only avg and std of `weights` are read. */
+int v2p_mvae_dual_reset(const v2p_mvae_cfg* cfg /*[2]*/, int64_t num_envs, const v2p_mvae_weights* weights /*[2]*/, const v2p_mvae_buffers* buffers,
+                        const v2p_mvae_racket* racket, const int64_t* env_ids, int64_t n_ids, const float* init_feature /*[n_ids,288]*/,
+                        const float* root_xy /*[n_ids,2]*/, const float* joint_pos_bind_rel /*[bind_rows,24,3]*/, int64_t bind_rows, void* stream);
+
 /* ---- the imitation target from the motion generator's pose (vid2player/env/tasks/humanoid_smpl_im_mvae.py): what turns the root
  * position and the 24 local joint matrices that v2p_mvae_step writes into the packed target row [331] (layout of v2p_env_buffers.target)
  * that the low-level policy's humanoid tracks.  Stateless like v2p_mvae_step: every buffer is the caller's, no allocation, no host

@@ -141,6 +141,11 @@ class MvaeBuffers(C.Structure):
     _fields_ = [(k, vp) for k in MVAE_BUFFER_NAMES]
 
 
+class MvaeRacket(C.Structure):
+    """v2p_mvae_racket: the one racket object of a two-player batch (v2p_mvae_dual_reset)."""
+    _fields_ = [("righthand", C.c_int32), ("dir", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
 class MvaeTargetCfg(C.Structure):
     """v2p_mvae_target_cfg: settings of the imitation target from the motion generator's pose (v2p_mvae_target_step / _reset / _actions)."""
     _fields_ = [("dt", C.c_float), ("fix_head_orientation", C.c_int32), ("head_body", C.c_int32), ("smpl_head", C.c_int32), ("smpl_neck", C.c_int32),
@@ -231,6 +236,8 @@ def load():
         "v2p_tennis_dual_handover": [C.POINTER(TennisCfg), C.POINTER(TennisDualCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(TennisDualBuffers), vp],
         "v2p_mvae_step": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, vp, vp],
         "v2p_mvae_reset": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, C.c_int64, vp, vp, vp, vp],
+        "v2p_mvae_dual_step": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, vp, C.c_int32, vp],
+        "v2p_mvae_dual_reset": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), C.POINTER(MvaeRacket), vp, C.c_int64, vp, vp, vp, C.c_int64, vp],
         "v2p_mvae_target_step": [C.POINTER(MvaeTargetCfg), C.c_int64, C.POINTER(MvaeTargetBuffers), vp],
         "v2p_mvae_target_reset": [C.POINTER(MvaeTargetCfg), C.c_int64, C.POINTER(MvaeTargetBuffers), vp, C.c_int64, vp],
         "v2p_mvae_target_actions": [C.POINTER(MvaeTargetCfg), C.c_int64, vp, C.POINTER(MvaeTargetBuffers), vp, vp],
@@ -253,7 +260,7 @@ def load():
 EXPORTED_SYMBOLS = (
     "v2p_model_create", "v2p_model_destroy", "v2p_mlib_create", "v2p_mlib_destroy", "v2p_motion_state", "v2p_reward", "v2p_reset_flags",
     "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_obs_imitation_packed_w", "v2p_policy_head_w", "v2p_policy_head_record_w", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_set_context_transform", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
-    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_tennis_dual_step", "v2p_tennis_dual_handover", "v2p_mvae_step", "v2p_mvae_reset", "v2p_mvae_target_step", "v2p_mvae_target_reset", "v2p_mvae_target_actions", "v2p_last_error", "v2p_abi_version",
+    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_tennis_dual_step", "v2p_tennis_dual_handover", "v2p_mvae_step", "v2p_mvae_reset", "v2p_mvae_dual_step", "v2p_mvae_dual_reset", "v2p_mvae_target_step", "v2p_mvae_target_reset", "v2p_mvae_target_actions", "v2p_last_error", "v2p_abi_version",
 )
 
 

@@ -394,6 +394,55 @@ int v2p_mvae_reset(const v2p_mvae_cfg* c, int64_t num_envs, const v2p_mvae_weigh
     return launch_mvae_reset(*c, num_envs, *w, *b, env_ids, n_ids, init_feature, root_xy, joint_pos_bind_rel, (hipStream_t)stream);
 }
 
+// what both two-player entry points refuse: each side's own refusals, and sides that disagree on what the batch shares
+static int mvae_dual_check(const char* fn, const v2p_mvae_cfg* c, int64_t n, const v2p_mvae_weights* w, const v2p_mvae_buffers* b, bool step) {
+    if (!c || !w || !b) { set_error("%s: null cfg / weights / buffers", fn); return V2P_ERR_INVALID; }
+    for (int side = 0; side < 2; ++side) {
+        const int rc = mvae_check(fn, c + side, n, w + side, b, step);
+        if (rc != V2P_OK) return rc;
+    }
+    if (c[0].is_train != c[1].is_train || c[0].add_residual_dof != c[1].add_residual_dof) {
+        set_error("%s: the two sides disagree on is_train (%d, %d) or add_residual_dof (%d, %d)", fn, c[0].is_train, c[1].is_train, c[0].add_residual_dof, c[1].add_residual_dof);
+        return V2P_ERR_INVALID;
+    }
+    return V2P_OK;
+}
+
+int v2p_mvae_dual_step(const v2p_mvae_cfg* c, int64_t n, const v2p_mvae_weights* w, const v2p_mvae_buffers* b, const float* latents, const float* residual, int32_t mapping,
+                       void* stream) {
+    const int rc = mvae_dual_check("v2p_mvae_dual_step", c, n, w, b, true);
+    if (rc != V2P_OK) return rc;
+    if (n & 1) { set_error("v2p_mvae_dual_step: n %lld is odd (envs 2k and 2k+1 are a pair)", (long long)n); return V2P_ERR_INVALID; }
+    if (mapping != V2P_MVAE_DUAL_MAP_PARITY && mapping != V2P_MVAE_DUAL_MAP_HALVES) { set_error("v2p_mvae_dual_step: unknown mapping %d", mapping); return V2P_ERR_INVALID; }
+    if (n > 0 && !latents) { set_error("v2p_mvae_dual_step: null latents"); return V2P_ERR_INVALID; }
+    if (residual && !c[0].add_residual_dof) { set_error("v2p_mvae_dual_step: a residual without add_residual_dof"); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    const v2p_mvae_cfg (&c2)[2] = *reinterpret_cast<const v2p_mvae_cfg(*)[2]>(c);
+    const v2p_mvae_weights (&w2)[2] = *reinterpret_cast<const v2p_mvae_weights(*)[2]>(w);
+    return launch_mvae_dual_step(c2, n, w2, *b, latents, residual, mapping, (hipStream_t)stream);
+}
+
+int v2p_mvae_dual_reset(const v2p_mvae_cfg* c, int64_t num_envs, const v2p_mvae_weights* w, const v2p_mvae_buffers* b, const v2p_mvae_racket* racket, const int64_t* env_ids,
+                        int64_t n_ids, const float* init_feature, const float* root_xy, const float* joint_pos_bind_rel, int64_t bind_rows, void* stream) {
+    const int rc = mvae_dual_check("v2p_mvae_dual_reset", c, n_ids, w, b, false);
+    if (rc != V2P_OK) return rc;
+    if (!racket) { set_error("v2p_mvae_dual_reset: null racket"); return V2P_ERR_INVALID; }
+    if (num_envs < 0) { set_error("v2p_mvae_dual_reset: num_envs %lld < 0", (long long)num_envs); return V2P_ERR_INVALID; }
+    if (n_ids > 0 && (!env_ids || !init_feature || !root_xy || !joint_pos_bind_rel)) {
+        set_error("v2p_mvae_dual_reset: null env_ids / init_feature / root_xy / joint_pos_bind_rel");
+        return V2P_ERR_INVALID;
+    }
+    if (bind_rows < 1 || (bind_rows > 1 && 2 * bind_rows < n_ids)) {
+        set_error("v2p_mvae_dual_reset: joint_pos_bind_rel has %lld rows; the pair at list positions 2i, 2i+1 reads row i: 1 row or at least %lld", (long long)bind_rows,
+                  (long long)((n_ids + 1) / 2));
+        return V2P_ERR_INVALID;
+    }
+    if (n_ids == 0 || num_envs == 0) return V2P_OK;
+    const v2p_mvae_cfg (&c2)[2] = *reinterpret_cast<const v2p_mvae_cfg(*)[2]>(c);
+    const v2p_mvae_weights (&w2)[2] = *reinterpret_cast<const v2p_mvae_weights(*)[2]>(w);
+    return launch_mvae_dual_reset(c2, num_envs, w2, *b, *racket, env_ids, n_ids, init_feature, root_xy, joint_pos_bind_rel, bind_rows, (hipStream_t)stream);
+}
+
 // what the three imitation-target entry points refuse (cfg and buffers common to them); `fn` names the call
 static int mvae_target_check(const char* fn, const v2p_mvae_target_cfg* c, int64_t n, const v2p_mvae_target_buffers* b) {
     if (!c || !b) { set_error("%s: null cfg / buffers", fn); return V2P_ERR_INVALID; }

@@ -5,9 +5,12 @@ One control step - the gate, the three expert-blended layers and the player's st
 `v2p_mvae_step` (csrc/mvae_player.hip); `reset(env_ids)` is `v2p_mvae_reset`.  The decoder computes every expert and blends the results,
 out = sum_e c_e (x W_e + b_e), which is the function the reference computes by blending the weights per env; fp32 throughout (the
 reference runs the decoder under autocast on CUDA - a reduced-precision path is not built).  Only the shipped architecture
-is built: frame 288, latent 32, hidden 256, 6 experts, gate 64, one condition frame, one prediction, predicted phase; of dual mode, `True` (`reset_dual`) is, `different` is not.
+is built: frame 288, latent 32, hidden 256, 6 experts, gate 64, one condition frame, one prediction, predicted phase.  Both dual modes are
+built: `True` (one generator for both sides, `reset_dual`) and `different` (a weight set, statistics, hand and player rule per side: env 2k
+is side 0, env 2k+1 side 1; `v2p_mvae_dual_step` / `v2p_mvae_dual_reset`, csrc/mvae_player_dual.hip).
 
-`mvae_step_reference` / `mvae_reset_reference` are the numpy statement of the same two calls on arrays - the checker of the tests, as
+`mvae_step_reference` / `mvae_reset_reference` (and `mvae_dual_step_reference` / `mvae_dual_reset_reference`, which apply them row-wise
+by parity) are the numpy statement of the same calls on arrays - the checker of the tests, as
 `tennis_controller.task_step_reference` is for the task step; the product never calls them.  There is no CPU path: a CPU device or a
 missing library is a RuntimeError.
 """
@@ -27,6 +30,8 @@ PLAYERS = {"djokovic": 0, "federer": 1, "nadal": 2}
 LELBOW, RELBOW, LWRIST, RWRIST = 18, 19, 20, 21  # utils/pose.py
 RACKET_CHAIN = {True: (0, 3, 6, 9, 14, 17, 19, 21, 23), False: (0, 3, 6, 9, 13, 16, 18, 20, 22)}  # utils/racket.py:152-161
 RACKET_LENGTHS = (0.2, 0.15, 0.15)  # handle, shaft, head radius of the eastern tennis racket (utils/racket.py:10-19)
+RACKET_DIR = (-1.0, 0.0, 0.0)  # the canonical racket direction of both tennis grips
+RACKET_NORMALS = {"eastern": (0.0, 1.0, 0.0), "semi_western": (0.0, 1.0 / math.sqrt(2), 1.0 / math.sqrt(2))}  # utils/racket.py:10-32, before F.normalize
 STATE_NAMES = _lib.MVAE_BUFFER_NAMES
 WEIGHT_KEYS = ("w0", "b0", "w1", "b1", "w2", "b2", "gate_w0", "gate_b0", "gate_w1", "gate_b1", "gate_w2", "gate_b2")
 # the residual-DoF rule (mvae_player.py:306-408).  A row: (swing type, lo, hi, lo inclusive, {base angle: value}); envs of that swing
@@ -43,14 +48,34 @@ RESIDUAL_RULES = {
 }
 
 
-def player_settings(cfg, is_train):
+def player_settings(cfg, is_train, num_envs=None):
     """What both the kernel's v2p_mvae_cfg and the numpy statement are made from.  cfg: the reference's cfg_v2p keys `player`, `righthand`,
-    `add_residual_dof` (and, refused when they ask for what is not built: `dual_mode: different` - two weight sets per batch -,
-    `predict_phase`, the sizes of another option set).  `dual_mode: True` (one generator for both sides of every pair) is the single
-    player's generator with two sets of initial frames, `reset_dual`."""
+    `add_residual_dof` (and, refused when they ask for what is not built: `predict_phase`, the sizes of another option set).
+    `dual_mode: True` (one generator for both sides of every pair) is the single player's generator with two sets of initial frames,
+    `reset_dual`.  `dual_mode: 'different'` (mvae_player.py:23-57): `player`, `righthand` and `grip` are lists of two - side 0: envs 2k,
+    side 1: envs 2k+1 - and `serve_from` ('near', the default, or 'far') picks the side whose hand and grip the batch's ONE racket object
+    has; the result is dict(dual=True, sides=(settings of side 0, of side 1), racket=racket_settings(...), is_train, add_residual_dof)."""
     cfg = dict(cfg)
+    if cfg.get("dual_mode") == "different":
+        for k in ("player", "righthand") + (("grip",) if cfg.get("grip") is not None else ()):
+            if not isinstance(cfg.get(k), (list, tuple)):  # (one value for both sides: the reference would index into it)
+                raise NotImplementedError("MotionVAEPlayer: dual_mode 'different' takes cfg %s as a list of two (side 0, side 1); one value for both sides is not built; got %r" % (k, cfg.get(k)))
+            if len(cfg[k]) != 2:
+                raise ValueError("MotionVAEPlayer: dual_mode 'different' needs cfg %s as a list of two (side 0, side 1); got %r" % (k, cfg.get(k)))
+        if num_envs is not None and int(num_envs) % 2:
+            raise ValueError("MotionVAEPlayer: dual_mode 'different' needs an even num_envs (envs 2k and 2k+1 are a pair); got %d" % num_envs)
+        residual = cfg.get("add_residual_dof")
+        if isinstance(residual, (list, tuple)):
+            if len(residual) != 2 or residual[0] != residual[1]:
+                raise ValueError("MotionVAEPlayer: add_residual_dof must be common to both sides (one residual tensor serves the batch); got %r" % (residual,))
+            residual = residual[0]
+        one = {k: v for k, v in cfg.items() if k not in ("dual_mode", "grip", "serve_from")}
+        sides = tuple(player_settings(dict(one, player=cfg["player"][i], righthand=cfg["righthand"][i], add_residual_dof=residual), is_train) for i in (0, 1))
+        server = 0 if cfg.get("serve_from", "near") != "near" else 1  # (mvae_player.py:56)
+        grip = cfg["grip"][server] if cfg.get("grip") is not None else None
+        return dict(dual=True, sides=sides, racket=racket_settings(grip, sides[server]["righthand"]), is_train=bool(is_train), add_residual_dof=sides[0]["add_residual_dof"])
     if cfg.get("dual_mode") and cfg["dual_mode"] is not True:
-        raise NotImplementedError("MotionVAEPlayer: dual_mode is not built")
+        raise NotImplementedError("MotionVAEPlayer: dual_mode %r is not built (True or 'different')" % (cfg["dual_mode"],))
     if cfg.get("player") not in PLAYERS:
         raise ValueError("MotionVAEPlayer: cfg player %r is none of %s" % (cfg.get("player"), sorted(PLAYERS)))
     if cfg.get("add_residual_dof") not in (None, False, "euler"):
@@ -61,6 +86,19 @@ def player_settings(cfg, is_train):
         if cfg.get(k, v) != v:
             raise NotImplementedError("MotionVAEPlayer: only the shipped architecture is built (%s); got %s = %r" % (", ".join("%s %s" % kv for kv in sizes.items()), k, cfg[k]))
     return dict(player=cfg["player"], righthand=bool(cfg.get("righthand", True)), is_train=bool(is_train), add_residual_dof=bool(cfg.get("add_residual_dof")))
+
+
+def racket_settings(grip, righthand):
+    """`Racket('tennis', grip=grip, righthand=righthand)` (utils/racket.py:148-181) as what the reset reads: the arm of the FK chain and the
+    canonical direction and normal, normalised in float32 by the reference's own expression."""
+    if grip not in (None,) + tuple(RACKET_NORMALS):
+        raise ValueError("MotionVAEPlayer: grip %r is none of %s" % (grip, sorted(RACKET_NORMALS)))
+    unit = lambda v: tuple(float(x) for x in torch.nn.functional.normalize(torch.tensor(v, dtype=torch.float32), dim=0))
+    return dict(grip=grip or "eastern", righthand=bool(righthand), direction=unit(RACKET_DIR), normal=unit(RACKET_NORMALS[grip or "eastern"]))
+
+
+def racket_struct(r):
+    return _lib.MvaeRacket(righthand=int(r["righthand"]), dir=(C.c_float * 3)(*r["direction"]), normal=(C.c_float * 3)(*r["normal"]))
 
 
 def cfg_struct(st):
@@ -291,29 +329,35 @@ def mvae_step_reference(st, w, avg, std, s, latents, residual=None, dt=np.float3
     return {k: (v.astype(dt) if v.dtype.kind == "f" else v) for k, v in o.items()}
 
 
-def mvae_reset_reference(st, avg, std, s, env_ids, init_feature, root_xy, joint_pos_bind_rel, dt=np.float32, probes=None):
+def mvae_reset_reference(st, avg, std, s, env_ids, init_feature, root_xy, joint_pos_bind_rel, dt=np.float32, probes=None, racket=None):
     """`MVAEPlayer.reset(env_ids)` on arrays (mvae_player.py:160-165, 212-252, 424-431): returns the whole state after the reset, rows of
-    ids outside the batch untouched.  init_feature [len(env_ids), 288], root_xy [len(env_ids), 2] (the caller's draw)."""
+    ids outside the batch untouched.  init_feature [len(env_ids), 288], root_xy [len(env_ids), 2] (the caller's draw).
+    joint_pos_bind_rel [24,3], or [len(env_ids),24,3]: a row per id.  racket: racket_settings(...) of a player whose racket is not the
+    eastern one of st's hand (the two-player batch)."""
     avg, std = np.asarray(avg, dtype=dt).reshape(FRAME), np.asarray(std, dtype=dt).reshape(FRAME)
     o = {k: np.array(s[k]) for k in STATE_NAMES if s.get(k) is not None}
     n = len(o["root_pos"])
     o["conditions"] = o["conditions"].reshape(n, 1, FRAME)
     ids = np.asarray(env_ids, dtype=np.int64)
     keep = (ids >= 0) & (ids < n)
+    bind = np.asarray(joint_pos_bind_rel, dtype=dt).reshape(-1, NUM_JOINTS, 3)
+    bind = np.broadcast_to(bind, (len(ids), NUM_JOINTS, 3))[keep]
     ids, f, xy = ids[keep], np.asarray(init_feature, dtype=dt)[keep], np.asarray(root_xy, dtype=dt)[keep]
-    bind = np.asarray(joint_pos_bind_rel, dtype=dt).reshape(NUM_JOINTS, 3)
     root = np.concatenate([xy, f[:, 2:3]], 1)
     cond = (f - avg) / std
     cond[:, :3] = (root - avg[:3]) / std[:3]
     r6 = f[:, COL_ROT6D:].reshape(-1, NUM_JOINTS, 6)
     rotmat = rot6d_to_rotmat_reference(r6, dt, probes)
     # the racket: the chain of transforms Pelvis .. Wrist (utils/racket.py:235-269), the eastern vectors in the wrist's frame
-    chain = RACKET_CHAIN[st["righthand"]]
-    R, p = rotmat[:, chain[0]], np.broadcast_to(bind[chain[0]], (len(ids), 3)).astype(dt)
+    chain = RACKET_CHAIN[st["righthand"] if racket is None else racket["righthand"]]
+    R, p = rotmat[:, chain[0]], bind[:, chain[0]].astype(dt)
     for j in chain[1:8]:
-        p = (R * bind[j]).sum(-1) + p
+        p = (R * bind[:, j][:, None]).sum(-1) + p
         R = R @ rotmat[:, j]
-    direction, normal = -R[:, :, 0], R[:, :, 1]
+    if racket is None:
+        direction, normal = -R[:, :, 0], R[:, :, 1]
+    else:
+        direction, normal = ((R * np.asarray(racket[k], dtype=np.float32).astype(dt)).sum(-1) for k in ("direction", "normal"))
     pos = p + root
     for length in RACKET_LENGTHS:
         pos = pos + direction * dt(length)
@@ -323,6 +367,47 @@ def mvae_reset_reference(st, avg, std, s, env_ids, init_feature, root_xy, joint_
     if not st["is_train"]:
         o["joint_rot"][ids] = rotmat_to_angle_axis_reference(rotmat, dt, probes)
     return o
+
+
+def mvae_dual_step_reference(st, w, avg, std, s, latents, residual=None, dt=np.float32, probes=None):
+    """`MVAEPlayer.step` under `_is_dual` (mvae_player.py:191-199) on arrays: mvae_step_reference of side 0 on the even rows and of side 1
+    on the odd rows - st: player_settings(...) of `dual_mode: different`; w, avg, std: pairs - and then the reference's quirk: its non-init
+    branch writes the root-position columns of EVERY env's condition (:254-262) and side 1's call runs last, so those three columns are
+    normalised with side 1's avg and std in the even rows too.  probes: a pair of dicts, one per side."""
+    n = len(latents)
+    out = []
+    for i in (0, 1):
+        rows = {k: np.asarray(v)[i::2] for k, v in s.items() if v is not None}
+        out.append(mvae_step_reference(st["sides"][i], w[i], avg[i], std[i], rows, np.asarray(latents)[i::2], None if residual is None or not len(residual) else np.asarray(residual)[i::2],
+                                       dt, None if probes is None else probes[i]))
+    o = {}
+    for k in out[0]:
+        o[k] = np.empty((n,) + out[0][k].shape[1:], out[0][k].dtype)
+        o[k][0::2], o[k][1::2] = out[0][k], out[1][k]
+    a1, s1 = np.asarray(avg[1], dtype=dt).reshape(FRAME), np.asarray(std[1], dtype=dt).reshape(FRAME)
+    o["conditions"][0::2, 0, :3] = (o["root_pos"][0::2] - a1[:3]) / s1[:3]
+    return o
+
+
+def mvae_dual_reset_reference(st, avg, std, s, env_ids, init_feature, root_xy, joint_pos_bind_rel, dt=np.float32, probes=None):
+    """`reset_dual` under `_is_dual` (mvae_player.py:175-180) on arrays, for env_ids of whole pairs, ascending: mvae_reset_reference of each
+    side on its ids (a row is normalised with its own side's statistics; the init branch writes only those rows), both with the batch's one
+    racket.  joint_pos_bind_rel [24,3] or [rows,24,3]: `infer_with_fk` reads joint_pos_bind_rel[:batch] of a side's sub-list, so the pair at
+    list positions 2i, 2i+1 reads row i.  probes: a pair of dicts, one per side."""
+    ids = np.asarray(env_ids, dtype=np.int64).reshape(-1)
+    bind = np.asarray(joint_pos_bind_rel).reshape(-1, NUM_JOINTS, 3)
+    o = {k: (np.asarray(v, dtype=dt) if np.asarray(v).dtype.kind == "f" else v) for k, v in s.items() if v is not None}  # (a float64 evaluation is stored as such)
+    for i in (0, 1):
+        at = np.nonzero(ids % 2 == i)[0]
+        o = mvae_reset_reference(st["sides"][i], avg[i], std[i], o, ids[at], np.asarray(init_feature)[at], np.asarray(root_xy)[at], bind[at >> 1] if len(bind) > 1 else bind, dt,
+                                 None if probes is None else probes[i], racket=st["racket"])
+    return o
+
+
+def whole_pairs(ids):
+    """Is the ascending list `ids` made of whole pairs (2k, 2k+1)?"""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    return len(ids) % 2 == 0 and bool((ids[0::2] % 2 == 0).all()) and bool((ids[1::2] == ids[0::2] + 1).all())
 
 
 def dual_reset_rows(reset_reaction_env_ids, reset_recovery_env_ids):
@@ -336,12 +421,23 @@ def dual_reset_rows(reset_reaction_env_ids, reset_recovery_env_ids):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the player
+DUAL_MAP_PARITY, DUAL_MAP_HALVES = 0, 1  # V2P_MVAE_DUAL_MAP_*
+
+
 class MotionVAEPlayer:
     """`MVAEPlayer` on the device, single player.  Attribute names are the reference's.  cfg: `player`, `righthand`, `add_residual_dof`,
     `test_mode`; weights: weights_from_state_dict(...); avg, std [288]; init_data [M,1,288] or [M,288] (`vae_init_conditions`: fewer rows
     than envs repeat the first row, as the reference does); joint_pos_bind_rel [24,3] of the player's SMPL body.  With cfg `dual_mode: True`
     init_data_ready and init_data_serve (`vae_init_conditions_ready` / `_serve`, mvae_player.py:122-128: the first row of each, for every
-    env) are required, and `reset_dual` resets whole pairs from them."""
+    env) are required, and `reset_dual` resets whole pairs from them.
+
+    With cfg `dual_mode: 'different'` (`player`, `righthand`, `grip` lists of two, `serve_from`) the batch holds two players: weights, avg,
+    std, init_data_ready and init_data_serve are PAIRS (side 0: envs 2k, side 1: envs 2k+1); the two initial frames are the first row of
+    each side's file, interleaved by parity (`init_states`, mvae_player.py:113-121); init_data is not read (pass None).  `step` is
+    v2p_mvae_dual_step, `reset_dual` v2p_mvae_dual_reset; `reset(ids)` is refused, as the reference's would fail on its missing `_mvae`.
+    joint_pos_bind_rel may be [rows,24,3]: the reset of the pair at list positions 2i, 2i+1 reads row i (v2p_rollout.h)."""
+
+    dual_mapping = DUAL_MAP_HALVES  # (the faster of the two at 8192 envs; tools/mvae_dual_bench.py times both)
 
     def __init__(self, cfg, num_envs, weights, avg, std, init_data, joint_pos_bind_rel, is_train, device, init_data_ready=None, init_data_serve=None):
         dev = torch.device(device)
@@ -349,22 +445,38 @@ class MotionVAEPlayer:
             raise RuntimeError("MotionVAEPlayer: the motion generator is a HIP kernel - it must live on a GPU (no CPU fallback)")
         _lib.load()
         self.cfg, self.num_envs, self.device, self._is_train = dict(cfg), int(num_envs), dev, bool(is_train)
-        self.settings = player_settings(cfg, is_train)
+        self.settings = player_settings(cfg, is_train, num_envs)
+        self._is_dual = bool(self.settings.get("dual"))
         self._predict_phase = True
         n = self.num_envs
         f, i64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.long, device=dev)
-        self._weights = pack_weights(weights, avg, std, dev)
-        self._avg, self._std = self._weights["avg"], self._weights["std"]
-        init = torch.as_tensor(np.asarray(init_data, dtype=np.float32) if not torch.is_tensor(init_data) else init_data).to(**f)
-        init = init.reshape(len(init), -1, FRAME)[:, -1]
-        self._init_data = (init[:1].repeat(n, 1) if len(init) < n else init[:n]).contiguous()
-        self._init_data_ready = self._init_data_serve = None
-        if self.cfg.get("dual_mode"):
-            if init_data_ready is None or init_data_serve is None:
-                raise ValueError("MotionVAEPlayer: dual_mode needs init_data_ready and init_data_serve")
-            first = lambda d: torch.as_tensor(np.asarray(d, dtype=np.float32) if not torch.is_tensor(d) else d).to(**f).reshape(len(d), -1, FRAME)[:1, -1].repeat(n, 1).contiguous()
-            self._init_data_ready, self._init_data_serve = first(init_data_ready), first(init_data_serve)
-        self._joint_pos_bind_rel = torch.as_tensor(np.asarray(joint_pos_bind_rel, dtype=np.float32)).to(**f).reshape(NUM_JOINTS, 3).contiguous()
+        last = lambda d: torch.as_tensor(np.asarray(d, dtype=np.float32) if not torch.is_tensor(d) else d).to(**f).reshape(len(d), -1, FRAME)[:, -1]
+        self._init_data = self._init_data_ready = self._init_data_serve = None
+        if self._is_dual:
+            for name, v in (("weights", weights), ("avg", avg), ("std", std), ("init_data_ready", init_data_ready), ("init_data_serve", init_data_serve)):
+                if not isinstance(v, (list, tuple)) or len(v) != 2:
+                    raise ValueError("MotionVAEPlayer: dual_mode 'different' takes %s as a pair (side 0, side 1)" % name)
+            self._weights = tuple(pack_weights(weights[i], avg[i], std[i], dev) for i in (0, 1))
+            # (init_states :113-121: cat(first row of side 0's file, of side 1's).repeat(n / 2))
+            pairs = lambda d: torch.cat([last(d[0])[:1], last(d[1])[:1]], 0).repeat(n // 2, 1).contiguous()
+            self._init_data_ready, self._init_data_serve = pairs(init_data_ready), pairs(init_data_serve)
+            self._joint_pos_bind_rel = torch.as_tensor(np.asarray(joint_pos_bind_rel, dtype=np.float32)).to(**f).reshape(-1, NUM_JOINTS, 3).contiguous()
+            self._cfg_struct = (_lib.MvaeCfg * 2)(*(cfg_struct(st) for st in self.settings["sides"]))
+            self._weights_struct = (_lib.MvaeWeights * 2)(*(_lib.MvaeWeights(**{k: w[k].data_ptr() for k in _lib.MVAE_WEIGHT_NAMES}) for w in self._weights))
+            self._racket_struct = racket_struct(self.settings["racket"])
+        else:
+            self._weights = pack_weights(weights, avg, std, dev)
+            self._avg, self._std = self._weights["avg"], self._weights["std"]
+            init = last(init_data)
+            self._init_data = (init[:1].repeat(n, 1) if len(init) < n else init[:n]).contiguous()
+            if self.cfg.get("dual_mode"):
+                if init_data_ready is None or init_data_serve is None:
+                    raise ValueError("MotionVAEPlayer: dual_mode needs init_data_ready and init_data_serve")
+                first = lambda d: last(d)[:1].repeat(n, 1).contiguous()
+                self._init_data_ready, self._init_data_serve = first(init_data_ready), first(init_data_serve)
+            self._joint_pos_bind_rel = torch.as_tensor(np.asarray(joint_pos_bind_rel, dtype=np.float32)).to(**f).reshape(NUM_JOINTS, 3).contiguous()
+            self._cfg_struct = cfg_struct(self.settings)
+            self._weights_struct = _lib.MvaeWeights(**{k: self._weights[k].data_ptr() for k in _lib.MVAE_WEIGHT_NAMES})
         self._conditions = torch.zeros((n, 1, FRAME), **f)
         self._root_pos, self._root_vel = torch.zeros((n, 3), **f), torch.zeros((n, 3), **f)
         self._joint_rot6d, self._joint_rotmat = torch.zeros((n, NUM_JOINTS, 6), **f), torch.zeros((n, NUM_JOINTS, 3, 3), **f)
@@ -374,8 +486,6 @@ class MotionVAEPlayer:
         self._swing_type = torch.full((n,), -1, **i64)
         self._swing_type_cycle = self._swing_type.clone()
         self._latents = None
-        self._cfg_struct = cfg_struct(self.settings)
-        self._weights_struct = _lib.MvaeWeights(**{k: self._weights[k].data_ptr() for k in _lib.MVAE_WEIGHT_NAMES})
 
     def _buffers(self):
         # (built per call: `_swing_type_cycle` may have become another task's tensor, TennisControllerTask.attach_motion_generator)
@@ -396,19 +506,24 @@ class MotionVAEPlayer:
         return torch.tensor([0.0, -13.0], device=self.device).repeat(count, 1)
 
     def reset(self, env_ids, root_xy=None):
+        if self._is_dual:
+            raise RuntimeError("MotionVAEPlayer.reset: with dual_mode 'different' envs are reset in whole pairs by reset_dual (the reference's reset reads a `_mvae` it does not have)")
         ids = torch.as_tensor(env_ids, device=self.device, dtype=torch.long).contiguous()
         if ids.numel() == 0:
             return
         self._reset_rows(ids, self._init_data[ids.clamp(0, self.num_envs - 1)].contiguous(), root_xy)
 
     def reset_dual(self, reset_reaction_env_ids, reset_recovery_env_ids, root_xy=None):
-        """`reset_dual` (mvae_player.py:167-182) with `dual_mode: True`: the envs of both lists, in ascending order, start from the ready
+        """`reset_dual` (mvae_player.py:167-182) with `dual_mode: True` or 'different': the envs of both lists, in ascending order, start from the ready
         frame (reaction ids: the receivers) or the serve frame (recovery ids: the servers) through the launch of `reset`.  root_xy
         [len(both),2], in that ascending order, replaces the draw near the baseline's centre."""
         if self._init_data_ready is None:
-            raise RuntimeError("MotionVAEPlayer.reset_dual: the player was not made with cfg dual_mode: True")
+            raise RuntimeError("MotionVAEPlayer.reset_dual: the player was not made with cfg dual_mode: True or 'different'")
         as_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else x
         ids, from_ready = dual_reset_rows(as_np(reset_reaction_env_ids), as_np(reset_recovery_env_ids))
+        if self._is_dual and not whole_pairs(ids):
+            # (the reference splits the sorted list by position, `env_ids[::2]` / `[1::2]`: that is the env's side only for whole pairs)
+            raise ValueError("MotionVAEPlayer.reset_dual: with dual_mode 'different' the two lists together must be whole pairs (2k, 2k+1); got %s" % ids.tolist())
         if len(ids) == 0:
             return
         ids = torch.from_numpy(ids).to(self.device)
@@ -420,6 +535,15 @@ class MotionVAEPlayer:
         xy = self.draw_root_xy(ids.numel()) if root_xy is None else torch.as_tensor(root_xy, dtype=torch.float32, device=self.device)
         xy = xy.to(torch.float32).reshape(ids.numel(), 2).contiguous()
         b = self._buffers()
+        if self._is_dual:
+            bind = self._joint_pos_bind_rel
+            if len(bind) > 1 and 2 * len(bind) < ids.numel():
+                raise ValueError("MotionVAEPlayer.reset_dual: joint_pos_bind_rel has %d rows, %d pairs are reset" % (len(bind), ids.numel() // 2))
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().v2p_mvae_dual_reset(self._cfg_struct, self.num_envs, self._weights_struct, C.byref(b), C.byref(self._racket_struct), _lib.ptr(ids),
+                                                           int(ids.numel()), _lib.ptr(feature), _lib.ptr(xy), _lib.ptr(bind), len(bind), _lib.current_stream(self.device)),
+                           "v2p_mvae_dual_reset")
+            return
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().v2p_mvae_reset(C.byref(self._cfg_struct), self.num_envs, C.byref(self._weights_struct), C.byref(b), _lib.ptr(ids), int(ids.numel()),
                                                   _lib.ptr(feature), _lib.ptr(xy), _lib.ptr(self._joint_pos_bind_rel), _lib.current_stream(self.device)), "v2p_mvae_reset")
@@ -437,6 +561,11 @@ class MotionVAEPlayer:
                 raise RuntimeError("MotionVAEPlayer.step: residual must be [%d, 3]" % self.num_envs)
             r = residual.to(device=self.device, dtype=torch.float32).contiguous()
         b = self._buffers()
+        if self._is_dual:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().v2p_mvae_dual_step(self._cfg_struct, self.num_envs, self._weights_struct, C.byref(b), _lib.ptr(z), _lib.ptr(r), self.dual_mapping,
+                                                          _lib.current_stream(self.device)), "v2p_mvae_dual_step")
+            return
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().v2p_mvae_step(C.byref(self._cfg_struct), self.num_envs, C.byref(self._weights_struct), C.byref(b), _lib.ptr(z), _lib.ptr(r),
                                                  _lib.current_stream(self.device)), "v2p_mvae_step")

@@ -13,7 +13,9 @@ the controller owns nor mask its actions.
 the same calls on arrays - the checker of the tests, as `mvae.mvae_step_reference` is for the generator; the product never calls them.
 There is no CPU path: a CPU device or a missing library is a RuntimeError.
 
-Not built: `dual_mode`, `obs_type: joint_pos`, `optimize_two_hand_backhand`, `update_mvae_from_sim`; `pd_action_scale` / `pd_action_offset`
+A two-player task (`dual_mode: different`, env i is player i % 2) takes joint_pos_bind [2,24,3] - the task's `_env_shape_ids` are the
+parities - and `smpl_beta` as a list of two; `pd_action_scale` / `pd_action_offset` stay one [69] pair for the batch, as in the reference.
+Not built: per-clip body shapes x two players (refused by the task), `obs_type: joint_pos`, `optimize_two_hand_backhand`, `update_mvae_from_sim`; `pd_action_scale` / `pd_action_offset`
 are the caller's arrays (the reference derives them from the actors' DoF limits, humanoid_smpl.py:368-410).
 """
 import ctypes as C
@@ -48,12 +50,16 @@ def tree_from_model(body_names, parents):
     return smpl_parents, smpl_of_body
 
 
-def target_settings(cfg_v2p, cfg_env, control_dt, body_names, parents, key_body_ids):
+def target_settings(cfg_v2p, cfg_env, control_dt, body_names, parents, key_body_ids, two_player=False):
     """What both the kernel's v2p_mvae_target_cfg and the numpy statement are made from.  cfg_v2p: the reference's `fix_head_orientation`,
-    `add_residual_root`, `residual_root_scale` (and `dual_mode`, refused); cfg_env: `pd_target_base`, `no_scale_action` (and `obs_type`)."""
+    `add_residual_root`, `residual_root_scale` (and `dual_mode`: 'different' goes with a two-player task, two_player, and is refused
+    without one); cfg_env: `pd_target_base`, `no_scale_action` (and `obs_type`)."""
     v2p, env = dict(cfg_v2p or {}), dict(cfg_env or {})
-    if v2p.get("dual_mode") and v2p["dual_mode"] is not True:  # (`True`: both sides of a pair share one tree and one body - the single target)
-        raise NotImplementedError("ImitationTarget: dual_mode is not built")
+    # (`True`: both sides of a pair share one tree and one body - the single target; 'different': the kernels take a shape per env)
+    if v2p.get("dual_mode") and v2p["dual_mode"] is not True and not (v2p["dual_mode"] == "different" and two_player):
+        raise NotImplementedError("ImitationTarget: dual_mode %r is not built over a single-player task ('different' takes a two-player one)" % (v2p["dual_mode"],))
+    if two_player and v2p.get("dual_mode") != "different":
+        raise ValueError("ImitationTarget: a two-player task goes with cfg v2p.dual_mode 'different', got %r" % (v2p.get("dual_mode"),))
     if env.get("obs_type", "joint_pos_and_angle") != "joint_pos_and_angle":
         raise NotImplementedError("ImitationTarget: obs_type %r is not built (only joint_pos_and_angle)" % (env.get("obs_type"),))
     base = env.get("pd_target_base", "target_pos")
@@ -365,15 +371,17 @@ class ImitationTarget:
     """The target half of `HumanoidSMPLIMMVAE` on the device, around a racket + ball task and the motion generator of its batch.
     task: a `HumanoidSMPLIMRacketBall`; player: its `MotionVAEPlayer`; joint_pos_bind [S,24,3] (or [24,3]): rest joints of the SMPL
     bodies (`self._smpl.joint_pos_bind`, one row per body shape; the task's `_env_shape_ids` pick an env's row); cfg: {"v2p": ..., "env": ...}
-    with the keys of `target_settings`, and optionally env `pd_action_scale` / `pd_action_offset` [69], v2p `smpl_beta` [10]."""
+    with the keys of `target_settings`, and optionally env `pd_action_scale` / `pd_action_offset` [69], v2p `smpl_beta` [10].  Over a
+    two-player task (`racket_players`): a player with `dual_mode: 'different'`, joint_pos_bind [2,24,3] (side 0, side 1), `smpl_beta` [2,10]."""
 
     def __init__(self, task, player, joint_pos_bind, cfg):
         v2p, env = dict(cfg.get("v2p") or {}), dict(cfg.get("env") or {})
         dev = torch.device(task.device)
         if dev.type != "cuda":
             raise RuntimeError("ImitationTarget: the target is written by a HIP kernel - the task must live on a GPU (no CPU fallback)")
-        if getattr(task, "racket_players", None) is not None:
-            raise NotImplementedError("ImitationTarget: dual_mode is not built")
+        two_player = getattr(task, "racket_players", None) is not None
+        if two_player != bool(getattr(player, "_is_dual", False)):
+            raise ValueError("ImitationTarget: a two-player task takes a motion generator with dual_mode 'different', a single-player task one without")
         if not hasattr(task, "_ball_root_states"):
             raise TypeError("ImitationTarget wraps a HumanoidSMPLIMRacketBall")
         if abs(float(task.pd_tar_lim) - math.pi / 2) > 1e-6:
@@ -382,7 +390,7 @@ class ImitationTarget:
             raise ValueError("ImitationTarget: the player has %d envs on %s, the task %d on %s" % (player.num_envs, player.device, task.num_envs, dev))
         _lib.load()
         self.task, self.player, self.device, self.num_envs = task, player, dev, task.num_envs
-        self.settings = target_settings(v2p, env, task.dt, task.body_names, task.body_model.parents, task._key_body_ids.tolist())
+        self.settings = target_settings(v2p, env, task.dt, task.body_names, task.body_model.parents, task._key_body_ids.tolist(), two_player)
         f = dict(dtype=torch.float32, device=dev)
         bind = torch.as_tensor(np.asarray(joint_pos_bind, dtype=np.float32)).to(**f).reshape(-1, NUM_JOINTS, 3).contiguous()
         shape_ids = getattr(task, "_env_shape_ids", None)
@@ -399,7 +407,12 @@ class ImitationTarget:
         # `_reset_ref_motion_bodies` (:257-264): gender male, then the player's betas
         self._reset_ref_motion_bodies = torch.zeros((self.num_envs, 11), **f)
         self._reset_ref_motion_bodies[:, 0] = 1
-        if v2p.get("smpl_beta") is not None:
+        if v2p.get("smpl_beta") is not None and two_player:  # (:260-262: the betas of side 0 and of side 1)
+            betas = torch.as_tensor(np.asarray(v2p["smpl_beta"], dtype=np.float32), **f)
+            if betas.shape != (2, 10):
+                raise ValueError("ImitationTarget: with a two-player task cfg v2p.smpl_beta is a list of two [10], got shape %s" % (tuple(betas.shape),))
+            self._reset_ref_motion_bodies[0::2, 1:11], self._reset_ref_motion_bodies[1::2, 1:11] = betas[0], betas[1]
+        elif v2p.get("smpl_beta") is not None:
             self._reset_ref_motion_bodies[:, 1:11] = torch.as_tensor(np.asarray(v2p["smpl_beta"], dtype=np.float32).reshape(10), **f)
         self.obs_buf = torch.zeros((self.num_envs, NUM_OBS_IM), **f)
         self._pd_actions = torch.zeros((self.num_envs, _lib.NUM_ACTIONS), **f)

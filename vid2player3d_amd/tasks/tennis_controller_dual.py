@@ -12,8 +12,8 @@ reference has two `.nonzero()`, `terminate.sum() > 0`, `index.cpu()` and a gathe
 `dual_step_reference` and `handover_reference` are the numpy statements of the two launches - the checkers of the tests; the product
 never calls them.  `DualTennisControllerTask` is the reference-shaped object.  Training-mode semantics: the extra
 `_update_state_from_sim()` "for vis" when not training (humanoid_smpl_im_mvae_dual.py:46-48) is not built.  Not built either: resetting
-finished pairs by mask without a host list (`reset(ids)` takes ids), `dual_mode: different` on the motion generator and the imitation
-target (two weight sets and two trees per batch) - a two-player batch runs with the caller's phase_pred / swing_type.
+finished pairs by mask without a host list (`reset(ids)` takes ids).  Under `dual_mode: different` the attached motion generator is the
+two-player one (a weight set per side, `v2p_mvae_dual_step` / `_reset`) and the imitation target takes a body shape per side.
 """
 import ctypes as C
 import math
@@ -275,6 +275,13 @@ class DualTennisControllerTask(tc.TennisControllerTask):
             return
         raise ValueError("DualTennisControllerTask: cfg v2p.dual_mode True goes with a single-player racket + ball task, 'different' with a "
                          "two-player one; got dual_mode %r over %s" % (mode, "a two-player task" if players is not None else "a single-player task"))
+
+    def attach_motion_generator(self, player):
+        """As `TennisControllerTask.attach_motion_generator`; the player's mode is the task's: one generator for both sides under
+        `dual_mode: True`, a weight set per side under 'different'."""
+        if bool(getattr(player, "_is_dual", False)) != (self.cfg_v2p.get("dual_mode") == "different"):
+            raise ValueError("attach_motion_generator: cfg v2p.dual_mode %r and the player's (%r) disagree" % (self.cfg_v2p.get("dual_mode"), player.cfg.get("dual_mode")))
+        super().attach_motion_generator(player)
 
     def _grip(self, v2p):
         """The grip of the base settings: the even side's (cfg v2p.grip is a list of two names under `dual_mode: different`, one name
