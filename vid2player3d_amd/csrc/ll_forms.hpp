@@ -74,6 +74,14 @@ struct LlForms {
     // alone stays inside it) - cause not found, docs/NOTES.md B, 2026-10-20, the arithmetic of the level loops
     static constexpr bool P2SHIFT = !(TGS && BALL);
 
+    // CGEN_EARLY (with the visit table): contact generation - the cull, the scan rounds, the records, the touched masks, the depth of each
+    // env's deepest stop, sweep_on - runs right behind the kinematics, where the pose is still in registers, instead of between the root
+    // solve and the Lambda recursion.  It reads only the pose and constants, so its results are the same bits; what goes is what its
+    // earlier place cost: the root's Lambda parked in LDS around it (21 writes, 21 reads), the placeholder fill of the other lanes' Lambda
+    // (21 moves) and the re-read of the pose (7 reads).  The joint-limit kernels activate their rows with v*, which exists only after pass
+    // 3: they, and with them the TGS and ball kernels, keep the earlier order (docs/NOTES.md B, 2026-10-20, contact generation first).
+    static constexpr bool CGEN_EARLY = VTAB;
+
     // DIAGX: the split of the sweep's remainder (counters CLOSE_MOVE .. SWEEP_SETUP: closing move, closing pass, head and tail of a visit,
     // set-up) is timed in the default build's diagnostic kernel only: in the register build's it costs 12 B of scratch per lane
     static constexpr bool DIAGX = REGS ? false : DIAG;
