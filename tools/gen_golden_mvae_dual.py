@@ -132,7 +132,7 @@ def check_margins(p32, p64, what):
     stored angle-axis is continuous across the pick, and no integer hangs on it."""
     tie = serve_wrist_tie()
     for i in (0, 1):
-        a, b = dict(p32[i]), dict(p64[i])
+        a, b = G1.with_diagonal(p32[i]), G1.with_diagonal(p64[i])
         if "diagonal" in a:
             x, y = (np.concatenate([np.ravel(u) for u in d["diagonal"]]) for d in (a, b))
             assert x.shape == y.shape, "%s side %d: a trace changes sign between float32 and float64" % (what, i)

@@ -131,8 +131,17 @@ def near(values, thresholds):
     return np.min(np.abs(v[:, None] - np.asarray(thresholds, dtype=np.float64)[None]), axis=1) if v.size else np.zeros(0)
 
 
+def with_diagonal(p):
+    """the probes with `diagonal`: the three differences of the diagonal where they can decide, that is where the trace is not positive"""
+    if "trace" not in p or "diagonal" in p:
+        return p
+    pick = [np.concatenate([d[t <= 0] for d in ds]) for t, *ds in zip(p["trace"], p["diag01"], p["diag02"], p["diag12"])]
+    return dict(p, diagonal=pick)
+
+
 def check_margins(p32, p64, what):
     """every float that picks a branch stays MARGIN x its scatter (float32 against float64 evaluation of the same statement) away"""
+    p32, p64 = with_diagonal(p32), with_diagonal(p64)
     for name, thresholds in (("phase", THRESHOLDS), ("atan2", (0.0,)), ("wrist_x", (0.0,)), ("rot6d_norm", (1e-8,)), ("trace", (0.0,)), ("diagonal", (0.0,)), ("quat_w", (0.0,)), ("sin2", (0.0,)), ("theta2", (1e-6,))):
         if name not in p32:
             continue

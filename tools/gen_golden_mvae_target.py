@@ -10,12 +10,12 @@ tests/golden/mvae_target.npz.
 
 Poses are constructed: a moderate base pose per env with small per-step increments; upright roots near the 120 degree base rotation
 (trace ~ 0 of the quaternion function); three envs carry a joint turned by ~165 degrees about x, y, z (the other three branches on local
-matrices, `cos_theta < 0`); env 0 does not move between steps 2 and 3 (the masked branch of `quat_to_angle_axis`); the ball is placed
+matrices, `quat_w < 0`); env 0 does not move between steps 2 and 3 (the masked branch of `quat_to_angle_axis`); the ball is placed
 left and right of the gaze, across both +-pi wraps, and into each of the two miss conditions.  The generator asserts that each occurs.
 
 Scatter.  The same run in float64 gives `scatter/<kind>/<name>` = max |float32 - float64| per quantity: `step` (one teacher-forced step
 from the recorded float32 state), `free` (the free-running sequence), `reset`, `actions`.  Margin.  Every float that picks a branch -
-the trace and the diagonal comparisons, `cos_theta`, the 1e-5 mask, the +-pi wraps, the two miss tests; from the numpy statement in
+the trace and the diagonal comparisons, `quat_w`, the 1e-5 mask, the +-pi wraps, the two miss tests; from the numpy statement in
 float32 and float64 - stays MARGIN x its own scatter from the threshold; a pose that violates it is re-drawn alone (a small offset of its own on every joint,
 a new place of the ball), the count of re-drawn poses is printed, more than 5 % of the poses fail.  (The static env has no margin at the mask and needs none: its difference quaternion is the identity up to rounding, on
 either side of the mask the velocity is 2 |xyz| / dt ~ 1e-5, far inside every allowance.)  Only arrays are stored.  Run where the
@@ -216,7 +216,18 @@ def flat(p, n):
     return out
 
 
-THRESHOLDS = {"trace": (0.0,), "diagonal": (0.0,), "cos_theta": (0.0,), "sin_theta": (1e-5,), "angle_diff": (-math.pi, math.pi), "miss_y": (0.0,), "miss_x": (0.0,)}
+THRESHOLDS = {"trace": (0.0,), "diagonal": (0.0,), "quat_w": (0.0,), "sin_theta": (1e-5,), "angle_diff": (-math.pi, math.pi), "miss_y": (0.0,), "miss_x": (0.0,)}
+
+
+def with_diagonal(p):
+    """the probes with `diagonal`: per call the three differences of the diagonal, each where its comparison decides (both of branch 1
+    unless the other already fails, the third only where branch 1 is not taken), inf elsewhere"""
+    out = {k: with_diagonal(v) if isinstance(v, dict) else v for k, v in p.items()}
+    if "trace" in p:
+        out["diagonal"] = []
+        for t, d01, d02, d12, br in zip(p["trace"], p["diag01"], p["diag02"], p["diag12"], p["branch"]):
+            out["diagonal"] += [np.where((t <= 0) & (d02 > 0), d01, np.inf), np.where((t <= 0) & (d01 > 0), d02, np.inf), np.where((t <= 0) & (br != 1), d12, np.inf)]
+    return out
 
 
 def chunks(p, n):
@@ -234,7 +245,7 @@ def chunks(p, n):
 def violators(p32, p64, n, steps):
     """[n, steps]: the (env, step) pairs with a branch-picking float within MARGIN x its own scatter of the threshold.  The probes of a
     run of `steps` steps come in step order, the same number of pieces per step."""
-    a, b = chunks(p32, n), chunks(p64, n)
+    a, b = chunks(with_diagonal(p32), n), chunks(with_diagonal(p64), n)
     bad = np.zeros((n, steps), bool)
     for k in a:
         name = k.split("/")[-1]
@@ -386,7 +397,7 @@ def run_variant(v, model, out, scat, counts):
     for name, br in (("local", br_local), ("global", br_global)):
         assert set(br.tolist()) == {0, 1, 2, 3}, "variant %s: %s matrices take only the branches %s of rotation_matrix_to_quaternion" % (v, name, sorted(set(br.tolist())))
     fl = flat(p32, N)
-    assert (fl["local/cos_theta"] < 0).any(), "no cos_theta < 0"
+    assert (fl["local/quat_w"] < 0).any(), "no quaternion with w < 0"
     root_trace = fl["global/trace"].reshape(N, -1, 24)[:, :, 0]
     facing = [e for e in range(N) if e not in GAZE]  # (the two envs of the wraps are turned away from the net to put their gaze next to +-pi)
     assert np.abs(root_trace[facing]).max() < 0.6 and (root_trace > 0).any() and (root_trace < 0).any(), "the roots' traces do not straddle 0"

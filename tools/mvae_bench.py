@@ -44,8 +44,8 @@ def safe_div(num, den, eps=1e-6):
     return num / den
 
 
-def rotmat_to_angle_axis(m, eps=1e-6):
-    """konia_transform.rotation_matrix_to_angle_axis, op by op"""
+def rotmat_to_quat(m, eps=1e-6):
+    """konia_transform.rotation_matrix_to_quaternion, op by op (w, x, y, z)"""
     m00, m01, m02, m10, m11, m12, m20, m21, m22 = [m[..., i, j] for i in range(3) for j in range(3)]
     trace = m00 + m11 + m22
     sq = torch.sqrt((trace + 1.0).clamp_min(eps)) * 2.0
@@ -58,13 +58,22 @@ def rotmat_to_angle_axis(m, eps=1e-6):
     c3 = torch.stack((safe_div(m10 - m01, sq), safe_div(m02 + m20, sq), safe_div(m12 + m21, sq), 0.25 * sq), dim=-1)
     w2 = torch.where((m11 > m22).unsqueeze(-1), c2, c3)
     w1 = torch.where(((m00 > m11) & (m00 > m22)).unsqueeze(-1), c1, w2)
-    q = torch.where((trace > 0.0).unsqueeze(-1), c0, w1)
+    return torch.where((trace > 0.0).unsqueeze(-1), c0, w1)
+
+
+def quat_to_angle_axis_konia(q, eps=1e-6):
+    """konia_transform.quaternion_to_angle_axis of (w, x, y, z), op by op"""
     cos, q1, q2, q3 = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
     s2 = q1 * q1 + q2 * q2 + q3 * q3
     s = torch.sqrt(s2.clamp_min(eps))
     two_theta = 2.0 * torch.where(cos < 0.0, torch.atan2(-s, -cos), torch.atan2(s, cos))
     k = torch.where(s2 > 0.0, safe_div(two_theta, s), 2.0 * torch.ones_like(s))
     return torch.stack((q1 * k, q2 * k, q3 * k), dim=-1)
+
+
+def rotmat_to_angle_axis(m):
+    """konia_transform.rotation_matrix_to_angle_axis"""
+    return quat_to_angle_axis_konia(rotmat_to_quat(m))
 
 
 def angle_axis_to_rotmat(aa, eps=1e-6):

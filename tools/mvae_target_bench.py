@@ -29,39 +29,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-from mvae_bench import DEV, angle_axis_to_rotmat, make_pair, safe_div, timed  # noqa: E402
+from mvae_bench import DEV, angle_axis_to_rotmat, make_pair, quat_to_angle_axis_konia, rotmat_to_quat, timed  # noqa: E402
 
 from vid2player3d_amd import mvae_target as mt  # noqa: E402
 
 HBM_TB_S = 6.29                     # float4 copy measured on this part
 READ_BYTES = 4 * (3 + 216 + 3 + 3 + 3 + 72 + 3 + 96)  # root, matrices, residual, ball, simulated root, bind row, previous root and rb_rot
 WRITE_BYTES = 4 * (331 + 18) + 20   # the row, Head and Neck, the three held clocks
-
-
-def rotmat_to_quat(m, eps=1e-6):
-    """konia_transform.rotation_matrix_to_quaternion, op by op (w, x, y, z)"""
-    m00, m01, m02, m10, m11, m12, m20, m21, m22 = [m[..., i, j] for i in range(3) for j in range(3)]
-    trace = m00 + m11 + m22
-    sq = torch.sqrt((trace + 1.0).clamp_min(eps)) * 2.0
-    c0 = torch.stack((0.25 * sq, safe_div(m21 - m12, sq), safe_div(m02 - m20, sq), safe_div(m10 - m01, sq)), dim=-1)
-    sq = torch.sqrt((1.0 + m00 - m11 - m22).clamp_min(eps)) * 2.0
-    c1 = torch.stack((safe_div(m21 - m12, sq), 0.25 * sq, safe_div(m01 + m10, sq), safe_div(m02 + m20, sq)), dim=-1)
-    sq = torch.sqrt((1.0 + m11 - m00 - m22).clamp_min(eps)) * 2.0
-    c2 = torch.stack((safe_div(m02 - m20, sq), safe_div(m01 + m10, sq), 0.25 * sq, safe_div(m12 + m21, sq)), dim=-1)
-    sq = torch.sqrt((1.0 + m22 - m00 - m11).clamp_min(eps)) * 2.0
-    c3 = torch.stack((safe_div(m10 - m01, sq), safe_div(m02 + m20, sq), safe_div(m12 + m21, sq), 0.25 * sq), dim=-1)
-    w2 = torch.where((m11 > m22).unsqueeze(-1), c2, c3)
-    w1 = torch.where(((m00 > m11) & (m00 > m22)).unsqueeze(-1), c1, w2)
-    return torch.where((trace > 0.0).unsqueeze(-1), c0, w1)
-
-
-def quat_to_angle_axis_konia(q, eps=1e-6):
-    cos, q1, q2, q3 = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
-    s2 = q1 * q1 + q2 * q2 + q3 * q3
-    s = torch.sqrt(s2.clamp_min(eps))
-    two_theta = 2.0 * torch.where(cos < 0.0, torch.atan2(-s, -cos), torch.atan2(s, cos))
-    k = torch.where(s2 > 0.0, safe_div(two_theta, s), 2.0 * torch.ones_like(s))
-    return torch.stack((q1 * k, q2 * k, q3 * k), dim=-1)
 
 
 def quat_to_rotmat(q):

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libv2p_rollout.so")
 SOURCES = ["capi.hip", "device_owner.hip", "model_compile.hip", "env.hip", "motion_state.hip", "task_ops.hip", "shape_compile.hip", "motion_build.hip", "physics.hip", "physics_ll.hip", "physics_ll_host.hip", "ball_rollout.hip", "tennis_task.hip", "mvae_player.hip", "mvae_player_dual.hip", "mvae_target.hip"]
-HEADERS = ["v2p_internal.hpp", "ll_schedule.hpp", "ll_forms.hpp", "ll_contact_setup.inc", "v2p_dev.hpp", "v2p_math.inc", "phys_math.hpp", "phys_common.hpp", "motion_sample.inc", "hull_gjk.hpp", "post_ops.inc", "strict_ops.inc", "tennis_task.hpp", "tennis_row.inc", "mvae_player.hpp", "mvae_player_dev.hpp", "mvae_rows.inc", "mvae_target.hpp", os.path.join("..", "..", "include", "v2p_rollout.h")]
+HEADERS = ["v2p_internal.hpp", "ll_schedule.hpp", "ll_forms.hpp", "ll_contact_setup.inc", "v2p_dev.hpp", "v2p_math.inc", "phys_math.hpp", "phys_common.hpp", "motion_sample.inc", "hull_gjk.hpp", "post_ops.inc", "strict_ops.inc", "tennis_task.hpp", "tennis_row.inc", "mvae_player.hpp", "mvae_player_dev.hpp", "mvae_rows.inc", "mvae_target.hpp", "ref_rotations.hpp", os.path.join("..", "..", "include", "v2p_rollout.h")]
 ARCH = "gfx950"
 
 

@@ -4,6 +4,7 @@
 // (7346 against 7309 instructions, the same text), and that kernel must stay the machine code it was (tools/kernel_identity.py).
 #pragma once
 #include "mvae_player.hpp"
+#include "ref_rotations.hpp"
 
 namespace v2p {
 
@@ -74,8 +75,7 @@ struct MvArgs {
 };
 
 // ---------------------------------------------------------------------------------------------------------------- rotations
-// x.clamp_min(lo) as torch evaluates it: a NaN stays a NaN
-__device__ inline float mv_clamp_min(float x, float lo) { return x < lo ? lo : x; }
+// (clamp_min, safe_zero_division, quaternion -> angle-axis, angle-axis -> matrix: ref_rotations.hpp)
 __device__ inline float mv_norm3(float x, float y, float z) { return sqrtf(x * x + y * y + z * z); }
 
 // rot6d_to_rotmat (utils/torch_transform.py:221-235) with its two eps = 1e-8 fallbacks; m row-major, columns b1 b2 b3
@@ -83,11 +83,11 @@ __device__ inline void mv_rot6d_to_rotmat(const float* r, float* m) {
     float ax = r[0], ay = r[1], az = r[2];
     const float cx = r[3], cy = r[4], cz = r[5];
     if (mv_norm3(ax, ay, az) < 1e-8f) { ax = 1.f; ay = 0.f; az = 0.f; }
-    const float n1 = mv_clamp_min(mv_norm3(ax, ay, az), 1e-9f);
+    const float n1 = ref_clamp_min(mv_norm3(ax, ay, az), 1e-9f);
     const float b1x = ax / n1, b1y = ay / n1, b1z = az / n1;
     const float d = b1x * cx + b1y * cy + b1z * cz;
     const float ux = cx - d * b1x, uy = cy - d * b1y, uz = cz - d * b1z;
-    const float n2 = mv_clamp_min(mv_norm3(ux, uy, uz), 1e-9f);
+    const float n2 = ref_clamp_min(mv_norm3(ux, uy, uz), 1e-9f);
     float b2x = ux / n2, b2y = uy / n2, b2z = uz / n2;
     if (mv_norm3(b2x, b2y, b2z) < 1e-8f) { b2x = 0.f; b2y = 1.f; b2z = 0.f; }
     m[0] = b1x; m[3] = b1y; m[6] = b1z;
@@ -97,58 +97,27 @@ __device__ inline void mv_rot6d_to_rotmat(const float* r, float* m) {
     m[8] = b1x * b2y - b1y * b2x;
 }
 
-// safe_zero_division (utils/konia_transform.py:336-344)
-__device__ inline float mv_szd(float num, float den) {
-    if (fabsf(den) < 1e-6f) den += 1e-6f;
-    return num / den;
-}
-// torch_safe_atan2 (:41-49)
-__device__ inline float mv_safe_atan2(float y, float x) {
-    if (fabsf(y) < 1e-6f && fabsf(x) < 1e-6f) y += 1e-6f;
-    return atan2f(y, x);
-}
-
-// rotation_matrix_to_angle_axis (:631-655) = rotation_matrix_to_quaternion (:347-438, wxyz) then quaternion_to_angle_axis (:557-628)
+// rotation_matrix_to_angle_axis (utils/konia_transform.py:631-655) with the table of rotation_matrix_to_quaternion (:347-438, wxyz) in
+// locals: the second statement of that table, kept because ref_rotations.hpp's form moves these kernels (see there)
 __device__ inline void mv_rotmat_to_angle_axis(const float* m, float* aa) {
     const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
     const float trace = m00 + m11 + m22;
     float qw, qx, qy, qz;
     if (trace > 0.f) {
-        const float sq = sqrtf(mv_clamp_min(trace + 1.f, 1e-6f)) * 2.f;
-        qw = 0.25f * sq; qx = mv_szd(m21 - m12, sq); qy = mv_szd(m02 - m20, sq); qz = mv_szd(m10 - m01, sq);
+        const float sq = sqrtf(ref_clamp_min(trace + 1.f, 1e-6f)) * 2.f;
+        qw = 0.25f * sq; qx = ref_szd(m21 - m12, sq); qy = ref_szd(m02 - m20, sq); qz = ref_szd(m10 - m01, sq);
     } else if (m00 > m11 && m00 > m22) {
-        const float sq = sqrtf(mv_clamp_min(1.f + m00 - m11 - m22, 1e-6f)) * 2.f;
-        qw = mv_szd(m21 - m12, sq); qx = 0.25f * sq; qy = mv_szd(m01 + m10, sq); qz = mv_szd(m02 + m20, sq);
+        const float sq = sqrtf(ref_clamp_min(1.f + m00 - m11 - m22, 1e-6f)) * 2.f;
+        qw = ref_szd(m21 - m12, sq); qx = 0.25f * sq; qy = ref_szd(m01 + m10, sq); qz = ref_szd(m02 + m20, sq);
     } else if (m11 > m22) {
-        const float sq = sqrtf(mv_clamp_min(1.f + m11 - m00 - m22, 1e-6f)) * 2.f;
-        qw = mv_szd(m02 - m20, sq); qx = mv_szd(m01 + m10, sq); qy = 0.25f * sq; qz = mv_szd(m12 + m21, sq);
+        const float sq = sqrtf(ref_clamp_min(1.f + m11 - m00 - m22, 1e-6f)) * 2.f;
+        qw = ref_szd(m02 - m20, sq); qx = ref_szd(m01 + m10, sq); qy = 0.25f * sq; qz = ref_szd(m12 + m21, sq);
     } else {
-        const float sq = sqrtf(mv_clamp_min(1.f + m22 - m00 - m11, 1e-6f)) * 2.f;
-        qw = mv_szd(m10 - m01, sq); qx = mv_szd(m02 + m20, sq); qy = mv_szd(m12 + m21, sq); qz = 0.25f * sq;
+        const float sq = sqrtf(ref_clamp_min(1.f + m22 - m00 - m11, 1e-6f)) * 2.f;
+        qw = ref_szd(m10 - m01, sq); qx = ref_szd(m02 + m20, sq); qy = ref_szd(m12 + m21, sq); qz = 0.25f * sq;
     }
-    const float s2 = qx * qx + qy * qy + qz * qz;
-    const float s = sqrtf(mv_clamp_min(s2, 1e-6f));
-    const float two_theta = 2.f * (qw < 0.f ? mv_safe_atan2(-s, -qw) : mv_safe_atan2(s, qw));
-    const float k = s2 > 0.f ? mv_szd(two_theta, s) : 2.f;
-    aa[0] = qx * k; aa[1] = qy * k; aa[2] = qz * k;
-}
-
-// angle_axis_to_rotation_matrix (:282-333): the Rodrigues form above theta^2 = 1e-6, the first-order form below
-__device__ inline void mv_angle_axis_to_rotmat(const float* aa, float* m) {
-    const float rx = aa[0], ry = aa[1], rz = aa[2];
-    const float theta2 = rx * rx + ry * ry + rz * rz;
-    if (theta2 > 1e-6f) {
-        const float theta = sqrtf(mv_clamp_min(theta2, 1e-6f));
-        const float wx = rx / (theta + 1e-6f), wy = ry / (theta + 1e-6f), wz = rz / (theta + 1e-6f);
-        const float c = cosf(theta), s = sinf(theta), t = 1.f - c;
-        m[0] = c + wx * wx * t;        m[1] = wx * wy * t - wz * s;   m[2] = wy * s + wx * wz * t;
-        m[3] = wz * s + wx * wy * t;   m[4] = c + wy * wy * t;        m[5] = -wx * s + wy * wz * t;
-        m[6] = -wy * s + wx * wz * t;  m[7] = wx * s + wy * wz * t;   m[8] = c + wz * wz * t;
-    } else {
-        m[0] = 1.f; m[1] = -rz; m[2] = ry;
-        m[3] = rz;  m[4] = 1.f; m[5] = -rx;
-        m[6] = -ry; m[7] = rx;  m[8] = 1.f;
-    }
+    const float q[4] = {qw, qx, qy, qz};
+    ref_quat_to_angle_axis(q, aa);
 }
 
 __device__ inline float mv_elu(float x) { return x > 0.f ? x : expm1f(x); }

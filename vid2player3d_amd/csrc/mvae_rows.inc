@@ -125,7 +125,7 @@
                     aa[1] = (base[2] + res[1]) * MV_PI;
                     aa[2] = (base[3] + res[2]) * MV_PI;
                 }
-                mv_angle_axis_to_rotmat(aa, m);
+                ref_angle_axis_to_rotmat(aa, m);
                 r6[0] = m[0]; r6[1] = m[3]; r6[2] = m[6]; r6[3] = m[1]; r6[4] = m[4]; r6[5] = m[7];
                 for (int k = 0; k < 6; ++k) a.b.joint_rot6d[e * (MV_JOINTS * 6) + j * 6 + k] = r6[k];
             }

@@ -15,6 +15,7 @@
 // same operations in the same order.  The tree and the order of the engine's bodies are the caller's (v2p_mvae_target_cfg); the
 // launcher derives the level of every joint and the inverse body order from them.
 #include "mvae_target.hpp"
+#include "ref_rotations.hpp"
 
 namespace v2p {
 
@@ -38,72 +39,6 @@ struct MtArgs {
     int32_t fix_lo, fix_hi;           // the levels that hold a descendant (or self) of Neck or Head: what the head rule's second pass redoes
 };
 
-// x.clamp_min(lo) as torch evaluates it: a NaN stays a NaN
-__device__ inline float mt_clamp_min(float x, float lo) { return x < lo ? lo : x; }
-// safe_zero_division (utils/konia_transform.py:336-344)
-__device__ inline float mt_szd(float num, float den) {
-    if (fabsf(den) < 1e-6f) den += 1e-6f;
-    return num / den;
-}
-// torch_safe_atan2 (:41-49)
-__device__ inline float mt_safe_atan2(float y, float x) {
-    if (fabsf(y) < 1e-6f && fabsf(x) < 1e-6f) y += 1e-6f;
-    return atan2f(y, x);
-}
-
-// rotation_matrix_to_quaternion (:347-438): m row-major -> (w, x, y, z), the branch torch.where selects
-__device__ inline void mt_rotmat_to_quat(const float* m, float* q) {
-    const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
-    const float trace = m00 + m11 + m22;
-    if (trace > 0.f) {
-        const float sq = sqrtf(mt_clamp_min(trace + 1.f, 1e-6f)) * 2.f;
-        q[0] = 0.25f * sq; q[1] = mt_szd(m21 - m12, sq); q[2] = mt_szd(m02 - m20, sq); q[3] = mt_szd(m10 - m01, sq);
-    } else if (m00 > m11 && m00 > m22) {
-        const float sq = sqrtf(mt_clamp_min(1.f + m00 - m11 - m22, 1e-6f)) * 2.f;
-        q[0] = mt_szd(m21 - m12, sq); q[1] = 0.25f * sq; q[2] = mt_szd(m01 + m10, sq); q[3] = mt_szd(m02 + m20, sq);
-    } else if (m11 > m22) {
-        const float sq = sqrtf(mt_clamp_min(1.f + m11 - m00 - m22, 1e-6f)) * 2.f;
-        q[0] = mt_szd(m02 - m20, sq); q[1] = mt_szd(m01 + m10, sq); q[2] = 0.25f * sq; q[3] = mt_szd(m12 + m21, sq);
-    } else {
-        const float sq = sqrtf(mt_clamp_min(1.f + m22 - m00 - m11, 1e-6f)) * 2.f;
-        q[0] = mt_szd(m10 - m01, sq); q[1] = mt_szd(m02 + m20, sq); q[2] = mt_szd(m12 + m21, sq); q[3] = 0.25f * sq;
-    }
-}
-
-// quaternion_to_angle_axis (:557-628) of (w, x, y, z)
-__device__ inline void mt_quat_to_angle_axis(const float* q, float* aa) {
-    const float s2 = q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-    const float s = sqrtf(mt_clamp_min(s2, 1e-6f));
-    const float two_theta = 2.f * (q[0] < 0.f ? mt_safe_atan2(-s, -q[0]) : mt_safe_atan2(s, q[0]));
-    const float k = s2 > 0.f ? mt_szd(two_theta, s) : 2.f;
-    aa[0] = q[1] * k; aa[1] = q[2] * k; aa[2] = q[3] * k;
-}
-
-// rotation_matrix_to_angle_axis (:631-655)
-__device__ inline void mt_rotmat_to_angle_axis(const float* m, float* aa) {
-    float q[4];
-    mt_rotmat_to_quat(m, q);
-    mt_quat_to_angle_axis(q, aa);
-}
-
-// angle_axis_to_rotation_matrix (:282-333): the Rodrigues form above theta^2 = 1e-6, the first-order form below
-__device__ inline void mt_angle_axis_to_rotmat(const float* aa, float* m) {
-    const float rx = aa[0], ry = aa[1], rz = aa[2];
-    const float theta2 = rx * rx + ry * ry + rz * rz;
-    if (theta2 > 1e-6f) {
-        const float theta = sqrtf(mt_clamp_min(theta2, 1e-6f));
-        const float wx = rx / (theta + 1e-6f), wy = ry / (theta + 1e-6f), wz = rz / (theta + 1e-6f);
-        const float c = cosf(theta), s = sinf(theta), t = 1.f - c;
-        m[0] = c + wx * wx * t;        m[1] = wx * wy * t - wz * s;   m[2] = wy * s + wx * wz * t;
-        m[3] = wz * s + wx * wy * t;   m[4] = c + wy * wy * t;        m[5] = -wx * s + wy * wz * t;
-        m[6] = -wy * s + wx * wz * t;  m[7] = wx * s + wy * wz * t;   m[8] = c + wz * wz * t;
-    } else {
-        m[0] = 1.f; m[1] = -rz; m[2] = ry;
-        m[3] = rz;  m[4] = 1.f; m[5] = -rx;
-        m[6] = -ry; m[7] = rx;  m[8] = 1.f;
-    }
-}
-
 // dof_vel of one body (:915-917): quat_mul_norm(quat_inverse(prev), cur) -> quat_to_angle_axis -> axis * angle / dt; quaternions
 // (x, y, z, w), utils/torch_utils.py:14-103 with isaacgym's quat_mul
 __device__ inline void mt_quat_diff_velocity(const float* prev, const float* cur, float dt, float* v) {
@@ -120,7 +55,7 @@ __device__ inline void mt_quat_diff_velocity(const float* prev, const float* cur
     float z = qq - zz + (z1 + y1) * (w2 - x2);
     const float sign = 1.f - 2.f * (w < 0.f ? 1.f : 0.f);  // quat_pos
     x = sign * x; y = sign * y; z = sign * z; w = sign * w;
-    const float nrm = mt_clamp_min(sqrtf(x * x + y * y + z * z + w * w), 1e-9f);  // quat_unit
+    const float nrm = ref_clamp_min(sqrtf(x * x + y * y + z * z + w * w), 1e-9f);  // quat_unit
     x = x / nrm; y = y / nrm; z = z / nrm; w = w / nrm;
     // quat_to_angle_axis (:82-103): a NaN of sqrt / acos (w a rounding above 1) fails the mask like the reference's
     const float sin_theta = sqrtf(1.f - w * w);
@@ -200,17 +135,17 @@ __global__ __launch_bounds__(MT_THREADS) void mvae_target_kernel(const MtArgs a)
     if (!RESET && a.c.fix_head_orientation) {
         // the head rule (:605-634), by every lane on its own transform; the head's lane has the answer
         float q[4];
-        mt_rotmat_to_quat(R, q);
+        ref_rotmat_to_quat(R, q);
         // quaternion_to_rotation_matrix (utils/konia_transform.py:474-549) x (0, 0, 1): the third column's x and y
-        const float qn = mt_clamp_min(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);
+        const float qn = ref_clamp_min(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);
         const float w = q[0] / qn, x = q[1] / qn, y = q[2] / qn, z = q[3] / qn;
         const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z;
         float l0 = tz * x + ty * w, l1 = tz * y - tx * w;
-        const float ln = mt_clamp_min(sqrtf(l0 * l0 + l1 * l1), 1e-12f);
+        const float ln = ref_clamp_min(sqrtf(l0 * l0 + l1 * l1), 1e-12f);
         l0 = l0 / ln; l1 = l1 / ln;
         const float ball_x = b.ball_state[er * 13], ball_y = b.ball_state[er * 13 + 1];
         float h0 = ball_x - (p[0] - (bind0[0] - root[0])), h1 = ball_y - (p[1] - (bind0[1] - root[1]));
-        const float hn = mt_clamp_min(sqrtf(h0 * h0 + h1 * h1), 1e-12f);
+        const float hn = ref_clamp_min(sqrtf(h0 * h0 + h1 * h1), 1e-12f);
         h0 = h0 / hn; h1 = h1 / hn;
         float diff = atan2f(h1, h0) - atan2f(l1, l0);
         if (diff > MT_PI) diff = diff - 2.f * MT_PI;
@@ -220,9 +155,9 @@ __global__ __launch_bounds__(MT_THREADS) void mvae_target_kernel(const MtArgs a)
         diff = __shfl(diff, a.c.smpl_head, MT_LANES);
         if (joint && (j == a.c.smpl_head || j == a.c.smpl_neck)) {
             float aa[3];
-            mt_rotmat_to_angle_axis(m, aa);
+            ref_rotmat_to_angle_axis(m, aa);
             aa[1] = aa[1] + diff / 2.f;
-            mt_angle_axis_to_rotmat(aa, m);
+            ref_angle_axis_to_rotmat(aa, m);
             if (live) {
 #pragma unroll
                 for (int k = 0; k < 9; ++k) b.joint_rotmat[e * (MT_JOINTS * 9) + j * 9 + k] = m[k];
@@ -235,8 +170,8 @@ __global__ __launch_bounds__(MT_THREADS) void mvae_target_kernel(const MtArgs a)
     float* row = s_row[slot];
     if (joint) {
         float q[4], aa[3];
-        mt_rotmat_to_quat(R, q);
-        mt_rotmat_to_angle_axis(m, aa);
+        ref_rotmat_to_quat(R, q);
+        ref_rotmat_to_angle_axis(m, aa);
         const float cur[4] = {q[1], q[2], q[3], q[0]};
 #pragma unroll
         for (int k = 0; k < 4; ++k) row[MS_RB_ROT + 4 * body + k] = cur[k];

@@ -16,7 +16,7 @@
         int64_t wl = b.wrist_link[e];
         wl = wl < 0 ? 0 : (wl > V2P_NUM_BODIES - 1 ? V2P_NUM_BODIES - 1 : wl);
         const float* q = rb + wl * 13 + 3;
-        const float n = tt_clamp_min(sqrtf(q[3] * q[3] + q[0] * q[0] + q[1] * q[1] + q[2] * q[2]), 1e-12f);
+        const float n = ref_clamp_min(sqrtf(q[3] * q[3] + q[0] * q[0] + q[1] * q[1] + q[2] * q[2]), 1e-12f);
         const float w = q[3] / n, x = q[0] / n, y = q[1] / n, z = q[2] / n;
         const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z;
         const float m[9] = {1.f - (ty * y + tz * z), ty * x - tz * w, tz * x + ty * w, ty * x + tz * w, 1.f - (tx * x + tz * z),

@@ -17,6 +17,7 @@
 // in-estimator's state, table row and direction) crosses the halves lane to lane.
 #include <type_traits>
 
+#include "ref_rotations.hpp"
 #include "tennis_task.hpp"
 
 namespace v2p {
@@ -41,8 +42,7 @@ struct TennisArgs {
     float g_lo[5], g_top[5], g_step[5], vx_hi, vy_hi, ty_hi, dim1, dim2;
 };
 
-// x.clamp_min(lo) / torch.clamp as torch evaluates them: a NaN stays a NaN (fmaxf / fminf would drop it)
-__device__ inline float tt_clamp_min(float x, float lo) { return x < lo ? lo : x; }
+// torch.clamp as torch evaluates it: a NaN stays a NaN (fminf / fmaxf would drop it); clamp_min is ref_rotations.hpp's
 __device__ inline float tt_clamp(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // round((clamp(v, lo, hi - step) - lo) / step), float32, halves to even (torch.round)
@@ -57,7 +57,7 @@ __device__ inline bool tt_in_court(float x, float y) { return (x > TT_COURT_X0) 
 // quaternion_to_rotation_matrix with its default order WXYZ (utils/torch_transform.py:249-250, konia_transform.py:474-549), so the four
 // numbers are unpacked as w, x, y, z = q[0], q[1], q[2], q[3]; rot6d = columns 0 and 1 of that matrix
 __device__ inline float tt_rot6d(const float* q4, int k) {
-    const float n = tt_clamp_min(sqrtf(q4[0] * q4[0] + q4[1] * q4[1] + q4[2] * q4[2] + q4[3] * q4[3]), 1e-12f);
+    const float n = ref_clamp_min(sqrtf(q4[0] * q4[0] + q4[1] * q4[1] + q4[2] * q4[2] + q4[3] * q4[3]), 1e-12f);
     const float w = q4[0] / n, x = q4[1] / n, y = q4[2] / n, z = q4[3] / n;
     const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z;
     switch (k) {
@@ -298,7 +298,7 @@ __device__ inline float th_cell(const TennisHandArgs& h, int g, float v) {
 // spin * 2 pi * normalize(cross(vel, (0, 0, -1))) as torch evaluates it (:70-71, 76-77)
 __device__ inline void th_ang_vel(const float* v, float spin, float* out) {
     const float c0 = v[1] * -1.f - v[2] * 0.f, c1 = v[2] * 0.f - v[0] * -1.f, c2 = v[0] * 0.f - v[1] * 0.f;
-    const float n = tt_clamp_min(sqrtf(c0 * c0 + c1 * c1 + c2 * c2), 1e-12f);
+    const float n = ref_clamp_min(sqrtf(c0 * c0 + c1 * c1 + c2 * c2), 1e-12f);
     const float mag = spin * 3.14159265358979323846f * 2.f;
     out[0] = mag * (c0 / n);
     out[1] = mag * (c1 / n);

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ref_rotations import angle_axis_to_rotmat_reference, rot6d_to_rotmat_reference, rotmat_to_angle_axis_reference
 
 FRAME, LATENT, HIDDEN, EXPERTS, GATE = 288, 32, 256, 6, 64
 OUT = FRAME + 2  # the feature and the two phase numbers
@@ -188,82 +189,6 @@ def decoder_reference(w, z, c, dt=np.float32, probes=None):
     if probes is not None:
         probes["coef"] = coef
     return h.astype(dt)
-
-
-def _norm(v):
-    return np.sqrt((v * v).sum(-1))
-
-
-def rot6d_to_rotmat_reference(r6, dt=np.float32, probes=None):
-    """rot6d_to_rotmat (utils/torch_transform.py:221-235): [..., 6] -> [..., 3, 3], columns b1 b2 b3."""
-    r6 = np.asarray(r6, dtype=dt)
-    a1, a2 = r6[..., :3].copy(), r6[..., 3:].copy()
-    small = _norm(a1) < dt(1e-8)
-    if probes is not None:
-        probes.setdefault("rot6d_norm", []).append(_norm(a1).ravel())
-    a1[small] = np.array([1, 0, 0], dt)
-    b1 = a1 / np.maximum(_norm(a1), dt(1e-9))[..., None]
-    u = a2 - (b1 * a2).sum(-1)[..., None] * b1
-    b2 = u / np.maximum(_norm(u), dt(1e-9))[..., None]
-    small = _norm(b2) < dt(1e-8)
-    if probes is not None:
-        probes.setdefault("rot6d_norm", []).append(_norm(u).ravel())
-    b2[small] = np.array([0, 1, 0], dt)
-    return np.stack([b1, b2, np.cross(b1, b2)], -1)
-
-
-def _szd(num, den, dt):
-    den = np.where(np.abs(den) < dt(1e-6), den + dt(1e-6), den)
-    return num / den
-
-
-def rotmat_to_angle_axis_reference(m, dt=np.float32, probes=None):
-    """rotation_matrix_to_angle_axis (utils/konia_transform.py:631-655, through the wxyz quaternion): [..., 3, 3] -> [..., 3]."""
-    m = np.asarray(m, dtype=dt)
-    m00, m01, m02, m10, m11, m12, m20, m21, m22 = [m[..., i, j] for i in range(3) for j in range(3)]
-    one, two, eps = dt(1), dt(2), dt(1e-6)
-    trace = m00 + m11 + m22
-    with np.errstate(invalid="ignore", divide="ignore"):
-        sq = np.sqrt(np.maximum(trace + one, eps)) * two
-        c0 = np.stack([dt(0.25) * sq, _szd(m21 - m12, sq, dt), _szd(m02 - m20, sq, dt), _szd(m10 - m01, sq, dt)], -1)
-        sq = np.sqrt(np.maximum(one + m00 - m11 - m22, eps)) * two
-        c1 = np.stack([_szd(m21 - m12, sq, dt), dt(0.25) * sq, _szd(m01 + m10, sq, dt), _szd(m02 + m20, sq, dt)], -1)
-        sq = np.sqrt(np.maximum(one + m11 - m00 - m22, eps)) * two
-        c2 = np.stack([_szd(m02 - m20, sq, dt), _szd(m01 + m10, sq, dt), dt(0.25) * sq, _szd(m12 + m21, sq, dt)], -1)
-        sq = np.sqrt(np.maximum(one + m22 - m00 - m11, eps)) * two
-        c3 = np.stack([_szd(m10 - m01, sq, dt), _szd(m02 + m20, sq, dt), _szd(m12 + m21, sq, dt), dt(0.25) * sq], -1)
-        q = np.where((trace > 0)[..., None], c0, np.where(((m00 > m11) & (m00 > m22))[..., None], c1, np.where((m11 > m22)[..., None], c2, c3)))
-        w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
-        s2 = x * x + y * y + z * z
-        s = np.sqrt(np.maximum(s2, eps))
-        two_theta = two * np.where(w < 0, np.arctan2(-s, -w), np.arctan2(s, w))  # (s >= 1e-3: torch_safe_atan2 never shifts)
-        k = np.where(s2 > 0, _szd(two_theta, s, dt), two)
-    if probes is not None:
-        tp = trace <= 0
-        probes.setdefault("trace", []).append(trace.ravel())
-        probes.setdefault("diagonal", []).extend([(m00 - m11)[tp].ravel(), (m00 - m22)[tp].ravel(), (m11 - m22)[tp].ravel()])
-        probes.setdefault("quat_w", []).append(w.ravel())
-        probes.setdefault("sin2", []).append(s2.ravel())
-    return (q[..., 1:] * k[..., None]).astype(dt)
-
-
-def angle_axis_to_rotmat_reference(aa, dt=np.float32, probes=None):
-    """angle_axis_to_rotation_matrix (utils/konia_transform.py:282-333): [..., 3] -> [..., 3, 3]."""
-    aa = np.asarray(aa, dtype=dt)
-    rx, ry, rz = aa[..., 0], aa[..., 1], aa[..., 2]
-    theta2 = rx * rx + ry * ry + rz * rz
-    eps, one = dt(1e-6), dt(1)
-    theta = np.sqrt(np.maximum(theta2, eps))
-    wx, wy, wz = rx / (theta + eps), ry / (theta + eps), rz / (theta + eps)
-    c, s = np.cos(theta), np.sin(theta)
-    t = one - c
-    normal = np.stack([c + wx * wx * t, wx * wy * t - wz * s, wy * s + wx * wz * t, wz * s + wx * wy * t, c + wy * wy * t, -wx * s + wy * wz * t,
-                       -wy * s + wx * wz * t, wx * s + wy * wz * t, c + wz * wz * t], -1)
-    o = np.ones_like(rx)
-    taylor = np.stack([o, -rz, ry, rz, o, -rx, -ry, rx, o], -1)
-    if probes is not None:
-        probes.setdefault("theta2", []).append(theta2.ravel())
-    return np.where((theta2 > eps)[..., None], normal, taylor).reshape(aa.shape[:-1] + (3, 3)).astype(dt)
 
 
 def _residual_bases(st, phase, swing, dt):

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ref_rotations import angle_axis_to_rotmat_reference, rotmat_to_angle_axis_reference, rotmat_to_quat_reference
 from .body_shapes import SMPL_JOINT_NAMES
 
 NUM_JOINTS = 24
@@ -124,74 +125,6 @@ def launch_actions(st, tensors, n, actions_in, actions_out, num_shapes=1):
 def _probe(probes, key, v):
     if probes is not None:
         probes.setdefault(key, []).append(np.asarray(v, dtype=np.float64).ravel())
-
-
-def _szd(num, den, dt):
-    den = np.where(np.abs(den) < dt(1e-6), den + dt(1e-6), den)
-    return num / den
-
-
-def rotmat_to_quat_reference(m, dt=np.float32, probes=None):
-    """rotation_matrix_to_quaternion (utils/konia_transform.py:347-438): [..., 3, 3] -> [..., 4] (w, x, y, z)."""
-    m = np.asarray(m, dtype=dt)
-    m00, m01, m02, m10, m11, m12, m20, m21, m22 = [m[..., i, j] for i in range(3) for j in range(3)]
-    one, two, eps = dt(1), dt(2), dt(1e-6)
-    trace = m00 + m11 + m22
-    with np.errstate(invalid="ignore", divide="ignore"):
-        sq = np.sqrt(np.maximum(trace + one, eps)) * two
-        c0 = np.stack([dt(0.25) * sq, _szd(m21 - m12, sq, dt), _szd(m02 - m20, sq, dt), _szd(m10 - m01, sq, dt)], -1)
-        sq = np.sqrt(np.maximum(one + m00 - m11 - m22, eps)) * two
-        c1 = np.stack([_szd(m21 - m12, sq, dt), dt(0.25) * sq, _szd(m01 + m10, sq, dt), _szd(m02 + m20, sq, dt)], -1)
-        sq = np.sqrt(np.maximum(one + m11 - m00 - m22, eps)) * two
-        c2 = np.stack([_szd(m02 - m20, sq, dt), _szd(m01 + m10, sq, dt), dt(0.25) * sq, _szd(m12 + m21, sq, dt)], -1)
-        sq = np.sqrt(np.maximum(one + m22 - m00 - m11, eps)) * two
-        c3 = np.stack([_szd(m10 - m01, sq, dt), _szd(m02 + m20, sq, dt), _szd(m12 + m21, sq, dt), dt(0.25) * sq], -1)
-    b1, b2 = (m00 > m11) & (m00 > m22), m11 > m22
-    q = np.where((trace > 0)[..., None], c0, np.where(b1[..., None], c1, np.where(b2[..., None], c2, c3)))
-    if probes is not None:
-        tp = trace <= 0
-        _probe(probes, "trace", trace)
-        # the diagonal comparisons that decide: both of branch 1 unless the other already fails, the third only where branch 1 is not taken
-        _probe(probes, "diagonal", np.where(tp & (m00 > m22), m00 - m11, np.inf))
-        _probe(probes, "diagonal", np.where(tp & (m00 > m11), m00 - m22, np.inf))
-        _probe(probes, "diagonal", np.where(tp & ~b1, m11 - m22, np.inf))
-        probes.setdefault("branch", []).append(np.where(trace > 0, 0, np.where(b1, 1, np.where(b2, 2, 3))).ravel())
-    return q.astype(dt)
-
-
-def quat_to_angle_axis_reference(q, dt=np.float32, probes=None):
-    """quaternion_to_angle_axis (utils/konia_transform.py:557-628) of (w, x, y, z)."""
-    q = np.asarray(q, dtype=dt)
-    w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
-    two, eps = dt(2), dt(1e-6)
-    s2 = x * x + y * y + z * z
-    s = np.sqrt(np.maximum(s2, eps))
-    with np.errstate(invalid="ignore", divide="ignore"):
-        two_theta = two * np.where(w < 0, np.arctan2(-s, -w), np.arctan2(s, w))  # (s >= 1e-3: torch_safe_atan2 never shifts)
-        k = np.where(s2 > 0, _szd(two_theta, s, dt), two)
-    _probe(probes, "cos_theta", w)
-    return (q[..., 1:] * k[..., None]).astype(dt)
-
-
-def rotmat_to_angle_axis_reference(m, dt=np.float32, probes=None):
-    return quat_to_angle_axis_reference(rotmat_to_quat_reference(m, dt, probes), dt, probes)
-
-
-def angle_axis_to_rotmat_reference(aa, dt=np.float32):
-    """angle_axis_to_rotation_matrix (utils/konia_transform.py:282-333): [..., 3] -> [..., 3, 3]."""
-    aa = np.asarray(aa, dtype=dt)
-    rx, ry, rz = aa[..., 0], aa[..., 1], aa[..., 2]
-    theta2 = rx * rx + ry * ry + rz * rz
-    eps, one = dt(1e-6), dt(1)
-    theta = np.sqrt(np.maximum(theta2, eps))
-    wx, wy, wz = rx / (theta + eps), ry / (theta + eps), rz / (theta + eps)
-    c, s = np.cos(theta), np.sin(theta)
-    t = one - c
-    normal = np.stack([c + wx * wx * t, wx * wy * t - wz * s, wy * s + wx * wz * t, wz * s + wx * wy * t, c + wy * wy * t, -wx * s + wy * wz * t,
-                       -wy * s + wx * wz * t, wx * s + wy * wz * t, c + wz * wz * t], -1)
-    o = np.ones_like(rx)
-    taylor = np.stack([o, -rz, ry, rz, o, -rx, -ry, rx, o], -1)
-    return np.where((theta2 > eps)[..., None], normal, taylor).reshape(aa.shape[:-1] + (3, 3)).astype(dt)
 
 
 def _chain(rotmat, bind, parents, dt):
