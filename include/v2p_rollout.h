@@ -35,7 +35,7 @@ extern "C" {
 #define V2P_MOTION_STATE_DIM 331  /* root_pos3 root_rot4 dof_pos69 root_vel3 root_ang_vel3 dof_vel69 key_pos12 rb_pos72 rb_rot96 */
 #define V2P_CONTEXT_DIM 378       /* body_pos72 body_rot96 dof_pos69 body_pos_gt72 dof_pos_gt69 (humanoid_smpl_im.py:202) */
 #define V2P_CONTEXT_DIM_CONF 402  /* ... + joint_conf24: the frame of a batch with a context transform (humanoid_smpl_im.py:202-205) */
-#define V2P_ABI_VERSION 14
+#define V2P_ABI_VERSION 15
 
 typedef enum {
     V2P_OK = 0,
@@ -43,7 +43,8 @@ typedef enum {
     V2P_ERR_UNSUPPORTED = -2, /* valid in the reference, not built yet (e.g. anisotropic joint gains) */
     V2P_ERR_HIP = -3,         /* HIP runtime error */
     V2P_ERR_NOMEM = -4,
-    V2P_ERR_INTERNAL = -5     /* the engine noticed that a launch did not do all it should have (v2p_env_check: skipped substep jobs) */
+    V2P_ERR_INTERNAL = -5     /* the engine noticed that a launch did not do all it should have (v2p_env_check: skipped substep jobs),
+                               * or that its own device memory was written outside an array (v2p_env_check under v2p_debug_guards) */
 } v2p_status;
 
 typedef struct v2p_model v2p_model; /* body model (host copy + device constants) */
@@ -857,6 +858,21 @@ int v2p_env_check(v2p_env* e, void* stream);
 int v2p_env_check_async(v2p_env* e, void* stream);
 int v2p_env_job_recoveries(v2p_env* e, int64_t* count);
 int v2p_env_jobs_skipped(v2p_env* e, int64_t* count);
+
+/* Guard zones and poison for the engine's own device arrays (ABI 15; a debugging aid of the test suite, off by default).
+ * v2p_debug_guards sets the process-wide zone size and returns the previous one: 0 = off, otherwise a multiple of 256 bytes up to 1 MiB
+ * (anything else: V2P_ERR_INVALID, nothing changed).  It is read when a batch allocates; a batch keeps what it was created with.  While
+ * it is on, every array of a batch lies between two zones of 0xff bytes - the back zone begins at the array's end to the byte - and an
+ * array the engine leaves unfilled is poisoned: 0xff bytes (a NaN) for float / double arrays, 0x00 for every other type (integer arrays
+ * hold indices; zero is what a fresh page holds, so the poison cannot form a wild index).  v2p_env_check then also copies the zones back
+ * and returns V2P_ERR_INTERNAL with a message that names the array, the side and the first byte when one was written.  Not seen: a store
+ * past one slot of a structure-of-arrays buffer that stays inside the allocation, and a read-before-write of an integer array.
+ * v2p_env_guard_counts: the arrays of the batch that lie between zones, and the float arrays among them that were poisoned (0, 0 for a
+ * batch created with guards off).  v2p_debug_guards_selftest: writes one byte in front of one small array of its own and four bytes
+ * behind another with hipMemset - inside its own allocations - and returns V2P_OK only when exactly that is reported. */
+int v2p_debug_guards(int64_t zone_bytes);
+int v2p_debug_guards_selftest(int device);
+int v2p_env_guard_counts(const v2p_env* e, int64_t* guarded, int64_t* poisoned);
 
 const char* v2p_last_error(void);
 int v2p_abi_version(void);

@@ -91,7 +91,7 @@ int main(void){ printf("%zu %zu %zu %zu %zu %zu\n", sizeof(v2p_ball_sim), offset
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
     S, O = _lib.BallSim, _lib.BallRolloutOut
     assert got == [C.sizeof(S), S.sim_dt.offset, S.enable_ground.offset, S.grid_x.offset, C.sizeof(O), O.traj_y.offset]
-    assert _lib.ABI_VERSION == 14
+    assert _lib.ABI_VERSION == 15
 
 
 def test_resample_reference_on_a_parabola():

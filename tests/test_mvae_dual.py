@@ -193,7 +193,7 @@ def lib():
 
 def test_bad_arguments_are_refused_without_a_gpu(lib):
     """every refusal comes before any HIP call (the pointers are never dereferenced)"""
-    assert lib.v2p_abi_version() == 14
+    assert lib.v2p_abi_version() == 15
     full = lambda names: {k: 0x1000 for k in names}
     st = DX.settings("A")
     cfgs = lambda **change: (_lib.MvaeCfg * 2)(*(mvae.cfg_struct(dict(s, **{k: x[i] for k, x in change.items()})) for i, s in enumerate(st["sides"])))

@@ -164,7 +164,7 @@ def test_struct_sizes_match_the_header(tmp_path):
     subprocess.check_call(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", exe])
     sizes = [int(x) for x in subprocess.check_output([exe]).split()]
     assert sizes == [ctypes.sizeof(_lib.TennisDualCfg), ctypes.sizeof(_lib.TennisDualBuffers)]
-    assert _lib.ABI_VERSION == 14
+    assert _lib.ABI_VERSION == 15
 
 
 def _mod(struct, **fields):

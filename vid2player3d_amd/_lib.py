@@ -13,7 +13,7 @@ NUM_BODIES, NUM_DOF, NUM_ACTIONS, NUM_OBS = 24, 69, 75, 461
 MOTION_STATE_DIM, CONTEXT_DIM = 331, 378
 CONTEXT_DIM_CONF = CONTEXT_DIM + NUM_BODIES  # frames of a batch with a context transform: + joint_conf (humanoid_smpl_im.py:202-205)
 CTX_MASK_JOINTS, CTX_NOISY_JOINTS, CTX_MASK_RANDOM_JOINTS = 1, 2, 3  # v2p_context_transform.ops
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 c_f = C.POINTER(C.c_float)
 c_i32 = C.POINTER(C.c_int32)
@@ -241,6 +241,9 @@ def load():
         "v2p_mvae_target_step": [C.POINTER(MvaeTargetCfg), C.c_int64, C.POINTER(MvaeTargetBuffers), vp],
         "v2p_mvae_target_reset": [C.POINTER(MvaeTargetCfg), C.c_int64, C.POINTER(MvaeTargetBuffers), vp, C.c_int64, vp],
         "v2p_mvae_target_actions": [C.POINTER(MvaeTargetCfg), C.c_int64, vp, C.POINTER(MvaeTargetBuffers), vp, vp],
+        "v2p_debug_guards": [C.c_int64],
+        "v2p_debug_guards_selftest": [C.c_int],
+        "v2p_env_guard_counts": [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
         "v2p_env_profile_begin": [vp, C.c_int64],
         "v2p_env_profile_begin_sampled": [vp, C.c_int64, C.c_int32, C.c_int32],
         "v2p_env_profile_end": [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)],
@@ -261,6 +264,7 @@ EXPORTED_SYMBOLS = (
     "v2p_model_create", "v2p_model_destroy", "v2p_mlib_create", "v2p_mlib_destroy", "v2p_motion_state", "v2p_reward", "v2p_reset_flags",
     "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_obs_imitation_packed_w", "v2p_policy_head_w", "v2p_policy_head_record_w", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_set_context_transform", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
     "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_tennis_dual_step", "v2p_tennis_dual_handover", "v2p_mvae_step", "v2p_mvae_reset", "v2p_mvae_dual_step", "v2p_mvae_dual_reset", "v2p_mvae_target_step", "v2p_mvae_target_reset", "v2p_mvae_target_actions", "v2p_last_error", "v2p_abi_version",
+    "v2p_debug_guards", "v2p_debug_guards_selftest", "v2p_env_guard_counts",
 )
 
 

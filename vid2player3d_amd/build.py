@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libv2p_rollout.so")
 SOURCES = ["capi.hip", "device_owner.hip", "model_compile.hip", "env.hip", "motion_state.hip", "task_ops.hip", "shape_compile.hip", "motion_build.hip", "physics.hip", "physics_ll.hip", "physics_ll_host.hip", "ball_rollout.hip", "tennis_task.hip", "mvae_player.hip", "mvae_player_dual.hip", "mvae_target.hip"]
-HEADERS = ["v2p_internal.hpp", "ll_schedule.hpp", "ll_forms.hpp", "ll_contact_setup.inc", "v2p_dev.hpp", "v2p_math.inc", "phys_math.hpp", "phys_common.hpp", "motion_sample.inc", "hull_gjk.hpp", "post_ops.inc", "strict_ops.inc", "tennis_task.hpp", "tennis_row.inc", "mvae_player.hpp", "mvae_player_dev.hpp", "mvae_rows.inc", "mvae_target.hpp", "ref_rotations.hpp", os.path.join("..", "..", "include", "v2p_rollout.h")]
+HEADERS = ["v2p_internal.hpp", "device_guards.hpp", "ll_schedule.hpp", "ll_forms.hpp", "ll_contact_setup.inc", "v2p_dev.hpp", "v2p_math.inc", "phys_math.hpp", "phys_common.hpp", "motion_sample.inc", "hull_gjk.hpp", "post_ops.inc", "strict_ops.inc", "tennis_task.hpp", "tennis_row.inc", "mvae_player.hpp", "mvae_player_dev.hpp", "mvae_rows.inc", "mvae_target.hpp", "ref_rotations.hpp", os.path.join("..", "..", "include", "v2p_rollout.h")]
 ARCH = "gfx950"
 
 
@@ -41,7 +41,7 @@ LL_CODEGEN_FLAGS = ["-mllvm", "-sink-insts-to-avoid-spills=1"]
 LL_MATH_FLAGS = ["-fassociative-math", "-freciprocal-math", "-fno-signed-zeros", "-fno-trapping-math", "-fno-honor-nans"]
 # what the physics kernel is compiled from: the counters kept under profiles/ (VALU instructions, HBM bytes per launch) describe ONE
 # kernel; they carry this hash, and bench.py drops them from its line when the sources have moved on
-KERNEL_SOURCES = ["physics_ll.hip", "phys_common.hpp", "phys_math.hpp", "hull_gjk.hpp", "strict_ops.inc", "post_ops.inc", "v2p_math.inc", "motion_sample.inc", "v2p_internal.hpp", "ll_schedule.hpp", "ll_forms.hpp", "ll_contact_setup.inc", "v2p_dev.hpp"]
+KERNEL_SOURCES = ["physics_ll.hip", "phys_common.hpp", "phys_math.hpp", "hull_gjk.hpp", "strict_ops.inc", "post_ops.inc", "v2p_math.inc", "motion_sample.inc", "v2p_internal.hpp", "device_guards.hpp", "ll_schedule.hpp", "ll_forms.hpp", "ll_contact_setup.inc", "v2p_dev.hpp"]
 
 
 def kernel_source_hash():

@@ -341,7 +341,17 @@ int v2p_env_set_racket_shapes(v2p_env* e, const v2p_racket_geom* per_shape, int3
 int v2p_env_check(v2p_env* e, void* stream) {
     if (!e) { set_error("v2p_env_check: bad argument"); return V2P_ERR_INVALID; }
     DeviceGuard g(e->device);
-    int rc = check_hip(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+    int rc = V2P_OK;
+    if (!e->own.guarded) rc = check_hip(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+    else {  // (v2p_debug_guards was on when the batch was created; check_guards synchronises the stream itself)
+        std::vector<DeviceOwner::GuardDamage> d;
+        rc = e->own.check_guards((hipStream_t)stream, &d);
+        if (rc == V2P_OK && !d.empty()) {
+            set_error("v2p_env_check: %zu byte(s) written outside '%s' (%s %zu byte(s) %s), %zu damaged guard zone(s) in all", d[0].count, d[0].name,
+                      d[0].behind ? "first" : "nearest", d[0].first, d[0].behind ? "behind its end" : "before its start", d.size());
+            return V2P_ERR_INTERNAL;
+        }
+    }
     if (rc != V2P_OK || !e->sched.job_progress) return rc;
     int32_t count[2] = {0, 0};
     rc = check_hip(hipMemcpy(count, e->sched.job_progress + v2p::job_wave_slots(e->n), sizeof(count), hipMemcpyDeviceToHost), "hipMemcpy(job recovery counters)");
@@ -426,6 +436,13 @@ int v2p_env_profile_end(v2p_env* e, double* physics_ms_total, int64_t* launches)
     *launches = e->prof_n;
     profile_close(e);
     return rc;
+}
+
+int v2p_env_guard_counts(const v2p_env* e, int64_t* guarded, int64_t* poisoned) {
+    if (!e || !guarded || !poisoned) { set_error("v2p_env_guard_counts: bad argument"); return V2P_ERR_INVALID; }
+    *guarded = e->own.guarded;
+    *poisoned = e->own.poisoned;
+    return V2P_OK;
 }
 
 int v2p_env_kernel_build(const v2p_env* e) {  // (the build the NEXT launch of the batch runs)

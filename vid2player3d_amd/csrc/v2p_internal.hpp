@@ -4,9 +4,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "../../include/v2p_rollout.h"
+#include "device_guards.hpp"
 #include "ll_schedule.hpp"
 
 namespace v2p {
@@ -113,7 +115,7 @@ public:
     template <class T>
     int alloc(T** p, size_t count, const char* name, Fill fill = NO_FILL, const void* host = nullptr) {
         void* q = nullptr;
-        const int rc = device_bytes(&q, sizeof(T) * count, name, fill, host);
+        const int rc = device_bytes(&q, sizeof(T) * count, name, fill, host, std::is_floating_point<T>::value);
         if (rc == V2P_OK) *p = (T*)q;
         return rc;
     }
@@ -126,6 +128,19 @@ public:
     }
     int events(hipEvent_t** ev, size_t count, unsigned flags, const char* name);  // a host array of `count` events (name NULL: "hipEventCreate")
     void release(const void* p);  // one holding, ahead of the owner's end (NULL, or nothing the owner holds: no-op)
+    // Guard zones (v2p_debug_guards, device_guards.hpp): while the process-wide setting is on, every device allocation of this owner lies
+    // between two zones of GUARD_BYTE, and a NO_FILL array without a host source is poisoned - 0xff bytes (a NaN) where T is float or
+    // double, 0x00 everywhere else.  (Integer arrays hold indices: zero is what a fresh page holds in every run there has been, so no
+    // garbage index can be formed from the poison and a read-before-write of one cannot send a store astray on a shared GPU.  Such a read
+    // stays unseen.)  An allocation keeps what it was created with; with the setting off nothing here allocates, fills or copies.
+    struct GuardDamage {
+        const char* name;
+        bool behind;          // false: in front of the payload
+        size_t first, count;  // GuardScan::before_first / behind_first, and the damaged bytes of that side
+    };
+    // synchronises `s`, copies every zone of this owner to the host and scans it; V2P_OK when the copies succeeded, whatever they show
+    int check_guards(hipStream_t s, std::vector<GuardDamage>* damage) const;
+    int64_t guarded = 0, poisoned = 0;  // device allocations held with zones; NO_FILL floating-point arrays among them that were poisoned
 
 private:
     enum Kind { DEVICE, PINNED, EVENTS };
@@ -133,9 +148,13 @@ private:
         void* p;
         size_t count;
         Kind kind;
+        void* base;        // DEVICE: what hipMalloc returned (= p without zones)
+        size_t zone;       // DEVICE: bytes of each guard zone, 0 = none
+        const char* name;  // DEVICE: what the caller calls the buffer (a literal)
+        bool poisoned;     // DEVICE: a NO_FILL floating-point array that was filled with NaN
     };
     std::vector<Item> items;
-    int device_bytes(void** p, size_t bytes, const char* name, Fill fill, const void* host);
+    int device_bytes(void** p, size_t bytes, const char* name, Fill fill, const void* host, bool floating);
     int pinned_bytes(void** p, size_t bytes, const char* name);
     static void free_item(const Item& it);
 };

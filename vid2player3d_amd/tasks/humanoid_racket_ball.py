@@ -114,23 +114,23 @@ class HumanoidSMPLIMRacketBall(HumanoidSMPLIM):
         super().__init__(cfg, sim_params, physics_engine, device_type, device_id, headless)
         n, dev = self.num_envs, self.device
         nsim = self.control_freq_inv
-        f = dict(dtype=torch.float32, device=dev)
-        self._ball_root_states = torch.zeros((n, 13), **f)
+        B = self._buffer  # (guard rows under cfg env debug_guard_rows, like the base task's buffers)
+        self._ball_root_states = B("_ball_root_states", (n, 13))
         self._ball_root_states[:, 2] = 1.0   # start_pose of the ball actor (:430-431)
         self._ball_root_states[:, 6] = 1.0
-        self._racket_rb_state = torch.zeros((n, 13), **f)
-        self._ball_states_per_sim = torch.zeros((n, nsim, 13), **f)
-        self._racket_ball_contact_per_sim = torch.zeros((n, nsim), dtype=torch.int32, device=dev)
-        self._ball_contact_forces = torch.zeros((n, 2, 3), **f)
-        self._ball_body_contact_force = torch.zeros((n, 3), **f)  # on the ball from the humanoid's links (ball x hull contacts)
+        self._racket_rb_state = B("_racket_rb_state", (n, 13))
+        self._ball_states_per_sim = B("_ball_states_per_sim", (n, nsim, 13))
+        self._racket_ball_contact_per_sim = B("_racket_ball_contact_per_sim", (n, nsim), torch.int32)
+        self._ball_contact_forces = B("_ball_contact_forces", (n, 2, 3))
+        self._ball_body_contact_force = B("_ball_body_contact_force", (n, 3))  # on the ball from the humanoid's links (ball x hull contacts)
         # `_contact_forces_sum` (:186, 690, 781): net contact forces of the links after each simulate() call, summed over the control step
         # (opt-in, cfg env contact_forces_sum: nothing in the reference reads it, and keeping it costs the launch 2 %)
-        self._contact_forces_sum = torch.zeros((n, 24, 3), **f) if env.get("contact_forces_sum", False) else None
-        self._has_bounce = torch.zeros(n, dtype=torch.bool, device=dev)
-        self._has_bounce_now = torch.zeros(n, dtype=torch.bool, device=dev)
-        self._bounce_pos = torch.zeros((n, 3), **f)
-        self._has_racket_ball_contact = torch.zeros(n, dtype=torch.bool, device=dev)
-        self._has_racket_ball_contact_now = torch.zeros(n, dtype=torch.bool, device=dev)
+        self._contact_forces_sum = B("_contact_forces_sum", (n, 24, 3)) if env.get("contact_forces_sum", False) else None
+        self._has_bounce = B("_has_bounce", (n,), torch.bool)
+        self._has_bounce_now = B("_has_bounce_now", (n,), torch.bool)
+        self._bounce_pos = B("_bounce_pos", (n, 3))
+        self._has_racket_ball_contact = B("_has_racket_ball_contact", (n,), torch.bool)
+        self._has_racket_ball_contact_now = B("_has_racket_ball_contact_now", (n,), torch.bool)
         mat = dict(racket.BALL_MATERIAL)
         if "restitution" in self.cfg_v2p:  # cfg_v2p.restitution sets ball AND racket head (:414, :436); the plane keeps 0
             mat["rest_ground"], mat["rest_racket"] = 0.5 * self.cfg_v2p["restitution"], self.cfg_v2p["restitution"]
@@ -146,16 +146,8 @@ class HumanoidSMPLIMRacketBall(HumanoidSMPLIM):
                          restitution_body=mat["rest_body"], friction_body=mat["fric_body"], body_contacts=int(env.get("ball_body_contacts", True)),
                          bounce_height=BALL_R * (6 if self.sim_params.substeps > 2 else 4), poll_racket_hits=int(self.sim_params.substeps <= 2))
         _fill_racket(c, g)
-        b = _lib.BallBuffers(ball_state=self._ball_root_states.data_ptr(), racket_state=self._racket_rb_state.data_ptr(),
-                             ball_per_sim=self._ball_states_per_sim.data_ptr(), racket_hit_per_sim=self._racket_ball_contact_per_sim.data_ptr(),
-                             ball_contact=self._ball_contact_forces.data_ptr(), ball_body_contact=self._ball_body_contact_force.data_ptr(),
-                             has_bounce=self._has_bounce.data_ptr(), has_bounce_now=self._has_bounce_now.data_ptr(), bounce_pos=self._bounce_pos.data_ptr(),
-                             has_racket_contact=self._has_racket_ball_contact.data_ptr(), has_racket_contact_now=self._has_racket_ball_contact_now.data_ptr(),
-                             contact_force_sum=None if self._contact_forces_sum is None else self._contact_forces_sum.data_ptr())
-        _lib.check(self._lib.v2p_env_attach_ball(self._h_env, C.byref(c), C.byref(b)), "v2p_env_attach_ball")
-        if self.racket_players is not None:
-            geoms = (_lib.RacketGeom * 2)(*[racket_geom_struct(g) for g in self.racket_geometries])
-            _lib.check(self._lib.v2p_env_set_racket_shapes(self._h_env, geoms, 2), "v2p_env_set_racket_shapes")
+        self._ball_cfg = c
+        self._attach_ball()
         # the reference's per-env racket attributes (humanoid_smpl_im_mvae.py:68-82): the link the racket is welded to, and which player of
         # a pair is left-handed (-1: the single player is; None: no left hand)
         links = [g["racket_link"] for g in self.racket_geometries]
@@ -179,6 +171,20 @@ class HumanoidSMPLIMRacketBall(HumanoidSMPLIM):
             random_rows = bool(self.cfg_v2p.get("is_train", True)) or self.cfg_v2p.get("test_mode", "random") == "random"
             self._ball_generator = TennisBallGeneratorOffline(self.cfg_v2p["ball_traj_file" if random_rows else "ball_traj_file_test"], sample_random=random_rows,
                                                               num_envs=n, device=dev)
+
+    def _attach_ball(self):
+        """v2p_env_attach_ball with the task's buffers as they stand (a second call keeps the batch's ball and replaces its parameters and
+        buffers; the engine allocates its per-call partial sums of the links' contact forces the first time `_contact_forces_sum` is given)."""
+        b = _lib.BallBuffers(ball_state=self._ball_root_states.data_ptr(), racket_state=self._racket_rb_state.data_ptr(),
+                             ball_per_sim=self._ball_states_per_sim.data_ptr(), racket_hit_per_sim=self._racket_ball_contact_per_sim.data_ptr(),
+                             ball_contact=self._ball_contact_forces.data_ptr(), ball_body_contact=self._ball_body_contact_force.data_ptr(),
+                             has_bounce=self._has_bounce.data_ptr(), has_bounce_now=self._has_bounce_now.data_ptr(), bounce_pos=self._bounce_pos.data_ptr(),
+                             has_racket_contact=self._has_racket_ball_contact.data_ptr(), has_racket_contact_now=self._has_racket_ball_contact_now.data_ptr(),
+                             contact_force_sum=None if self._contact_forces_sum is None else self._contact_forces_sum.data_ptr())
+        _lib.check(self._lib.v2p_env_attach_ball(self._h_env, C.byref(self._ball_cfg), C.byref(b)), "v2p_env_attach_ball")
+        if self.racket_players is not None:
+            geoms = (_lib.RacketGeom * 2)(*[racket_geom_struct(g) for g in self.racket_geometries])
+            _lib.check(self._lib.v2p_env_set_racket_shapes(self._h_env, geoms, 2), "v2p_env_set_racket_shapes")
 
     # ------------------------------------------------------------------ two players: shapes by env, not by clip
     def _env_body_shapes(self, env):

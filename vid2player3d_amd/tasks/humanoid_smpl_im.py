@@ -392,30 +392,62 @@ class HumanoidSMPLIM:
         raise RuntimeError("no motion library: pass cfg['env']['motion_lib'] (MotionLib), 'synthetic_motions', a flat .npz / .v2pm 'motion_file' or the "
                            "reference's .pth file / directory of mlib_part_*.pth")
 
+    # ------------------------------------------------------------------ guard rows (cfg env debug_guard_rows)
+    GUARD_BYTE = 0x5A  # integer guard rows hold 0x5A5A5A5A5A5A5A5A (uint8 / bool: 0x5A), floating-point ones NaN
+
+    def _buffer(self, name, shape, dtype=torch.float32, fill=0, rows_per_env=1):
+        """A tensor the engine borrows.  With cfg env debug_guard_rows = G > 0 it is the contiguous middle slice of a tensor with
+        G x rows_per_env more rows on either side, which hold a fixed pattern that check() compares: a kernel that stores in front of or
+        behind its rows is named.  (G = 64 keeps the byte offset of every float32 / int64 view a multiple of 256, whatever the row width.)
+        With G = 0 it is what torch.zeros / torch.ones returned before."""
+        g = self._guard_rows * rows_per_env
+        if g == 0:
+            return torch.full(shape, fill, dtype=dtype, device=self.device) if fill else torch.zeros(shape, dtype=dtype, device=self.device)
+        full = torch.full((shape[0] + 2 * g,) + tuple(shape[1:]), fill, dtype=dtype, device=self.device)
+        for rows in (full[:g], full[g + shape[0]:]):
+            if dtype.is_floating_point:
+                rows.fill_(float("nan"))
+            else:
+                rows.view(torch.uint8).fill_(self.GUARD_BYTE)
+        self._guarded_buffers.append((name, full, g))
+        return full[g:g + shape[0]]
+
+    def _check_guard_rows(self):
+        for name, full, g in self._guarded_buffers:
+            for side, rows, first in (("in front of", full[:g], -g), ("behind", full[full.shape[0] - g:], 0)):
+                ok = torch.isnan(rows) if full.dtype.is_floating_point else rows.view(torch.uint8) == self.GUARD_BYTE
+                bad = ~ok.reshape(g, -1).all(dim=1)
+                if bool(bad.any()):
+                    k = int(torch.nonzero(bad)[0 if first == 0 else -1])
+                    raise RuntimeError("guard rows of '%s' were written: %d row(s) %s its %d rows, the nearest of them %d row(s) %s" %
+                                       (name, int(bad.sum()), side, full.shape[0] - 2 * g, k + 1 if first == 0 else g - k, side))
+
     def _allocate_buffers(self):
         n, dev = self.num_envs, self.device
         f = dict(dtype=torch.float32, device=dev)
-        i = dict(dtype=torch.long, device=dev)
-        self.obs_buf = torch.zeros((n, self.num_obs), **f)
-        self.states_buf = torch.zeros((n, self.num_states), **f)
-        self.rew_buf = torch.zeros(n, **f)
-        self.reset_buf = torch.ones(n, **i)
-        self.progress_buf = torch.zeros(n, **i)
-        self.randomize_buf = torch.zeros(n, **i)
-        self._terminate_buf = torch.ones(n, **i)
-        self._sub_rewards = torch.zeros((n, 4), **f)
+        self._guard_rows = int(self.cfg["env"].get("debug_guard_rows", 0))
+        self._guarded_buffers = []
+        B, i64 = self._buffer, torch.long
+        self.obs_buf = B("obs_buf", (n, self.num_obs))
+        self.states_buf = B("states_buf", (n, self.num_states))
+        self.rew_buf = B("rew_buf", (n,))
+        self.reset_buf = B("reset_buf", (n,), i64, fill=1)
+        self.progress_buf = B("progress_buf", (n,), i64)
+        self.randomize_buf = B("randomize_buf", (n,), i64)
+        self._terminate_buf = B("_terminate_buf", (n,), i64, fill=1)
+        self._sub_rewards = B("_sub_rewards", (n, 4))
         # the tensors gym.acquire_*_tensor would have returned (humanoid_smpl.py:66-113)
-        self._root_states = torch.zeros((n, 13), **f)
+        self._root_states = B("_root_states", (n, 13))
         self._humanoid_root_states = self._root_states
         # the actors' start pose (humanoid_smpl.py:348-353: char_h 0.89, identity rotation), velocities zeroed (:89-90): what
         # _reset_default restores
         self._root_states[:, 2] = 0.89
         self._root_states[:, 6] = 1.0
         self._initial_humanoid_root_states = self._root_states.clone()
-        self._dof_state = torch.zeros((n * self._num_dof, 2), **f)
+        self._dof_state = B("_dof_state", (n * self._num_dof, 2), rows_per_env=self._num_dof)
         ds = self._dof_state.view(n, self._num_dof, 2)
         self._dof_pos, self._dof_vel = ds[..., 0], ds[..., 1]
-        self._rigid_body_state = torch.zeros((n * self.num_bodies, 13), **f)
+        self._rigid_body_state = B("_rigid_body_state", (n * self.num_bodies, 13), rows_per_env=self.num_bodies)
         rb = self._rigid_body_state.view(n, self.num_bodies, 13)
         # bodies of the freshly created actors: the start pose with every joint at zero (a default-pose reset leaves the rigid-body
         # tensor as it is until the next simulate(), like gym.refresh_rigid_body_state_tensor does: at creation it holds this pose)
@@ -429,19 +461,19 @@ class HumanoidSMPLIM:
             rb[:, :, 6] = 1.0
         self._rigid_body_pos, self._rigid_body_rot = rb[..., 0:3], rb[..., 3:7]
         self._rigid_body_vel, self._rigid_body_ang_vel = rb[..., 7:10], rb[..., 10:13]
-        self._contact_forces = torch.zeros((n, self.num_bodies, 3), **f)
-        self.dof_force_tensor = torch.zeros((n, self._num_dof), **f)
-        self._pd_target = torch.zeros((n, self._num_dof), **f)
-        self._cur_ref_motion_times = torch.zeros(n, **f)
-        self._reset_ref_motion_times = torch.zeros(n, **f)
-        self._target_bufs = [torch.zeros((n, _lib.MOTION_STATE_DIM), **f) for _ in range(2)]
+        self._contact_forces = B("_contact_forces", (n, self.num_bodies, 3))
+        self.dof_force_tensor = B("dof_force_tensor", (n, self._num_dof))
+        self._pd_target = B("_pd_target", (n, self._num_dof))
+        self._cur_ref_motion_times = B("_cur_ref_motion_times", (n,))
+        self._reset_ref_motion_times = B("_reset_ref_motion_times", (n,))
+        self._target_bufs = [B("_target_bufs[%d]" % k, (n, _lib.MOTION_STATE_DIM)) for k in range(2)]
         w = self.context_length + 2 * self.context_padding
         xf = self._context_transform
-        self.context_feat = torch.zeros((n, w, _lib.CONTEXT_DIM if xf is None else _lib.CONTEXT_DIM_CONF), **f)
+        self.context_feat = B("context_feat", (n, w, _lib.CONTEXT_DIM if xf is None else _lib.CONTEXT_DIM_CONF))
         # the draws of the context transform's random ops, per (env, frame, body): u_noise, z.xyz, u_drop (refilled before every window)
         random_ops = xf is not None and any(xf.ops[k] != _lib.CTX_MASK_JOINTS for k in range(xf.num_ops))
-        self._context_draws = torch.zeros((n, w, self.num_bodies, 5), **f) if random_ops else None
-        self._context_mask_u8 = torch.zeros((n, w), dtype=torch.uint8, device=dev)
+        self._context_draws = B("_context_draws", (n, w, self.num_bodies, 5)) if random_ops else None
+        self._context_mask_u8 = B("_context_mask_u8", (n, w), torch.uint8)
         self._humanoid_actor_ids = torch.arange(n, device=dev, dtype=torch.int32)
         self._prev_dof_pos = None
 
@@ -797,7 +829,15 @@ class HumanoidSMPLIM:
     def check(self):
         """Synchronise (v2p_env_check: raises on a HIP error) and fetch the substep jobs' recovery counter."""
         _lib.check(self._lib.v2p_env_check(self._h_env, self._stream()), "v2p_env_check")
+        self._check_guard_rows()
         self._warn_job_recoveries()
+
+    def guard_counts(self):
+        """(engine arrays of this batch that lie between guard zones, float arrays among them that were poisoned at creation): (0, 0)
+        unless v2p_debug_guards was on when the batch was created."""
+        g, p = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.v2p_env_guard_counts(self._h_env, C.byref(g), C.byref(p)), "v2p_env_guard_counts")
+        return int(g.value), int(p.value)
 
     def kernel_build(self):
         """Which of the library's two builds of the physics kernel this batch runs (v2p_sim_cfg.kernel_build)."""
