@@ -106,33 +106,10 @@ def test_reset_of_a_subset_of_ids(v):
 
 @pytest.fixture(scope="module")
 def edge_inputs():
-    """seeded inputs of the tile-edge cases, shared: 257 rows of state, latents and residuals (a case takes the first N)"""
-    rng = np.random.default_rng(77)
-    _, avg, std = FX.weights()
-    n = 257
-    return dict(init=(avg + std * rng.normal(0, 0.8, (n, FX.FRAME))).astype(np.float32), xy=((rng.uniform(size=(n, 2)) - 0.5) * [2, 1.5] + [0, -13]).astype(np.float32),
-                z=np.clip(rng.normal(0, 1, (n, FX.LATENT)), -3, 3).astype(np.float32), res=rng.uniform(-2, 2, (n, 3)).astype(np.float32),
-                swing=rng.integers(-1, 4, n).astype(np.int64), bind=rng.uniform(-0.3, 0.3, (24, 3)).astype(np.float32))
+    return FX.edge_inputs()
 
 
-def _near_threshold(st, w, avg, std, s, z, res):
-    """envs of a seeded case whose branch floats come within 1e-3 of a threshold (their integers, and what hangs on them, may differ)"""
-    pr = {}
-    mvae.mvae_step_reference(st, w, avg, std, s, z, res, np.float64, pr)
-    thresholds = np.array([2.0, 2.5, 3.0, 3.1, 3.2, 3.3, 3.5])
-    return (np.abs(pr["phase"][:, None] - thresholds[None]).min(1) < 1e-3) | (np.abs(pr["atan2"]) < 1e-3) | (np.abs(pr["wrist_x"]) < 1e-3)
-
-
-def _well_conditioned(want32, want64, scatter):
-    """Seeded rows are not kept away from ill-conditioned rotations (a rot6d whose two vectors are nearly parallel, an angle next to pi)
-    as the fixture's rows are.  A row is judged when the numpy statement itself, evaluated in float32 and in float64, agrees on it within
-    2 x the recorded scatter: that leaves 6 of the 8 x scatter of the allowance to the kernel.  Decided without looking at the kernel."""
-    n = len(want32["root_pos"])
-    ok = np.ones(n, bool)
-    for k, x in want32.items():
-        if x.dtype.kind == "f" and k in scatter:
-            ok &= np.abs(x.astype(np.float64) - want64[k]).reshape(n, -1).max(1) <= 2 * scatter[k]
-    return ok
+_near_threshold, _well_conditioned = FX.near_threshold, FX.well_conditioned
 
 
 @gpu
