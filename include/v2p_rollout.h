@@ -682,6 +682,90 @@ int v2p_tennis_dual_step(const v2p_tennis_cfg* cfg, const v2p_tennis_dual_cfg* d
 int v2p_tennis_dual_handover(const v2p_tennis_cfg* cfg, const v2p_tennis_dual_cfg* dual, int64_t n, const v2p_tennis_buffers* buffers,
                              const v2p_tennis_dual_buffers* dual_buffers, void* stream);
 
+/* ---- the action part of the controller's pre_physics_step (physics_mvae_controller.py:247-266) with `random_walk_in_recovery`
+ * (:252-257) in one launch, without a host synchronisation or an allocation.  A policy action row is 32 latent columns, then
+ * num_res_dof residual-DoF columns, then num_res_root residual-root columns; columns behind them are not read.
+ * The random numbers are Philox4x32-10 under key (seed) and counter (env, block | stream << 28, call) with the laws of csrc/philox.hpp
+ * (numpy: vid2player3d_amd/device_rng.py): env i draws its 32 normals from blocks 0..7 of the WALK stream, normal 4b+2p+q is element q of
+ * the Box-Muller pair of words 2p, 2p+1 of block b.  A draw depends on (seed, call, env) alone - the reference deals draw k of a call to
+ * the k-th env in recovery instead; both are iid.  The caller counts `call` on the host. */
+typedef struct {
+    int32_t num_res_dof;            /* columns 32 .. 32+num_res_dof-1 (add_residual_dof: 3), >= 0 */
+    int32_t num_res_root;           /* the columns behind them (add_residual_root: 3), >= 0 */
+    int32_t random_walk;            /* 0 / 1: random_walk_in_recovery */
+    float vae_action_scale, residual_dof_scale, residual_root_scale;
+    float clamp;                    /* 5.0: the drawn latent is clamped to [-clamp, clamp]; >= 0 */
+    uint64_t seed, call;
+} v2p_controller_actions_cfg;
+typedef struct {                    /* DEVICE buffers */
+    const float* actions;           /* [N, actions_stride] read only */
+    int64_t actions_stride;         /* floats from one row to the next, >= 32 + num_res_dof + num_res_root */
+    const int64_t* tar_action;      /* [N] read only; required with random_walk: 0 = the env is in recovery */
+    const uint32_t* words;          /* [N,32] nullable: stands in for the generator's output words (word 4b+j = word j of block b) */
+    float* actions_out;             /* [N, 32+num_res_dof+num_res_root] `_actions`: the copy */
+    float* mvae_actions;            /* [N,32] `_mvae_actions`: actions[:, :32] * vae_action_scale; in recovery under random_walk the
+                                     * clamped draws */
+    float* res_dof_actions;         /* [N,num_res_dof] `_res_dof_actions` (nullable when num_res_dof = 0) */
+    float* res_root_actions;        /* [N,num_res_root] `_res_root_actions` (nullable when num_res_root = 0) */
+} v2p_controller_actions_buffers;
+/* Refused before any HIP call (V2P_ERR_INVALID, a message that names the call): null cfg / buffers, n < 0 or above 2^31-1, a negative
+ * column count, a stride below the row's width, a clamp that is negative or NaN, a null required pointer.  n = 0 is a no-op. */
+int v2p_controller_actions(const v2p_controller_actions_cfg* cfg, int64_t n, const v2p_controller_actions_buffers* buffers, void* stream);
+
+/* ---- the flag-driven half of the single-player `_reset_envs` (physics_mvae_controller.py:167-242 with `_reset_balls`,
+ * humanoid_smpl_im_mvae.py:503-524, and TennisBallGeneratorOffline.generate, utils/tennis_ball.py:422-456) for all n envs in ONE launch,
+ * without an id list, a host synchronisation or an allocation; one wavefront per env.  rx = reset_reaction[e], rc = reset_recovery[e],
+ * both as they stand at entry; the flags are read, not cleared.  In the reference's order:
+ *   rx: the pool row - random rule: integer(word 0, 0, rows), and for a ball with y > 0
+ *       clamp(long((x + 4) / 8 * rows) + integer(word 1, -1000, 1000), 0, rows - 1), the float part in float32; round-robin rule:
+ *       sample_idx[e], post-incremented modulo rows -; ball_state = (pos, (0,0,0,1), vel, vspin 2 pi normalize(vel x (0,0,-1)));
+ *       has_bounce, bounce_pos, has_racket_contact cleared; ball_traj row = the pool row's frames, zeros past them; traj_cursor = 0;
+ *       prev_ball_vy = the launch vy
+ *   rc: tar_action = 0, has_bounce and bounce_pos cleared
+ *   rx: the history fill (use_history_ball_obs), tar_time = 0, tar_action = 1, num_reset_reaction += 1, bounce_in and est_* cleared,
+ *       swing_type_cycle = -1, tar_time_total = reset_reaction_nframes + integer(word 2, -5, 5); target_bounce_pos: discrete mode from
+ *       u = uniform(word 3): u < 0.33 -> (-3, 10, 0), u > 0.67 -> (3, 10, 0), else (0, 10, 0); continuous mode
+ *       uniform(words 4..6) * (target_max - target_min) + target_min, ONE draw for all envs of the call
+ *   rx | rc: the observation row of v2p_tennis_task_obs (history roll, racket_pos, racket_normal included)
+ * Envs without a flag keep every bit.  The words are block 0 of the RESET stream of csrc/philox.hpp under (seed, call, env), words 4..6
+ * those of env 0xffffffff (the whole call); `words` [N,8], when given, stands in for them.  A draw depends on (seed, call, env) alone -
+ * the reference draws for the flagged envs in order of env id; both are iid.
+ * What the launch writes of buffers that v2p_tennis_buffers declares read-only comes again, writable, in v2p_tennis_reset_buffers (the
+ * same memory).  Of v2p_tennis_buffers it reads rb_state, root_states, racket_state, wrist_link, reset_reaction, reset_recovery and
+ * writes tar_time, prev_ball_vy, traj_cursor, ball_obs, bounce_in, est_*, racket_pos, racket_normal, obs. */
+enum { V2P_TENNIS_TARGET_OFF = 0, V2P_TENNIS_TARGET_DISCRETE = 1, V2P_TENNIS_TARGET_CONTINUOUS = 2 };
+enum { V2P_TENNIS_POOL_RANDOM = 0, V2P_TENNIS_POOL_ROUND_ROBIN = 1 };
+typedef struct {
+    int64_t reset_reaction_nframes; /* cfg_v2p reset_reaction_nframes */
+    int32_t target_mode;            /* V2P_TENNIS_TARGET_* (cfg_v2p use_random_ball_target: False / True / 'continuous') */
+    int32_t pool_rule;              /* V2P_TENNIS_POOL_* (TennisBallGeneratorOffline.sample_random: True / False) */
+    float target_min[3], target_max[3]; /* (-3, 9, 0), (3, 11, 0) (:84-85) */
+    int64_t pool_rows;              /* >= 1 */
+    int32_t pool_frames;            /* frames of a pool row's trajectory, 1..100 */
+    int64_t pool_stride;            /* floats from one pool row to the next, >= 7 + 3 pool_frames */
+    uint64_t seed, call;
+} v2p_tennis_reset_cfg;
+typedef struct {                    /* DEVICE buffers */
+    const float* pool;              /* [rows, pool_stride]: launch pos3, vel3, vspin1, then pool_frames x 3 positions; read only */
+    int64_t* sample_idx;            /* [N] the round-robin rule's next row per env (nullable under the random rule) */
+    float* ball_state;              /* [N,13] */
+    uint8_t* has_bounce;            /* [N] */
+    float* bounce_pos;              /* [N,3] */
+    uint8_t* has_racket_contact;    /* [N] */
+    float* ball_traj;               /* [N,100,3] */
+    int64_t* tar_time_total;        /* [N] */
+    int64_t* tar_action;            /* [N] */
+    float* target_bounce_pos;       /* [N,3] (nullable with V2P_TENNIS_TARGET_OFF) */
+    int64_t* num_reset_reaction;    /* [N] */
+    int64_t* swing_type_cycle;      /* [N] */
+    const uint32_t* words;          /* [N,8] nullable: stands in for the generator's output words */
+} v2p_tennis_reset_buffers;
+/* Refused before any HIP call (V2P_ERR_INVALID, a message that names the call): null cfg / reset cfg / buffers / reset buffers, n < 0
+ * or above 2^31-1, L outside 1..100, pool_rows < 1, pool_frames outside 1..100, a stride below 7 + 3 pool_frames, an unknown target
+ * mode or pool rule, a null required pointer.  n = 0 is a no-op. */
+int v2p_tennis_task_reset(const v2p_tennis_cfg* cfg, const v2p_tennis_reset_cfg* reset_cfg, int64_t n, const v2p_tennis_buffers* buffers,
+                          const v2p_tennis_reset_buffers* reset_buffers, void* stream);
+
 /* ---- the MotionVAE motion generator of a control step (vid2player/players/mvae_player.py `MVAEPlayer.step` / `reset` around
  * motion_vae/model.py:186-252 `MixedDecoder.forward`): the gate, the three expert-blended layers and the player's state update
  * (`_update_mvae_state`) in ONE launch, without a host synchronisation or an allocation.  The decoder computes every expert and blends

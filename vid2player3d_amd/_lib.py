@@ -122,6 +122,33 @@ class TennisDualBuffers(C.Structure):
     _fields_ = [(k, vp) for k in TENNIS_DUAL_BUFFER_NAMES]
 
 
+class TennisResetCfg(C.Structure):
+    """v2p_tennis_reset_cfg: what the flag-driven task reset (v2p_tennis_task_reset) needs on top of v2p_tennis_cfg."""
+    _fields_ = [("reset_reaction_nframes", C.c_int64), ("target_mode", C.c_int32), ("pool_rule", C.c_int32), ("target_min", C.c_float * 3), ("target_max", C.c_float * 3),
+                ("pool_rows", C.c_int64), ("pool_frames", C.c_int32), ("pool_stride", C.c_int64), ("seed", C.c_uint64), ("call", C.c_uint64)]
+
+
+TENNIS_RESET_BUFFER_NAMES = ("pool", "sample_idx", "ball_state", "has_bounce", "bounce_pos", "has_racket_contact", "ball_traj", "tar_time_total", "tar_action",
+                             "target_bounce_pos", "num_reset_reaction", "swing_type_cycle", "words")
+TENNIS_TARGET_MODES = {False: 0, True: 1, "continuous": 2}  # V2P_TENNIS_TARGET_*
+TENNIS_POOL_RULES = {"random": 0, "round_robin": 1}  # V2P_TENNIS_POOL_*
+
+
+class TennisResetBuffers(C.Structure):
+    _fields_ = [(k, vp) for k in TENNIS_RESET_BUFFER_NAMES]
+
+
+class ControllerActionsCfg(C.Structure):
+    """v2p_controller_actions_cfg: the action part of the controller's pre_physics_step (v2p_controller_actions)."""
+    _fields_ = [("num_res_dof", C.c_int32), ("num_res_root", C.c_int32), ("random_walk", C.c_int32), ("vae_action_scale", C.c_float),
+                ("residual_dof_scale", C.c_float), ("residual_root_scale", C.c_float), ("clamp", C.c_float), ("seed", C.c_uint64), ("call", C.c_uint64)]
+
+
+class ControllerActionsBuffers(C.Structure):
+    _fields_ = [("actions", vp), ("actions_stride", C.c_int64), ("tar_action", vp), ("words", vp), ("actions_out", vp), ("mvae_actions", vp),
+                ("res_dof_actions", vp), ("res_root_actions", vp)]
+
+
 class MvaeCfg(C.Structure):
     """v2p_mvae_cfg: sizes and switches of the MotionVAE motion generator (v2p_mvae_step / _reset)."""
     _fields_ = [(k, C.c_int32) for k in ("frame_size", "latent_size", "hidden_size", "num_experts", "gate_hidden_size", "num_condition_frames", "num_future_predictions",
@@ -234,6 +261,8 @@ def load():
         "v2p_tennis_task_obs": [C.POINTER(TennisCfg), C.c_int64, C.POINTER(TennisBuffers), vp, C.c_int64, vp],
         "v2p_tennis_dual_step": [C.POINTER(TennisCfg), C.POINTER(TennisDualCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(C.c_char_p), vp],
         "v2p_tennis_dual_handover": [C.POINTER(TennisCfg), C.POINTER(TennisDualCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(TennisDualBuffers), vp],
+        "v2p_tennis_task_reset": [C.POINTER(TennisCfg), C.POINTER(TennisResetCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(TennisResetBuffers), vp],
+        "v2p_controller_actions": [C.POINTER(ControllerActionsCfg), C.c_int64, C.POINTER(ControllerActionsBuffers), vp],
         "v2p_mvae_step": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, vp, vp],
         "v2p_mvae_reset": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, C.c_int64, vp, vp, vp, vp],
         "v2p_mvae_dual_step": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, vp, C.c_int32, vp],
@@ -263,7 +292,7 @@ def load():
 EXPORTED_SYMBOLS = (
     "v2p_model_create", "v2p_model_destroy", "v2p_mlib_create", "v2p_mlib_destroy", "v2p_motion_state", "v2p_reward", "v2p_reset_flags",
     "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_obs_imitation_packed_w", "v2p_policy_head_w", "v2p_policy_head_record_w", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_set_context_transform", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
-    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_tennis_dual_step", "v2p_tennis_dual_handover", "v2p_mvae_step", "v2p_mvae_reset", "v2p_mvae_dual_step", "v2p_mvae_dual_reset", "v2p_mvae_target_step", "v2p_mvae_target_reset", "v2p_mvae_target_actions", "v2p_last_error", "v2p_abi_version",
+    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_tennis_dual_step", "v2p_tennis_dual_handover", "v2p_controller_actions", "v2p_tennis_task_reset", "v2p_mvae_step", "v2p_mvae_reset", "v2p_mvae_dual_step", "v2p_mvae_dual_reset", "v2p_mvae_target_step", "v2p_mvae_target_reset", "v2p_mvae_target_actions", "v2p_last_error", "v2p_abi_version",
     "v2p_debug_guards", "v2p_debug_guards_selftest", "v2p_env_guard_counts",
 )
 

@@ -256,6 +256,7 @@ class TennisBallGeneratorOffline:
     def __init__(self, traj_file, sample_random=False, num_envs=None, device="cpu", seed=None):
         data = torch.from_numpy(np.load(traj_file) if isinstance(traj_file, str) else np.asarray(traj_file)).to(device=device, dtype=torch.float32)
         self.device = data.device
+        self.data = data  # [rows, 7 + 3 frames]: what the controller's device reset reads rows of
         self.launch_pos, self.launch_vel, self.launch_vspin = data[:, 0:3], data[:, 3:6], data[:, 6]
         self.traj_pool = data[:, 7:].reshape(len(data), -1, 3)
         self.sample_random = sample_random

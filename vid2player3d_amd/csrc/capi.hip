@@ -7,8 +7,10 @@
 
 #include <new>
 
+#include "controller_actions.hpp"
 #include "mvae_player.hpp"
 #include "mvae_target.hpp"
+#include "tennis_reset.hpp"
 #include "tennis_task.hpp"
 #include "v2p_internal.hpp"
 
@@ -350,6 +352,53 @@ int v2p_tennis_dual_handover(const v2p_tennis_cfg* c, const v2p_tennis_dual_cfg*
     ok = ok && (c->use_history_ball_obs || db->ball_traj) && (!c->use_random_ball_target || db->target_bounce_pos);
     if (!ok) { set_error("%s: null dual buffer", fn); return V2P_ERR_INVALID; }
     return launch_tennis_dual_handover(*c, *dc, n, *b, *db, (hipStream_t)stream);
+}
+
+int v2p_controller_actions(const v2p_controller_actions_cfg* c, int64_t n, const v2p_controller_actions_buffers* b, void* stream) {
+    const char* fn = "v2p_controller_actions";
+    if (!c || !b) { set_error("%s: null cfg / buffers", fn); return V2P_ERR_INVALID; }
+    if (n < 0 || n > INT32_MAX) { set_error("%s: n %lld outside 0..2^31-1", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (c->num_res_dof < 0 || c->num_res_root < 0 || c->num_res_dof > 1024 || c->num_res_root > 1024) {
+        set_error("%s: num_res_dof %d / num_res_root %d outside 0..1024", fn, c->num_res_dof, c->num_res_root);
+        return V2P_ERR_INVALID;
+    }
+    const int64_t width = V2P_MVAE_LATENT + c->num_res_dof + c->num_res_root;
+    if (b->actions_stride < width) { set_error("%s: actions_stride %lld below the %lld columns of a row", fn, (long long)b->actions_stride, (long long)width); return V2P_ERR_INVALID; }
+    if (!(c->clamp >= 0.f)) { set_error("%s: clamp %g is negative or NaN", fn, (double)c->clamp); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    bool ok = b->actions && b->actions_out && b->mvae_actions && (!c->random_walk || b->tar_action);
+    ok = ok && (c->num_res_dof == 0 || b->res_dof_actions) && (c->num_res_root == 0 || b->res_root_actions);
+    if (!ok) { set_error("%s: null buffer", fn); return V2P_ERR_INVALID; }
+    return launch_controller_actions(*c, n, *b, (hipStream_t)stream);
+}
+
+int v2p_tennis_task_reset(const v2p_tennis_cfg* c, const v2p_tennis_reset_cfg* rc, int64_t n, const v2p_tennis_buffers* b, const v2p_tennis_reset_buffers* r, void* stream) {
+    const char* fn = "v2p_tennis_task_reset";
+    if (!c || !rc || !b || !r) { set_error("%s: null cfg / reset cfg / buffers / reset buffers", fn); return V2P_ERR_INVALID; }
+    if (n < 0 || n > INT32_MAX) { set_error("%s: n %lld outside 0..2^31-1", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (c->obs_ball_traj_length < 1 || c->obs_ball_traj_length > V2P_TENNIS_TRAJ_FRAMES) {
+        set_error("%s: obs_ball_traj_length %d outside 1..%d", fn, c->obs_ball_traj_length, V2P_TENNIS_TRAJ_FRAMES);
+        return V2P_ERR_INVALID;
+    }
+    if (rc->pool_rows < 1 || rc->pool_rows > INT32_MAX) { set_error("%s: the pool has %lld rows (1..2^31-1)", fn, (long long)rc->pool_rows); return V2P_ERR_INVALID; }
+    if (rc->pool_frames < 1 || rc->pool_frames > V2P_TENNIS_TRAJ_FRAMES) { set_error("%s: pool_frames %d outside 1..%d", fn, rc->pool_frames, V2P_TENNIS_TRAJ_FRAMES); return V2P_ERR_INVALID; }
+    if (rc->pool_stride < 7 + 3 * (int64_t)rc->pool_frames) { set_error("%s: pool_stride %lld below 7 + 3 x %d frames", fn, (long long)rc->pool_stride, rc->pool_frames); return V2P_ERR_INVALID; }
+    if (rc->target_mode < V2P_TENNIS_TARGET_OFF || rc->target_mode > V2P_TENNIS_TARGET_CONTINUOUS) { set_error("%s: unknown target mode %d", fn, rc->target_mode); return V2P_ERR_INVALID; }
+    if (rc->pool_rule != V2P_TENNIS_POOL_RANDOM && rc->pool_rule != V2P_TENNIS_POOL_ROUND_ROBIN) { set_error("%s: unknown pool rule %d", fn, rc->pool_rule); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    bool ok = b->rb_state && b->root_states && b->racket_state && b->wrist_link && b->reset_reaction && b->reset_recovery && b->tar_time && b->prev_ball_vy && b->traj_cursor;
+    ok = ok && b->bounce_in && b->est_bounce_pos && b->est_bounce_time && b->est_max_height && b->est_bounce_in && b->racket_pos && b->racket_normal && b->obs;
+    ok = ok && (!c->use_history_ball_obs || b->ball_obs) && (c->use_history_ball_obs || b->ball_traj) && (!c->use_random_ball_target || b->target_bounce_pos);
+    if (!ok) { set_error("%s: null buffer", fn); return V2P_ERR_INVALID; }
+    ok = r->pool && r->ball_state && r->has_bounce && r->bounce_pos && r->has_racket_contact && r->ball_traj && r->tar_time_total && r->tar_action && r->num_reset_reaction;
+    ok = ok && r->swing_type_cycle && (rc->pool_rule != V2P_TENNIS_POOL_ROUND_ROBIN || r->sample_idx) && (rc->target_mode == V2P_TENNIS_TARGET_OFF || r->target_bounce_pos);
+    if (!ok) { set_error("%s: null reset buffer", fn); return V2P_ERR_INVALID; }
+    // the observation reads the window and the target through v2p_tennis_buffers: they must be the memory this launch writes
+    if ((!c->use_history_ball_obs && b->ball_traj != r->ball_traj) || (c->use_random_ball_target && rc->target_mode != V2P_TENNIS_TARGET_OFF && b->target_bounce_pos != r->target_bounce_pos)) {
+        set_error("%s: ball_traj / target_bounce_pos of the two buffer structs are not the same memory", fn);
+        return V2P_ERR_INVALID;
+    }
+    return launch_tennis_task_reset(*c, *rc, n, *b, *r, (hipStream_t)stream);
 }
 
 // what both motion-generator entry points refuse; `step`: the decoder's weights are required too

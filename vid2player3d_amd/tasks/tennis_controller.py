@@ -17,7 +17,21 @@ What turns the generator's kinematic pose into the imitation target of the low-l
 `attach_imitation_target(target)`, `pre_physics_step` ends with `post_mvae_step()`, the reset puts the humanoid into the generator's
 pose, and `physics_step(ll_actions)` steps the wrapped task on the PD targets of the low-level policy's actions: `pre_physics_step` ->
 `physics_step` -> `post_physics_step` is vid2player's control step.  Without one, every path is as before.  The dual controller is
-`tasks.tennis_controller_dual.DualTennisControllerTask`.  Not built: `random_walk_in_recovery`, `optimize_two_hand_backhand`, `update_mvae_from_sim`, the low-level policy network itself.
+`tasks.tennis_controller_dual.DualTennisControllerTask`.  Not built: `optimize_two_hand_backhand`, `update_mvae_from_sim`, the low-level policy network itself.
+
+With cfg v2p `random_walk_in_recovery` (every shipped controller config sets it) the action part of `pre_physics_step` is ONE launch,
+`v2p_controller_actions` (csrc/controller_actions.hip): the copy of the actions, the scaled latent and residual columns, and the latent
+of envs in recovery (`_tar_action == 0`) replaced by clamp(N(0,1), -5, 5) (:252-257).  The normals come from the counter-based generator
+of csrc/philox.hpp under the controller's `seed` and a call counter kept on the host; `controller_actions_reference` with
+`device_rng.philox_words` states them in numpy.  A departure from the reference: it deals draw k of a step to the k-th env in recovery
+(a host read sizes the slice), here env i owns its draws whatever the other envs do.  Both are iid draws.  Without the key the
+torch lines run as before.
+
+With cfg v2p `task_reset: 'device'` the flag-driven half of `_reset_envs` - ball draw from the offline pool, `_reset_recovery_tasks`,
+`_reset_reaction_tasks`, the observation of the flagged envs - is ONE launch over all envs, `v2p_tennis_task_reset`
+(csrc/tennis_reset.hip), without a `nonzero()` or any other host read; `task_reset_reference` states it in numpy.  Its draws come from
+the same generator (stream RESET), with the same departure.  The default `'torch'` is the indexed torch code with torch's own random
+stream, as before.  `'device'` needs the task's ball generator to be a `TennisBallGeneratorOffline` on the task's device.
 
 `task_step_reference` is a numpy statement of the same step on arrays - the checker of the tests, as `ball_traj.resample_reference`
 and `body_shapes` have theirs; the product never calls it.  There is no CPU path: a CPU device or a missing library is a RuntimeError.
@@ -283,6 +297,178 @@ def task_step_reference(st, s):
     return o
 
 
+# ------------------------------------------------------------------------------------------------------------------ the actions
+def action_settings(num_res_dof=0, num_res_root=0, vae_action_scale=1.0, residual_dof_scale=0.1, residual_root_scale=0.02, random_walk=True, clamp=5.0, seed=0):
+    """The settings of `v2p_controller_actions` as a plain dict (defaults: the reference's, physics_mvae_controller.py:249-266)."""
+    if num_res_dof < 0 or num_res_root < 0:
+        raise ValueError("action_settings: negative column counts")
+    return dict(num_res_dof=int(num_res_dof), num_res_root=int(num_res_root), vae_action_scale=float(vae_action_scale), residual_dof_scale=float(residual_dof_scale),
+                residual_root_scale=float(residual_root_scale), random_walk=bool(random_walk), clamp=float(clamp), seed=int(seed) & (2 ** 64 - 1))
+
+
+def action_width(st):
+    return LATENT + st["num_res_dof"] + st["num_res_root"]
+
+
+def action_outputs(st, n, **kw):
+    """The four output tensors of `v2p_controller_actions` for n envs (rows of zero width are kept as empty tensors)."""
+    return dict(actions_out=torch.zeros((n, action_width(st)), **kw), mvae_actions=torch.zeros((n, LATENT), **kw),
+                res_dof_actions=torch.zeros((n, st["num_res_dof"]), **kw), res_root_actions=torch.zeros((n, st["num_res_root"]), **kw))
+
+
+def launch_actions(st, n, actions, tar_action, out, call=0, words=None):
+    """v2p_controller_actions on device tensors: `actions` [>= n, W] float32 with unit column stride (rows may be strided), `tar_action`
+    [n] int64, `out` the dict of action_outputs; `words` [n,32] int32 / uint32 bits stands in for the generator's words."""
+    lib = _lib.load()
+    dev = out["mvae_actions"].device
+    for k, t in list(out.items()) + [("tar_action", tar_action), ("words", words)]:
+        if t is not None and (not t.is_cuda or not t.is_contiguous() or t.device != dev):
+            raise RuntimeError("controller actions: buffer %s must be a contiguous tensor on %s (there is no CPU path)" % (k, dev))
+    if not actions.is_cuda or actions.device != dev or actions.dtype != torch.float32 or actions.dim() != 2 or actions.stride(1) != 1:
+        raise RuntimeError("controller actions: actions must be float32 rows on %s with unit column stride (there is no CPU path)" % (dev,))
+    c = _lib.ControllerActionsCfg(num_res_dof=st["num_res_dof"], num_res_root=st["num_res_root"], random_walk=int(st["random_walk"]),
+                                  vae_action_scale=st["vae_action_scale"], residual_dof_scale=st["residual_dof_scale"], residual_root_scale=st["residual_root_scale"],
+                                  clamp=st["clamp"], seed=st["seed"], call=int(call) & (2 ** 64 - 1))
+    nul = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    b = _lib.ControllerActionsBuffers(actions=nul(actions), actions_stride=int(actions.stride(0)) if actions.shape[0] > 1 else int(actions.shape[1]),
+                                      tar_action=nul(tar_action), words=nul(words), actions_out=nul(out["actions_out"]), mvae_actions=nul(out["mvae_actions"]),
+                                      res_dof_actions=nul(out["res_dof_actions"]), res_root_actions=nul(out["res_root_actions"]))
+    with torch.cuda.device(dev):
+        _lib.check(lib.v2p_controller_actions(C.byref(c), int(n), C.byref(b), _lib.current_stream(dev)), "v2p_controller_actions")
+
+
+def controller_actions_reference(st, actions, tar_action, words, dt=np.float32):
+    """The action part of pre_physics_step (:247-266) on arrays: `actions` [n, >= width], `tar_action` [n], `words` [n,32] uint32 (the
+    generator's: `device_rng.philox_words(seed, call, STREAM_WALK, n, 8)`).  dt float64 is the same law in double (the scatter of the
+    normals).  Returns the four arrays `v2p_controller_actions` writes."""
+    from .. import device_rng
+
+    a = np.asarray(actions, dtype=np.float32)
+    nr, nroot = st["num_res_dof"], st["num_res_root"]
+    z = a[:, :LATENT].astype(dt) * dt(st["vae_action_scale"])
+    if st["random_walk"]:
+        walk = np.asarray(tar_action) == 0
+        z[walk] = device_rng.clamped_normals(np.asarray(words, dtype=np.uint32)[walk], st["clamp"], dt)
+    return dict(actions_out=a[:, :LATENT + nr + nroot].copy(), mvae_actions=z, res_dof_actions=a[:, LATENT:LATENT + nr].astype(dt) * dt(st["residual_dof_scale"]),
+                res_root_actions=a[:, LATENT + nr:LATENT + nr + nroot].astype(dt) * dt(st["residual_root_scale"]))
+
+
+# ------------------------------------------------------------------------------------------------------------------ the task reset
+RESET_WRITES = ("ball_state", "has_bounce", "bounce_pos", "has_racket_contact", "ball_traj", "traj_cursor", "prev_ball_vy", "tar_action", "tar_time", "tar_time_total",
+                "num_reset_reaction", "bounce_in", "est_bounce_pos", "est_bounce_time", "est_bounce_in", "est_max_height", "swing_type_cycle", "target_bounce_pos",
+                "ball_obs", "sample_idx", "obs", "racket_pos", "racket_normal")  # what v2p_tennis_task_reset may write
+RESET_WORDS = 8  # words of an env per call: pool row, near offset, reaction-time offset, target uniform, the whole call's three target uniforms, one spare
+
+
+def reset_settings(reset_reaction_nframes, use_random_ball_target=False, sample_random=True, target_min=(-3.0, 9.0, 0.0), target_max=(3.0, 11.0, 0.0), seed=0):
+    """The settings of `v2p_tennis_task_reset` on top of task_settings(...), as a plain dict (target bounds: :84-85)."""
+    mode = use_random_ball_target if use_random_ball_target == "continuous" else bool(use_random_ball_target)
+    return dict(reset_reaction_nframes=int(reset_reaction_nframes), target_mode=mode, pool_rule="random" if sample_random else "round_robin",
+                target_min=tuple(float(x) for x in target_min), target_max=tuple(float(x) for x in target_max), seed=int(seed) & (2 ** 64 - 1))
+
+
+def launch_reset(st, tensors, n, pool, num_reset_reaction, sample_idx=None, call=0, words=None):
+    """v2p_tennis_task_reset on a dict of device tensors named like v2p_tennis_buffers; `st`: task_settings merged with reset_settings;
+    `pool` [rows, 7 + 3 frames] float32, `num_reset_reaction` [n] int64, `sample_idx` [n] int64 (round robin), `words` [n,8] int32 bits."""
+    lib = _lib.load()
+    tx, ty = tensors.get("traj_out_x"), tensors.get("traj_out_y")
+    c = cfg_struct(st, (1, 1) if tx is None else tx.shape, (1, 1, 2) if ty is None else ty.shape)
+    b = buffers_struct(tensors)
+    dev = tensors["obs"].device
+    extra = dict(pool=pool, num_reset_reaction=num_reset_reaction, sample_idx=sample_idx, words=words)
+    for k, t in extra.items():
+        if t is not None and (not t.is_cuda or not t.is_contiguous() or t.device != dev):
+            raise RuntimeError("tennis task reset: buffer %s must be a contiguous tensor on %s (there is no CPU path)" % (k, dev))
+    if pool.dim() != 2 or pool.dtype != torch.float32 or (pool.shape[1] - 7) % 3:
+        raise ValueError("tennis task reset: the pool must be float32 [rows, 7 + 3 frames]")
+    rc = _lib.TennisResetCfg(reset_reaction_nframes=st["reset_reaction_nframes"], target_mode=_lib.TENNIS_TARGET_MODES[st["target_mode"]],
+                             pool_rule=_lib.TENNIS_POOL_RULES[st["pool_rule"]], pool_rows=int(pool.shape[0]), pool_frames=min((int(pool.shape[1]) - 7) // 3, TRAJ_FRAMES),
+                             pool_stride=int(pool.shape[1]), seed=st["seed"], call=int(call) & (2 ** 64 - 1))
+    rc.target_min[:] = st["target_min"]
+    rc.target_max[:] = st["target_max"]
+    shared = {k: tensors.get(k) for k in _lib.TENNIS_RESET_BUFFER_NAMES if k not in extra}
+    r = _lib.TennisResetBuffers(**{k: t.data_ptr() for k, t in dict(shared, **extra).items() if t is not None})
+    with torch.cuda.device(dev):
+        _lib.check(lib.v2p_tennis_task_reset(C.byref(c), C.byref(rc), int(n), C.byref(b), C.byref(r), _lib.current_stream(dev)), "v2p_tennis_task_reset")
+
+
+def task_reset_reference(st, s, words):
+    """The flag-driven half of `_reset_envs` (:167-242 with `_reset_balls` and `TennisBallGeneratorOffline.generate`) on arrays, numpy
+    float32.  `st`: task_settings merged with reset_settings; `s`: arrays named like v2p_tennis_buffers plus `pool` [rows, 7 + 3 F],
+    `num_reset_reaction` and, for the round robin, `sample_idx`; `words` [n,8] uint32: `device_rng.philox_words(seed, call, STREAM_RESET,
+    n, 1)` in columns 0..3 and, for the continuous target, the whole call's block in columns 4..7 of every row.  Returns every array the
+    launch may write (RESET_WRITES) and `pool_rows`, the row each reacting env drew (-1 elsewhere).  Nothing in `s` is modified."""
+    from .. import device_rng as R
+
+    n = len(s["ball_state"])
+    A = lambda k, dt=None: np.array(s[k], dtype=dt)
+    w = np.asarray(words, dtype=np.uint32).reshape(n, RESET_WORDS)
+    rx, rc = A("reset_reaction").astype(bool), A("reset_recovery").astype(bool)
+    pool = np.asarray(s["pool"], dtype=_f)
+    rows, frames = len(pool), min((pool.shape[1] - 7) // 3, TRAJ_FRAMES)
+    L = st["L"]
+    o = dict(ball_state=A("ball_state", _f), has_bounce=A("has_bounce").astype(bool), bounce_pos=A("bounce_pos", _f), has_racket_contact=A("has_racket_contact").astype(bool),
+             ball_traj=A("ball_traj", _f).reshape(n, TRAJ_FRAMES, 3), traj_cursor=A("traj_cursor", np.int32), prev_ball_vy=A("prev_ball_vy", _f),
+             tar_action=A("tar_action", np.int64), tar_time=A("tar_time", np.int64), tar_time_total=A("tar_time_total", np.int64),
+             num_reset_reaction=A("num_reset_reaction", np.int64), bounce_in=A("bounce_in").astype(bool), est_bounce_pos=A("est_bounce_pos", _f),
+             est_bounce_time=A("est_bounce_time", _f), est_bounce_in=A("est_bounce_in").astype(bool), est_max_height=A("est_max_height", _f),
+             swing_type_cycle=A("swing_type_cycle", np.int64), target_bounce_pos=A("target_bounce_pos", _f), obs=A("obs", _f), racket_pos=A("racket_pos", _f),
+             racket_normal=A("racket_normal", _f))
+    if s.get("ball_obs") is not None:
+        o["ball_obs"] = A("ball_obs", _f).reshape(n, L, 3)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        # ---- TennisBallGeneratorOffline.indices
+        if st["pool_rule"] == "round_robin":
+            o["sample_idx"] = A("sample_idx", np.int64)
+            idx = np.clip(o["sample_idx"], 0, rows - 1)
+            o["sample_idx"][rx] = (idx[rx] + 1) % rows
+        else:
+            idx = R.integer(w[:, 0], 0, rows)
+            x, y = o["ball_state"][:, 0], o["ball_state"][:, 1]
+            nf = (x + _f(4)) / _f(8) * _f(rows)
+            base = np.where((nf >= _f(-1e15)) & (nf <= _f(1e15)), nf, _f(-1e15)).astype(np.int64)  # (trunc toward zero, as .long())
+            idx = np.where(y > 0, np.clip(base + R.integer(w[:, 1], -1000, 1000), 0, rows - 1), idx)
+        # ---- reset_balls and the trajectory row
+        row = pool[idx]
+        vel, vspin = row[:, 3:6], row[:, 6]
+        cr = np.stack([vel[:, 1] * _f(-1) - vel[:, 2] * _f(0), vel[:, 2] * _f(0) - vel[:, 0] * _f(-1), vel[:, 0] * _f(0) - vel[:, 1] * _f(0)], -1)
+        nrm = np.maximum(np.sqrt(cr[:, 0] * cr[:, 0] + cr[:, 1] * cr[:, 1] + cr[:, 2] * cr[:, 2]), _f(1e-12))
+        mag = vspin * _f(math.pi) * _f(2)
+        state = np.concatenate([row[:, 0:3], np.tile(np.array([0, 0, 0, 1], _f), (n, 1)), vel, mag[:, None] * (cr / nrm[:, None])], 1).astype(_f)
+        o["ball_state"][rx] = state[rx]
+        o["has_bounce"][rx], o["bounce_pos"][rx], o["has_racket_contact"][rx] = False, 0, False
+        o["ball_traj"][rx] = 0
+        o["ball_traj"][rx, :frames] = row[rx, 7:7 + 3 * frames].reshape(-1, frames, 3)
+        o["traj_cursor"][rx] = 0
+        o["prev_ball_vy"][rx] = state[rx, 8]
+        # ---- _reset_recovery_tasks, then _reset_reaction_tasks
+        o["tar_action"][rc] = 0
+        o["has_bounce"][rc], o["bounce_pos"][rc] = False, 0
+        if st["use_history"]:
+            o["ball_obs"][rx] = o["ball_state"][rx, None, 0:3]
+        o["tar_time"][rx], o["tar_action"][rx] = 0, 1
+        o["num_reset_reaction"][rx] += 1
+        o["bounce_in"][rx], o["est_bounce_pos"][rx], o["est_bounce_time"][rx], o["est_bounce_in"][rx], o["est_max_height"][rx] = False, 0, 0, False, 0
+        o["swing_type_cycle"][rx] = -1
+        o["tar_time_total"][rx] = st["reset_reaction_nframes"] + R.integer(w[rx, 2], -5, 5)
+        if st["target_mode"] == "continuous":
+            lo, hi = np.array(st["target_min"], _f), np.array(st["target_max"], _f)
+            o["target_bounce_pos"][rx] = R.uniform(w[rx, 4:7]) * (hi - lo) + lo
+        elif st["target_mode"]:
+            u = R.uniform(w[rx, 3])
+            o["target_bounce_pos"][rx] = np.stack([np.where(u < _f(0.33), _f(-3), np.where(u > _f(0.67), _f(3), _f(0))), np.full_like(u, 10), np.zeros_like(u)], -1)
+        # ---- the observation of the flagged envs on the new state
+        ids = np.nonzero(rx | rc)[0]
+        if len(ids):
+            s2 = dict(s, **{k: v for k, v in o.items() if k in ("ball_state", "ball_traj", "traj_cursor", "target_bounce_pos", "ball_obs")})
+            obs, hist, rpos, rnorm = observation_reference(st, s2, ids)
+            o["obs"][ids], o["racket_pos"][ids], o["racket_normal"][ids] = obs, rpos, rnorm
+            if hist is not None:
+                o["ball_obs"][ids] = hist
+    o["pool_rows"] = np.where(rx, idx, -1)
+    return o
+
+
 # ------------------------------------------------------------------------------------------------------------------ the task
 class TennisControllerTask:
     """`PhysicsMVAEController` without the MVAE player, on top of a single-player `HumanoidSMPLIMRacketBall`.  Attribute names are the
@@ -291,7 +477,7 @@ class TennisControllerTask:
     file names or arrays).  `_ball_traj` [N,100,3] holds every env's drawn trajectory as it was drawn; `_ball_traj_cursor` [N] is the
     first frame of its window (the reference rolls the tensor instead, :365-366): `ball_traj_window()` gives the rolled view."""
 
-    def __init__(self, task, cfg, params=traj_out_params):
+    def __init__(self, task, cfg, params=traj_out_params, seed=None):
         env, v2p = dict(cfg.get("env") or {}), dict(cfg.get("v2p") or {})
         self._check_mode(task, v2p)
         if not hasattr(task, "_ball_root_states"):
@@ -350,6 +536,30 @@ class TennisControllerTask:
         self._imitation_target = None
         self._num_res_root_action = 0
         self._res_root_actions = None
+        # the device generator's key and the count of `v2p_controller_actions` launches: host numbers, never read back from the device
+        self.seed = int((cfg.get("params") or {}).get("seed", 0) if seed is None else seed) & (2 ** 64 - 1)
+        self._walk_calls = 0
+        self._walk_buffers = None
+        # cfg v2p.task_reset: 'torch' (default) is the reference's indexed torch code, random stream and all; 'device' is one launch
+        self._task_reset = v2p.get("task_reset", "torch")
+        if self._task_reset not in ("torch", "device"):
+            raise ValueError("TennisControllerTask: cfg v2p.task_reset %r is neither 'torch' nor 'device'" % (self._task_reset,))
+        self._reset_calls = 0
+        self._no_ids = torch.zeros(0, **i64)
+        if self._task_reset == "device":
+            self._init_device_reset(v2p)
+
+    def _init_device_reset(self, v2p):
+        from ..ball_traj import TennisBallGeneratorOffline
+
+        gen = getattr(self.task, "_ball_generator", None)
+        if not isinstance(gen, TennisBallGeneratorOffline) or torch.device(gen.device) != self.device:
+            raise NotImplementedError("TennisControllerTask: cfg v2p.task_reset 'device' draws from the pool of a TennisBallGeneratorOffline on %s "
+                                      "(cfg v2p.ball_traj_file); the task's ball generator is %s" % (self.device, "none" if gen is None else
+                                                                                                   "%s on %s" % (type(gen).__name__, gen.device)))
+        self._pool = gen.data.contiguous()
+        self.reset_settings = reset_settings(v2p["reset_reaction_nframes"], v2p.get("use_random_ball_target", False), gen.sample_random,
+                                             tuple(self._target_bounce_min.tolist()), tuple(self._target_bounce_max.tolist()), self.seed)
 
     def _check_mode(self, task, v2p):
         if v2p.get("dual_mode") or getattr(task, "racket_players", None) is not None:
@@ -386,8 +596,6 @@ class TennisControllerTask:
 
     def _refuse_unbuilt(self):
         """(`add_residual_root` moves the target's root: it needs an imitation target, attached before the step - or before the generator)"""
-        if self.cfg_v2p.get("random_walk_in_recovery"):
-            raise NotImplementedError("TennisControllerTask: random_walk_in_recovery is not built")
         if self.cfg_v2p.get("add_residual_root") and self._imitation_target is None:
             raise NotImplementedError("TennisControllerTask: add_residual_root is not built without an imitation target (attach_imitation_target)")
 
@@ -418,6 +626,12 @@ class TennisControllerTask:
         nz, nr, nroot = self._num_mvae_action, self._num_res_dof_action, self._num_res_root_action
         if actions.dim() != 2 or actions.shape[0] != self.num_envs or actions.shape[1] < nz + nr + nroot:
             raise ValueError("pre_physics_step: actions must be [%d, >= %d]" % (self.num_envs, nz + nr + nroot))
+        if self.cfg_v2p.get("random_walk_in_recovery"):
+            self._launch_actions(actions)
+            self._mvae_player.step(self._mvae_actions, self._res_dof_actions)
+            if self._imitation_target is not None:
+                self.post_mvae_step()
+            return
         self._actions = actions.clone()
         self._mvae_actions = actions[:, :nz].clone() * self.cfg_v2p.get("vae_action_scale", 1.0)
         self._res_dof_actions = torch.empty(0, device=self.device)
@@ -429,6 +643,28 @@ class TennisControllerTask:
             if nroot:
                 self._res_root_actions = actions[:, nz + nr:nz + nr + nroot].clone() * self._imitation_target.settings["residual_root_scale"]
             self.post_mvae_step()
+
+    def action_settings(self):
+        """What `v2p_controller_actions` and `controller_actions_reference` are made from, of the cfg and what is attached."""
+        root_scale = self._imitation_target.settings["residual_root_scale"] if self._num_res_root_action else 0.0
+        return action_settings(num_res_dof=self._num_res_dof_action, num_res_root=self._num_res_root_action,
+                               vae_action_scale=self.cfg_v2p.get("vae_action_scale", 1.0), residual_dof_scale=self.cfg_v2p.get("residual_dof_scale", 0.1),
+                               residual_root_scale=root_scale, random_walk=self.cfg_v2p.get("random_walk_in_recovery", False), seed=self.seed)
+
+    def _launch_actions(self, actions):
+        """`_actions`, `_mvae_actions`, `_res_dof_actions`, `_res_root_actions` of this step in one launch, into tensors allocated once;
+        the call counter advances by one per launch."""
+        st = self.action_settings()
+        key = (st["num_res_dof"], st["num_res_root"])
+        if self._walk_buffers is None or self._walk_buffers[0] != key:
+            f = dict(dtype=torch.float32, device=self.device)
+            self._walk_buffers = (key, action_outputs(st, self.num_envs, **f))
+        out = self._walk_buffers[1]
+        launch_actions(st, self.num_envs, actions, self._tar_action, out, call=self._walk_calls)
+        self._walk_calls += 1
+        self._actions, self._mvae_actions = out["actions_out"], out["mvae_actions"]
+        self._res_dof_actions = out["res_dof_actions"] if st["num_res_dof"] else torch.empty(0, device=self.device)
+        self._res_root_actions = out["res_root_actions"] if st["num_res_root"] and self._imitation_target is not None else None
 
     def post_mvae_step(self):
         """`HumanoidSMPLIMMVAE.post_mvae_step` (humanoid_smpl_im_mvae.py:593-598): the new imitation target and the low-level policy's
@@ -483,9 +719,33 @@ class TennisControllerTask:
             if self._has_init and self.num_envs > 1:
                 return
             env_ids = torch.arange(self.num_envs, device=self.device, dtype=torch.long)
+        if not torch.is_tensor(env_ids) and len(env_ids) == 0:
+            env_ids = self._no_ids  # (the rally path: no tensor is made)
         self._reset_envs(torch.as_tensor(env_ids, device=self.device, dtype=torch.long))
 
+    def _reset_envs_device(self, env_ids):
+        """`_reset_envs` under cfg v2p.task_reset 'device': the humanoid part for `env_ids` as ever, then `v2p_tennis_task_reset` for all
+        envs by their flags, then the two flags of `env_ids` are cleared.  No host read of a device result."""
+        some = env_ids.numel() > 0
+        if some:
+            self._reset_env_tensors(env_ids, keep_flags=True)
+            if self._mvae_player is not None:
+                self._mvae_player.reset(env_ids)
+                if self._imitation_target is not None:
+                    self._imitation_target.reset(env_ids)
+            self._num_reset[env_ids] += 1
+        gen = self.task._ball_generator
+        launch_reset(dict(self.settings, **self.reset_settings), self._tensors(), self.num_envs, self._pool, self._num_reset_reaction,
+                     sample_idx=None if gen.sample_random else gen.sample_idx, call=self._reset_calls)
+        self._reset_calls += 1
+        if some:
+            self._reset_reaction_buf[env_ids] = False
+            self._reset_recovery_buf[env_ids] = False
+        self._has_init = True
+
     def _reset_envs(self, env_ids):
+        if self._task_reset == "device":
+            return self._reset_envs_device(env_ids)
         reaction_ids = self._reset_reaction_buf.nonzero(as_tuple=False).flatten()  # (include env_ids)
         recovery_ids = self._reset_recovery_buf.nonzero(as_tuple=False).flatten()
         all_ids = (self._reset_reaction_buf | self._reset_recovery_buf).nonzero(as_tuple=False).flatten()
@@ -512,12 +772,13 @@ class TennisControllerTask:
             launch_obs(self.settings, self._tensors(), self.num_envs, all_ids)
         self._has_init = True
 
-    def _reset_env_tensors(self, env_ids):
+    def _reset_env_tensors(self, env_ids, keep_flags=False):
         self.progress_buf[env_ids] = 0
         self.reset_buf[env_ids] = 0
         self._terminate_buf[env_ids] = 0
-        self._reset_reaction_buf[env_ids] = False
-        self._reset_recovery_buf[env_ids] = False
+        if not keep_flags:
+            self._reset_reaction_buf[env_ids] = False
+            self._reset_recovery_buf[env_ids] = False
         self._num_reset_reaction[env_ids] = 0
         self._distance[env_ids] = 0
 

@@ -252,8 +252,8 @@ class DualTennisControllerTask(tc.TennisControllerTask):
     flags start at zero (:16-17).  `post_physics_step()` is `v2p_tennis_dual_step`; `reset([])` is `v2p_tennis_dual_handover` alone - the
     rally path, no synchronisation; `reset(ids)` with whole sorted pairs resets their actors first."""
 
-    def __init__(self, task, cfg, params=traj_out_params, traj_in_params=traj_in_params):
-        super().__init__(task, cfg, params)
+    def __init__(self, task, cfg, params=traj_out_params, traj_in_params=traj_in_params, seed=None):
+        super().__init__(task, cfg, params, seed=seed)
         v2p, dev, n = self.cfg_v2p, self.device, self.num_envs
         if "ball_traj_in_file" not in v2p:
             raise ValueError("DualTennisControllerTask: cfg v2p.ball_traj_in_file (the in-estimator's table, a file name or an array) is required")
