@@ -916,6 +916,56 @@ int v2p_mvae_target_reset(const v2p_mvae_target_cfg* cfg, int64_t num_envs, cons
 int v2p_mvae_target_actions(const v2p_mvae_target_cfg* cfg, int64_t n, const float* actions_in /*[n,75]*/, const v2p_mvae_target_buffers* base_buffers,
                             float* actions_out /*[n,75]*/, void* stream);
 
+/* ---- what stands around the policy networks' dense layers in a control step (vid2player/players/im_player.py:187-199,
+ * players/v2p_player.py:113-131, models/im_network_builder.py:53-81, models/im_network_builder_dual.py:37-45): the clamp of the
+ * observation, the input normaliser, the split of a two-player batch into one contiguous GEMM operand per network, and on the way back
+ * the clamp of the low-level policy's mu and `_action_to_pd_targets`.  The dense layers themselves are the caller's (hipBLASLt).
+ * Stateless: every buffer is the caller's, no allocation, no host synchronisation, one launch per call.
+ *
+ * Side-major order of the network's rows: with sides = 1 env i is row i; with sides = 2 (n even; env i is player i & 1, rows 0::2 go
+ * through network1 and rows 1::2 through network2) env i is row (i & 1) * (n / 2) + (i >> 1), so that each network reads and writes one
+ * contiguous [n/2, .] block and nothing is gathered or interleaved.
+ * Every clamp is torch.clamp's: a NaN stays a NaN, a clip of +inf changes nothing. */
+enum { V2P_NORM_NONE = 0, V2P_NORM_RUNNING = 1, V2P_NORM_MEAN_VAR = 2 };
+typedef struct {
+    int32_t kind;        /* V2P_NORM_NONE:     y = x (models/running_norm.py:35 with n == 0)
+                          * V2P_NORM_RUNNING:  y = clamp((x - mean) / (spread + 1e-8), -clip, clip), spread = the std (running_norm.py:31-42, eval)
+                          * V2P_NORM_MEAN_VAR: y = clamp((x - mean) / sqrt(spread + eps), -clip, clip), spread = the variance (rl_games'
+                          *                    RunningMeanStd in eval mode: eps 1e-5, clip 5, statistics cast to float32) */
+    float eps;           /* MEAN_VAR only */
+    float clip;          /* > 0 (not read by NONE) */
+    const float* mean;   /* [dim] DEVICE (not read by NONE) */
+    const float* spread; /* [dim] DEVICE: std or variance by kind (not read by NONE) */
+} v2p_policy_norm;
+typedef struct {
+    int32_t sides;           /* 1 or 2 */
+    float clip_obs;          /* the observation is clamped to +-clip_obs first (> 0; +inf: no clamp) */
+    v2p_policy_norm norm[2]; /* the normaliser of each side's network; [1] is not read with sides = 1 */
+} v2p_policy_input_cfg;
+/* x = normaliser(clamp(obs, +-clip_obs)) for envs 0 .. n-1, obs [n,dim] in env order, x [n,dim] in side-major order; dim >= 1.  x must
+ * not alias obs with sides = 2.  Refused before any HIP call (V2P_ERR_INVALID, a message that names the call): a null cfg, obs or x, a
+ * null mean / spread of a normaliser that reads them, sides outside {1, 2}, an odd n with two sides, n < 0, dim < 1, an unknown
+ * normaliser kind, a clip that is not > 0.  n = 0 is a no-op. */
+int v2p_policy_input(const v2p_policy_input_cfg* cfg, int64_t n, int64_t dim, const float* obs /*[n,dim]*/, float* x /*[n,dim]*/, void* stream);
+typedef struct {                  /* DEVICE buffers the imitation observation is computed from, in place */
+    const float* rb_state;        /* [n,24,13] the engine's `_rigid_body_state` */
+    const float* dof_state;       /* [n,69,2]  the engine's `_dof_state` */
+    const float* target;          /* the packed current-target rows (layout of v2p_env_buffers.target): rb_pos, rb_rot, dof_pos are read */
+    int64_t target_stride;        /* floats between the rows of `target` (>= 331) */
+    const float* motion_bodies;   /* [n,11] `_reset_ref_motion_bodies` */
+} v2p_ll_policy_src;
+/* The same tail over the low-level policy's own observation: the 734 columns of v2p_obs_imitation (the same device code, the same bits)
+ * are computed from the engine's state in place, written to raw_obs [n,734] in env order when it is given (nullable), and
+ * x [n,734] = normaliser(clamp(row, +-clip_obs)) in side-major order.  Refused: as v2p_policy_input, and dim != 734, a null src or
+ * pointer of it, target_stride < 331. */
+int v2p_ll_policy_input(const v2p_policy_input_cfg* cfg, int64_t n, int64_t dim, const v2p_ll_policy_src* src, float* raw_obs /*[n,734] nullable*/,
+                        float* x /*[n,734]*/, void* stream);
+/* v2p_mvae_target_actions of clamp(mu, +-clip_actions), mu [n,75] in side-major order, actions_out [n,75] in env order (the same device
+ * code as v2p_mvae_target_actions, the same bits).  actions_out must not alias mu with sides = 2.  Refused: as v2p_mvae_target_actions,
+ * and sides outside {1, 2}, an odd n with two sides, a clip_actions that is not > 0. */
+int v2p_ll_policy_actions(const v2p_mvae_target_cfg* cfg, int64_t n, int32_t sides, float clip_actions, const float* mu /*[n,75]*/,
+                          const v2p_mvae_target_buffers* base_buffers, float* actions_out /*[n,75]*/, void* stream);
+
 /* measurement: HIP events around every launch of the physics kernel (the dominant kernel of the step), recorded on the launch stream
  * by v2p_env_step / v2p_env_physics between _begin and _end (at most max_launches of them).  _end synchronises the events and returns
  * the summed kernel time in milliseconds and the number of launches measured.  bench.py's roofline.kernel_ms comes from here, from

@@ -10,6 +10,7 @@
 #include "controller_actions.hpp"
 #include "mvae_player.hpp"
 #include "mvae_target.hpp"
+#include "policy_io.hpp"
 #include "tennis_reset.hpp"
 #include "tennis_task.hpp"
 #include "v2p_internal.hpp"
@@ -551,6 +552,71 @@ int v2p_mvae_target_actions(const v2p_mvae_target_cfg* c, int64_t n, const float
     if (n > 0 && (!actions_in || !actions_out)) { set_error("v2p_mvae_target_actions: null actions"); return V2P_ERR_INVALID; }
     if (n == 0) return V2P_OK;
     return launch_mvae_target_actions(*c, n, actions_in, *b, actions_out, (hipStream_t)stream);
+}
+
+// what the two policy-input entry points refuse; `fn` names the call
+static int policy_input_check(const char* fn, const v2p_policy_input_cfg* c, int64_t n, int64_t dim) {
+    if (!c) { set_error("%s: null cfg", fn); return V2P_ERR_INVALID; }
+    if (n < 0) { set_error("%s: n %lld < 0", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (dim < 1) { set_error("%s: dim %lld < 1", fn, (long long)dim); return V2P_ERR_INVALID; }
+    if (c->sides != 1 && c->sides != 2) { set_error("%s: sides %d is neither 1 nor 2", fn, c->sides); return V2P_ERR_INVALID; }
+    if (c->sides == 2 && (n & 1)) { set_error("%s: n %lld is odd with two sides", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (!(c->clip_obs > 0.f)) { set_error("%s: clip_obs %g is not > 0", fn, (double)c->clip_obs); return V2P_ERR_INVALID; }
+    for (int s = 0; s < c->sides; ++s) {
+        const v2p_policy_norm& nm = c->norm[s];
+        if (nm.kind != V2P_NORM_NONE && nm.kind != V2P_NORM_RUNNING && nm.kind != V2P_NORM_MEAN_VAR) {
+            set_error("%s: unknown normaliser kind %d of side %d", fn, nm.kind, s);
+            return V2P_ERR_INVALID;
+        }
+        if (nm.kind == V2P_NORM_NONE) continue;
+        if (!nm.mean || !nm.spread) { set_error("%s: null mean / spread of side %d's normaliser", fn, s); return V2P_ERR_INVALID; }
+        if (!(nm.clip > 0.f)) { set_error("%s: side %d's normaliser clip %g is not > 0", fn, s, (double)nm.clip); return V2P_ERR_INVALID; }
+        if (nm.kind == V2P_NORM_MEAN_VAR && !(nm.eps >= 0.f)) { set_error("%s: side %d's normaliser eps %g < 0", fn, s, (double)nm.eps); return V2P_ERR_INVALID; }
+    }
+    return V2P_OK;
+}
+
+int v2p_policy_input(const v2p_policy_input_cfg* c, int64_t n, int64_t dim, const float* obs, float* x, void* stream) {
+    const int rc = policy_input_check("v2p_policy_input", c, n, dim);
+    if (rc != V2P_OK) return rc;
+    if (!obs || !x) { set_error("v2p_policy_input: null obs / x"); return V2P_ERR_INVALID; }
+    if (c->sides == 2 && obs == x) { set_error("v2p_policy_input: x must not be obs with two sides"); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    return launch_policy_input(*c, n, dim, obs, x, (hipStream_t)stream);
+}
+
+int v2p_ll_policy_input(const v2p_policy_input_cfg* c, int64_t n, int64_t dim, const v2p_ll_policy_src* src, float* raw_obs, float* x, void* stream) {
+    const int rc = policy_input_check("v2p_ll_policy_input", c, n, dim);
+    if (rc != V2P_OK) return rc;
+    if (dim != POLICY_LL_OBS) { set_error("v2p_ll_policy_input: dim %lld is not %d", (long long)dim, POLICY_LL_OBS); return V2P_ERR_INVALID; }
+    if (!src || !x) { set_error("v2p_ll_policy_input: null src / x"); return V2P_ERR_INVALID; }
+    if (!src->rb_state || !src->dof_state || !src->target || !src->motion_bodies) {
+        set_error("v2p_ll_policy_input: null rb_state / dof_state / target / motion_bodies");
+        return V2P_ERR_INVALID;
+    }
+    if (src->target_stride < MSD) { set_error("v2p_ll_policy_input: target_stride %lld < %d", (long long)src->target_stride, MSD); return V2P_ERR_INVALID; }
+    if (raw_obs == x) { set_error("v2p_ll_policy_input: raw_obs and x are the same buffer"); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    return launch_ll_policy_input(*c, n, *src, raw_obs, x, (hipStream_t)stream);
+}
+
+int v2p_ll_policy_actions(const v2p_mvae_target_cfg* c, int64_t n, int32_t sides, float clip_actions, const float* mu, const v2p_mvae_target_buffers* b,
+                          float* actions_out, void* stream) {
+    const int rc = mvae_target_check("v2p_ll_policy_actions", c, n, b);
+    if (rc != V2P_OK) return rc;
+    if (sides != 1 && sides != 2) { set_error("v2p_ll_policy_actions: sides %d is neither 1 nor 2", sides); return V2P_ERR_INVALID; }
+    if (sides == 2 && (n & 1)) { set_error("v2p_ll_policy_actions: n %lld is odd with two sides", (long long)n); return V2P_ERR_INVALID; }
+    if (!(clip_actions > 0.f)) { set_error("v2p_ll_policy_actions: clip_actions %g is not > 0", (double)clip_actions); return V2P_ERR_INVALID; }
+    if (c->pd_target_base != V2P_PD_BASE_TARGET_POS && c->pd_target_base != V2P_PD_BASE_CURRENT_POS && c->pd_target_base != V2P_PD_BASE_NONE) {
+        set_error("v2p_ll_policy_actions: unknown pd_target_base %d", c->pd_target_base);
+        return V2P_ERR_INVALID;
+    }
+    const void* base = c->pd_target_base == V2P_PD_BASE_TARGET_POS ? (const void*)b->target : (c->pd_target_base == V2P_PD_BASE_CURRENT_POS ? (const void*)b->dof_state : (const void*)b->pd_action_offset);
+    if (!base || (!c->no_scale_action && !b->pd_action_scale)) { set_error("v2p_ll_policy_actions: null base buffer / pd_action_scale"); return V2P_ERR_INVALID; }
+    if (!mu || !actions_out) { set_error("v2p_ll_policy_actions: null mu / actions_out"); return V2P_ERR_INVALID; }
+    if (sides == 2 && mu == actions_out) { set_error("v2p_ll_policy_actions: actions_out must not be mu with two sides"); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    return launch_ll_policy_actions(*c, n, sides, clip_actions, mu, *b, actions_out, (hipStream_t)stream);
 }
 
 int v2p_env_reset(v2p_env* e, const int64_t* env_ids, int64_t n, const float* motion_times, void* stream) {

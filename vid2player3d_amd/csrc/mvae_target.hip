@@ -237,15 +237,7 @@ __global__ __launch_bounds__(256) void mvae_target_actions_kernel(const MtArgs a
     if (tid >= a.n * NACT) return;
     const int64_t e = tid / NACT;
     const int c = (int)(tid - e * NACT);
-    float v = in[tid];
-    if (c < NDOF) {
-        float base;
-        if (a.c.pd_target_base == V2P_PD_BASE_TARGET_POS) base = a.b.target[e * MSD + MS_DOF_POS + c];
-        else if (a.c.pd_target_base == V2P_PD_BASE_CURRENT_POS) base = a.b.dof_state[(e * NDOF + c) * 2];
-        else base = a.b.pd_action_offset[c];
-        v = a.c.no_scale_action ? base + v : base + a.b.pd_action_scale[c] * v;
-    }
-    out[tid] = v;
+    out[tid] = mvae_pd_target(a.c, a.b, e, c, in[tid]);
 }
 
 // the levels and the inverse body order of a checked cfg

@@ -17,7 +17,11 @@ What turns the generator's kinematic pose into the imitation target of the low-l
 `attach_imitation_target(target)`, `pre_physics_step` ends with `post_mvae_step()`, the reset puts the humanoid into the generator's
 pose, and `physics_step(ll_actions)` steps the wrapped task on the PD targets of the low-level policy's actions: `pre_physics_step` ->
 `physics_step` -> `post_physics_step` is vid2player's control step.  Without one, every path is as before.  The dual controller is
-`tasks.tennis_controller_dual.DualTennisControllerTask`.  Not built: `optimize_two_hand_backhand`, `update_mvae_from_sim`, the low-level policy network itself.
+`tasks.tennis_controller_dual.DualTennisControllerTask`.  Not built: `optimize_two_hand_backhand`, `update_mvae_from_sim`.
+
+The low-level policy network is `vid2player3d_amd.policies.LowLevelPolicy` (two launches around the dense layers).  Attached with
+`attach_low_level_policy(policy)`, `physics_step()` takes no argument: the policy computes the imitation observation in place, runs its
+network(s) and hands the PD targets to the engine.  `step(actions)` is then the reference's `PhysicsMVAEController.step(actions)`.
 
 With cfg v2p `random_walk_in_recovery` (every shipped controller config sets it) the action part of `pre_physics_step` is ONE launch,
 `v2p_controller_actions` (csrc/controller_actions.hip): the copy of the actions, the scaled latent and residual columns, and the latent
@@ -534,6 +538,7 @@ class TennisControllerTask:
         self._has_init = False
         self._mvae_player = None
         self._imitation_target = None
+        self._ll_policy = None
         self._num_res_root_action = 0
         self._res_root_actions = None
         # the device generator's key and the count of `v2p_controller_actions` launches: host numbers, never read back from the device
@@ -612,6 +617,13 @@ class TennisControllerTask:
         self._imitation_target = target
         self._num_res_root_action = 3 if target.settings["add_residual_root"] else 0
 
+    def attach_low_level_policy(self, policy):
+        """Make `policy` (a `policies.LowLevelPolicy` around the attached imitation target) the physics player's network: `physics_step()`
+        without an argument then takes its actions, and the imitation observation is computed by the policy's input launch."""
+        if self._imitation_target is None or policy.target is not self._imitation_target:
+            raise ValueError("attach_low_level_policy: the policy wraps another imitation target than the attached one (attach_imitation_target first)")
+        self._ll_policy = policy
+
     def get_action_size(self):
         if self._mvae_player is None:
             raise RuntimeError("TennisControllerTask: no motion generator is attached")
@@ -674,14 +686,28 @@ class TennisControllerTask:
         if self._num_res_root_action and self._res_root_actions is None:
             raise RuntimeError("TennisControllerTask.post_mvae_step: add_residual_root needs the actions of a pre_physics_step first")
         self._imitation_target.step(self._res_root_actions)
-        self._imitation_target.compute_observations()
+        if self._ll_policy is None:  # (an attached policy computes the observation in its own input launch, from the same state)
+            self._imitation_target.compute_observations()
 
-    def physics_step(self, ll_actions):
+    def physics_step(self, ll_actions=None):
         """The physics player's control step on the low-level policy's actions [N,75]: `_action_to_pd_targets` (the engine clamps), then
-        the wrapped task's step."""
+        the wrapped task's step.  Without an argument the attached low-level policy makes the actions (`ImitatorPlayer.run_one_step`)."""
         if self._imitation_target is None:
             raise RuntimeError("TennisControllerTask.physics_step: no imitation target is attached (attach_imitation_target)")
+        if ll_actions is None:
+            if self._ll_policy is None:
+                raise RuntimeError("TennisControllerTask.physics_step: no low-level policy is attached (attach_low_level_policy) and no actions are given")
+            self.task.step(self._ll_policy.step())
+            return
         self.task.step(self._imitation_target.actions(ll_actions))
+
+    def step(self, actions):
+        """`PhysicsMVAEController.step(actions)` (:244-246 with the base task's step): pre_physics_step -> physics_step ->
+        post_physics_step with the attached generator, target and low-level policy.  Returns (obs_buf, rew_buf, reset_buf, extras)."""
+        self.pre_physics_step(actions)
+        self.physics_step()
+        self.post_physics_step()
+        return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
 
     # ------------------------------------------------------------------ sizes
     def get_actor_obs_size(self):
