@@ -966,6 +966,84 @@ int v2p_ll_policy_input(const v2p_policy_input_cfg* cfg, int64_t n, int64_t dim,
 int v2p_ll_policy_actions(const v2p_mvae_target_cfg* cfg, int64_t n, int32_t sides, float clip_actions, const float* mu /*[n,75]*/,
                           const v2p_mvae_target_buffers* base_buffers, float* actions_out /*[n,75]*/, void* stream);
 
+/* ---- The tennis controller's PPO agent (V2PAgent, vid2player/agents/v2p_agent.py, over PhysicsMVAEController): three row kernels.
+ * All of them are built without FMA contraction, with the correctly rounded division and square root, and clamp by compare-and-select
+ * (a NaN stays a NaN).  DEVICE pointers throughout. */
+#define V2P_CTL_MAX_ACTIONS 128
+#define V2P_CTL_MAX_SUB_REWARDS 8
+/* What V2PModel.Network.forward(is_train = False) and the env wrapper do behind the `mu` layer (models/v2p_models.py:41-52,
+ * env/tasks/vec_task.py:103), rows 0 .. n-1, columns 0 .. num_actions-1 (1 <= num_actions <= 128):
+ *   actions = mu + sigma * noise;  mus = mu;  sigmas = sigma (every row);
+ *   neglogp = 0.5 sum(((actions - mu) / sigma)^2) + float(0.5 log(2 pi) num_actions) + sum(logstd);
+ *   actions_clamped = clamp(actions, +-clip_actions).
+ * sigma [A] is exp(logstd), made by the caller; noise [n,A] are the caller's standard-normal draws.  The elementwise outputs are
+ * torch's float32 results bit for bit; the two sums of neglogp are taken over the wave (columns k and k + 64 on lane k, then a
+ * butterfly), so neglogp agrees with torch's to rounding.  actions_row / mus_row / sigmas_row (the experience buffer's rows) are
+ * nullable.  Refused before any HIP call: n < 0, num_actions outside [1, 128], a clip_actions that is not > 0, a null mu, logstd,
+ * sigma, noise, neglogp_row or actions_clamped.  n = 0 is a no-op. */
+int v2p_ctl_policy_head(int64_t n, int32_t num_actions, const float* mu /*[n,A]*/, const float* logstd /*[A]*/, const float* sigma /*[A]*/,
+                        const float* noise /*[n,A]*/, float clip_actions, float* actions_row /*[n,A] nullable*/, float* mus_row /*[n,A] nullable*/,
+                        float* sigmas_row /*[n,A] nullable*/, float* neglogp_row /*[n]*/, float* actions_clamped /*[n,A]*/, void* stream);
+/* The bookkeeping of V2PAgent.play_steps behind env_step (v2p_agent.py:245-276) in one launch.  obs [n,obs_dim], rew [n], reset /
+ * terminate [n] int64 (the controller's buffers), sub_rewards [n,num_sub] with 0 <= num_sub <= 8 (nullable at 0):
+ *   next_obs_row = clamp(obs, +-clip_obs) (the env wrapper's clamp; +inf: none);  rewards_row = rew;  dones_row = float(reset);
+ *   terminated = float(terminate);  cur_rewards += rew;  cur_lengths += 1;
+ *   acc[0] += the number of envs with reset != 0, acc[1] += the sum of their cur_rewards, acc[2] += the sum of their cur_lengths
+ *   (what game_rewards / game_lengths receive), acc[3] += sum(rew) over ALL envs, sub_acc[k] += sum(sub_rewards[:, k]) over all envs
+ *   (what the two AverageMeters receive, times n);  then cur_rewards *= 1 - dones, cur_lengths *= 1 - dones.
+ * The sums are float64 and deterministic, with no atomics: workgroup 0 alone takes the per-env work; its thread t adds the envs
+ * t, t + 256, ... in rising order, the 64 lanes of a wave combine by a butterfly (offsets 32, 16, .., 1; lane 0's value), the four
+ * waves add as ((w0 + w1) + w2) + w3, and one thread adds the result to the accumulator.  The other workgroups stream the
+ * observation rows.  Refused before any HIP call: n < 0, obs_dim < 1, num_sub outside [0, 8], a clip_obs that is not > 0, any null
+ * pointer with n > 0 (sub_rewards / sub_acc only with num_sub > 0).  n = 0 is a no-op. */
+int v2p_ctl_rollout_record(int64_t n, int64_t obs_dim, int32_t num_sub, float clip_obs, const float* obs, const float* rew, const int64_t* reset,
+                           const int64_t* terminate, const float* sub_rewards, float* next_obs_row /*[n,obs_dim]*/, float* rewards_row /*[n]*/,
+                           float* dones_row /*[n]*/, float* terminated /*[n]*/, float* cur_rewards /*[n] in/out*/, float* cur_lengths /*[n] in/out*/,
+                           double* acc /*[4] in/out*/, double* sub_acc /*[num_sub] in/out*/, void* stream);
+/* The loss head of V2PAgent.calc_gradients (v2p_agent.py:329-362, 395-397; learning/common_agent.py:442-450, 491-520 with clip_value
+ * False; PhysicsMVAEController.get_aux_losses) under a fixed sigma, forward and backward.  With row r of the minibatch and
+ * j = idx ? idx[r] : r its row of the epoch's dataset:
+ *   t = (actions[j] - mu[r]) / sigma;  neglogp = 0.5 sum(t^2) + float(0.5 log(2 pi) A) + sum(logstd);
+ *   ratio = exp(old_neglogp[j] - neglogp);  a = max(-adv[j] ratio, -adv[j] clamp(ratio, 1 - e_clip, 1 + e_clip));
+ *   c = (returns[j] - value[r])^2;  b = sum(clamp_max(mu + 1, 0)^2 + clamp_min(mu - 1, 0)^2) (0 without has_bounds_loss);
+ *   d = sum(mu[r, c0:c1]^2);  loss = mean a + critic_coef mean c - entropy_coef ent + bounds_loss_coef mean b + dof_res_weight mean d.
+ * grad_mu [B,A] and grad_value [B] are d loss / d mu and d loss / d value, computed directly (ties of the max split evenly and the
+ * inclusive bounds of the clamp pass, as autograd has them).  stats[8] (float64): the means of a, c, b, d, of |ratio - 1| > e_clip,
+ * of policy_kl(mu, sigma, old_mu[j], old_sigma) with its 1e-5 guards, the entropy sum(0.5 + 0.5 log(2 pi) + log(sigma)), and loss.
+ * One wave per row (columns k and k + 64 on lane k); the statistics reduce in two stages - per-workgroup partials in float64 into
+ * `partials`, then a second launch of one workgroup that adds them in workgroup order - so they are the same bits on every run.
+ * A row whose j is outside [0, dataset_rows) gets NaN gradients and makes the statistics NaN; nothing is read for it. */
+#define V2P_PPO_LOSS_MAX_BLOCKS 1024
+#define V2P_PPO_LOSS_PARTIALS (6 * V2P_PPO_LOSS_MAX_BLOCKS) /* doubles of the `partials` workspace */
+typedef struct {
+    int32_t num_actions;       /* A, 1 .. 128 */
+    int32_t has_bounds_loss;   /* 0: bounds_loss_coef None */
+    int32_t c0, c1;            /* columns [c0, c1) of the residual-DoF means, 0 <= c0 <= c1 <= A (empty allowed) */
+    int64_t dataset_rows;      /* rows of the dataset arrays (N * T); B with idx null */
+    double e_clip;             /* > 0 */
+    float critic_coef, entropy_coef, bounds_loss_coef, dof_res_weight;
+} v2p_ppo_loss_cfg;
+typedef struct {
+    const float* mu;           /* [B,A] the network's means */
+    const float* value;        /* [B] the network's values */
+    const int64_t* idx;        /* [B] rows of the dataset, nullable = identity */
+    const float* old_neglogp;  /* [rows] */
+    const float* advantages;   /* [rows] */
+    const float* returns;      /* [rows] */
+    const float* actions;      /* [rows,A] */
+    const float* old_mu;       /* [rows,A] */
+    const float* old_sigma;    /* [A] */
+    const float* logstd;       /* [A] */
+    const float* sigma;        /* [A] exp(logstd) */
+    float* grad_mu;            /* [B,A] out */
+    float* grad_value;         /* [B] out */
+    double* stats;             /* [8] out */
+    double* partials;          /* [V2P_PPO_LOSS_PARTIALS] workspace */
+} v2p_ppo_loss_buffers;
+/* Refused before any HIP call: a null cfg / buffers, B < 0, A outside [1, 128], c0 / c1 outside 0 <= c0 <= c1 <= A, an e_clip that
+ * is not > 0, dataset_rows < B without idx, any null pointer but idx with B > 0.  B = 0 is a no-op. */
+int v2p_ppo_loss(const v2p_ppo_loss_cfg* cfg, int64_t B, const v2p_ppo_loss_buffers* buffers, void* stream);
+
 /* measurement: HIP events around every launch of the physics kernel (the dominant kernel of the step), recorded on the launch stream
  * by v2p_env_step / v2p_env_physics between _begin and _end (at most max_launches of them).  _end synchronises the events and returns
  * the summed kernel time in milliseconds and the number of launches measured.  bench.py's roofline.kernel_ms comes from here, from

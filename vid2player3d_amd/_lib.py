@@ -207,6 +207,26 @@ class LLPolicySrc(C.Structure):
     _fields_ = [("rb_state", vp), ("dof_state", vp), ("target", vp), ("target_stride", C.c_int64), ("motion_bodies", vp)]
 
 
+CTL_MAX_ACTIONS, CTL_MAX_SUB_REWARDS = 128, 8
+PPO_LOSS_MAX_BLOCKS = 1024
+PPO_LOSS_PARTIALS = 6 * PPO_LOSS_MAX_BLOCKS  # doubles of v2p_ppo_loss_buffers.partials
+PPO_LOSS_STATS = ("actor_loss", "critic_loss", "b_loss", "aux_dof_res_loss", "actor_clip_frac", "kl", "entropy", "loss")
+
+
+class PpoLossCfg(C.Structure):
+    """v2p_ppo_loss_cfg: the constants of the controller agent's loss head (v2p_ppo_loss)."""
+    _fields_ = [("num_actions", C.c_int32), ("has_bounds_loss", C.c_int32), ("c0", C.c_int32), ("c1", C.c_int32), ("dataset_rows", C.c_int64),
+                ("e_clip", C.c_double), ("critic_coef", C.c_float), ("entropy_coef", C.c_float), ("bounds_loss_coef", C.c_float), ("dof_res_weight", C.c_float)]
+
+
+PPO_LOSS_BUFFER_NAMES = ("mu", "value", "idx", "old_neglogp", "advantages", "returns", "actions", "old_mu", "old_sigma", "logstd", "sigma", "grad_mu", "grad_value",
+                         "stats", "partials")
+
+
+class PpoLossBuffers(C.Structure):
+    _fields_ = [(k, vp) for k in PPO_LOSS_BUFFER_NAMES]
+
+
 class ContextTransform(C.Structure):
     _fields_ = [("num_ops", C.c_int32), ("ops", C.c_int32 * 3), ("mask_joints", C.c_uint32), ("noise_prob", C.c_float), ("noise_std", C.c_float),
                 ("conf_std", C.c_float), ("min_conf", C.c_float), ("drop_prob", C.c_float)]
@@ -291,6 +311,9 @@ def load():
         "v2p_policy_input": [C.POINTER(PolicyInputCfg), C.c_int64, C.c_int64, vp, vp, vp],
         "v2p_ll_policy_input": [C.POINTER(PolicyInputCfg), C.c_int64, C.c_int64, C.POINTER(LLPolicySrc), vp, vp, vp],
         "v2p_ll_policy_actions": [C.POINTER(MvaeTargetCfg), C.c_int64, C.c_int32, C.c_float, vp, C.POINTER(MvaeTargetBuffers), vp, vp],
+        "v2p_ctl_policy_head": [C.c_int64, C.c_int32, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp],
+        "v2p_ctl_rollout_record": [C.c_int64, C.c_int64, C.c_int32, C.c_float] + [vp] * 14,
+        "v2p_ppo_loss": [C.POINTER(PpoLossCfg), C.c_int64, C.POINTER(PpoLossBuffers), vp],
         "v2p_debug_guards": [C.c_int64],
         "v2p_debug_guards_selftest": [C.c_int],
         "v2p_env_guard_counts": [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
@@ -313,7 +336,7 @@ def load():
 EXPORTED_SYMBOLS = (
     "v2p_model_create", "v2p_model_destroy", "v2p_mlib_create", "v2p_mlib_destroy", "v2p_motion_state", "v2p_reward", "v2p_reset_flags",
     "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_obs_imitation_packed_w", "v2p_policy_head_w", "v2p_policy_head_record_w", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_set_context_transform", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
-    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_tennis_dual_step", "v2p_tennis_dual_handover", "v2p_controller_actions", "v2p_tennis_task_reset", "v2p_mvae_step", "v2p_mvae_reset", "v2p_mvae_dual_step", "v2p_mvae_dual_reset", "v2p_mvae_target_step", "v2p_mvae_target_reset", "v2p_mvae_target_actions", "v2p_policy_input", "v2p_ll_policy_input", "v2p_ll_policy_actions", "v2p_last_error", "v2p_abi_version",
+    "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_tennis_dual_step", "v2p_tennis_dual_handover", "v2p_controller_actions", "v2p_tennis_task_reset", "v2p_mvae_step", "v2p_mvae_reset", "v2p_mvae_dual_step", "v2p_mvae_dual_reset", "v2p_mvae_target_step", "v2p_mvae_target_reset", "v2p_mvae_target_actions", "v2p_policy_input", "v2p_ll_policy_input", "v2p_ll_policy_actions", "v2p_ctl_policy_head", "v2p_ctl_rollout_record", "v2p_ppo_loss", "v2p_last_error", "v2p_abi_version",
     "v2p_debug_guards", "v2p_debug_guards_selftest", "v2p_env_guard_counts",
 )
 

@@ -8,6 +8,7 @@
 #include <new>
 
 #include "controller_actions.hpp"
+#include "ctl_ppo.hpp"
 #include "mvae_player.hpp"
 #include "mvae_target.hpp"
 #include "policy_io.hpp"
@@ -598,6 +599,65 @@ int v2p_ll_policy_input(const v2p_policy_input_cfg* c, int64_t n, int64_t dim, c
     if (raw_obs == x) { set_error("v2p_ll_policy_input: raw_obs and x are the same buffer"); return V2P_ERR_INVALID; }
     if (n == 0) return V2P_OK;
     return launch_ll_policy_input(*c, n, *src, raw_obs, x, (hipStream_t)stream);
+}
+
+int v2p_ctl_policy_head(int64_t n, int32_t num_actions, const float* mu, const float* logstd, const float* sigma, const float* noise, float clip_actions,
+                        float* actions_row, float* mus_row, float* sigmas_row, float* neglogp_row, float* actions_clamped, void* stream) {
+    if (n < 0) { set_error("v2p_ctl_policy_head: n %lld < 0", (long long)n); return V2P_ERR_INVALID; }
+    if (num_actions < 1 || num_actions > V2P_CTL_MAX_ACTIONS) {
+        set_error("v2p_ctl_policy_head: num_actions %d is outside [1, %d]", num_actions, V2P_CTL_MAX_ACTIONS);
+        return V2P_ERR_INVALID;
+    }
+    if (!(clip_actions > 0.f)) { set_error("v2p_ctl_policy_head: clip_actions %g is not > 0", (double)clip_actions); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    if (!mu || !logstd || !sigma || !noise || !neglogp_row || !actions_clamped) {
+        set_error("v2p_ctl_policy_head: null mu / logstd / sigma / noise / neglogp_row / actions_clamped");
+        return V2P_ERR_INVALID;
+    }
+    return launch_ctl_policy_head(n, num_actions, mu, logstd, sigma, noise, clip_actions, actions_row, mus_row, sigmas_row, neglogp_row, actions_clamped,
+                                  (hipStream_t)stream);
+}
+
+int v2p_ctl_rollout_record(int64_t n, int64_t obs_dim, int32_t num_sub, float clip_obs, const float* obs, const float* rew, const int64_t* reset,
+                           const int64_t* terminate, const float* sub_rewards, float* next_obs_row, float* rewards_row, float* dones_row, float* terminated,
+                           float* cur_rewards, float* cur_lengths, double* acc, double* sub_acc, void* stream) {
+    if (n < 0) { set_error("v2p_ctl_rollout_record: n %lld < 0", (long long)n); return V2P_ERR_INVALID; }
+    if (obs_dim < 1) { set_error("v2p_ctl_rollout_record: obs_dim %lld < 1", (long long)obs_dim); return V2P_ERR_INVALID; }
+    if (num_sub < 0 || num_sub > V2P_CTL_MAX_SUB_REWARDS) {
+        set_error("v2p_ctl_rollout_record: num_sub %d is outside [0, %d]", num_sub, V2P_CTL_MAX_SUB_REWARDS);
+        return V2P_ERR_INVALID;
+    }
+    if (!(clip_obs > 0.f)) { set_error("v2p_ctl_rollout_record: clip_obs %g is not > 0", (double)clip_obs); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    if (!obs || !rew || !reset || !terminate || !next_obs_row || !rewards_row || !dones_row || !terminated || !cur_rewards || !cur_lengths || !acc ||
+        (num_sub > 0 && (!sub_rewards || !sub_acc))) {
+        set_error("v2p_ctl_rollout_record: null buffer");
+        return V2P_ERR_INVALID;
+    }
+    return launch_ctl_rollout_record(n, obs_dim, num_sub, clip_obs, obs, rew, reset, terminate, sub_rewards, next_obs_row, rewards_row, dones_row, terminated,
+                                     cur_rewards, cur_lengths, acc, sub_acc, (hipStream_t)stream);
+}
+
+int v2p_ppo_loss(const v2p_ppo_loss_cfg* c, int64_t B, const v2p_ppo_loss_buffers* b, void* stream) {
+    if (!c || !b) { set_error("v2p_ppo_loss: null cfg / buffers"); return V2P_ERR_INVALID; }
+    if (B < 0) { set_error("v2p_ppo_loss: B %lld < 0", (long long)B); return V2P_ERR_INVALID; }
+    if (c->num_actions < 1 || c->num_actions > V2P_CTL_MAX_ACTIONS) {
+        set_error("v2p_ppo_loss: num_actions %d is outside [1, %d]", c->num_actions, V2P_CTL_MAX_ACTIONS);
+        return V2P_ERR_INVALID;
+    }
+    if (c->c0 < 0 || c->c0 > c->c1 || c->c1 > c->num_actions) {
+        set_error("v2p_ppo_loss: columns [%d, %d) are not inside [0, %d]", c->c0, c->c1, c->num_actions);
+        return V2P_ERR_INVALID;
+    }
+    if (!(c->e_clip > 0.0)) { set_error("v2p_ppo_loss: e_clip %g is not > 0", c->e_clip); return V2P_ERR_INVALID; }
+    if (!b->idx && c->dataset_rows < B) { set_error("v2p_ppo_loss: dataset_rows %lld < B %lld without idx", (long long)c->dataset_rows, (long long)B); return V2P_ERR_INVALID; }
+    if (B == 0) return V2P_OK;
+    if (!b->mu || !b->value || !b->old_neglogp || !b->advantages || !b->returns || !b->actions || !b->old_mu || !b->old_sigma || !b->logstd || !b->sigma ||
+        !b->grad_mu || !b->grad_value || !b->stats || !b->partials) {
+        set_error("v2p_ppo_loss: null buffer");
+        return V2P_ERR_INVALID;
+    }
+    return launch_ppo_loss(*c, B, *b, (hipStream_t)stream);
 }
 
 int v2p_ll_policy_actions(const v2p_mvae_target_cfg* c, int64_t n, int32_t sides, float clip_actions, const float* mu, const v2p_mvae_target_buffers* b,

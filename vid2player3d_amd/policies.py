@@ -18,7 +18,7 @@ the tests; the product never calls them.  There is no CPU path for the policies:
 
 Checkpoints: the caller loads the file (`torch.load`) and hands over the dict, as `mvae.weights_from_state_dict` has it; no class of the
 reference is unpickled.  Built: the shipped option set - ReLU MLPs, no mu activation, fixed sigma, no CNN, no RNN.  Anything else raises.
-Not built: critics, sampling, `neglogp`, `vid2player_dual_v2`.
+Critics, sampling, `neglogp` and the controller's PPO agent for these networks: `ctl_ppo.py`.  Not built: `vid2player_dual_v2`.
 """
 import ctypes as C
 import math
