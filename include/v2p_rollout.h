@@ -413,6 +413,9 @@ int v2p_env_post_physics(v2p_env* e, void* stream);                   /* humanoi
  * teacher-forced replay): pushes the caller-edited root_states/dof_state (and rb_state when
  * `with_rb_state`) buffers into the engine's internal structure-of-arrays state. */
 int v2p_env_push_state(v2p_env* e, const int64_t* env_ids, int64_t n, int with_rb_state, void* stream);
+/* v2p_env_push_state for every env of the batch whose flags[env] is not 0 (device, [N]; only read), indexed by env: no id list.  The
+ * engine's state of every other env keeps every bit.  Refused before any HIP call (V2P_ERR_INVALID): a null batch or null flags. */
+int v2p_env_push_state_flagged(v2p_env* e, const int64_t* flags /*[N]*/, int with_rb_state, void* stream);
 
 /* Two schedules of the same physics model are built: 0 = one LINK per lane (default: 32 lanes per env, state in
  * registers, level-synchronous tree recursions), 1 = one ENV per lane (LDS-resident workspace).  They agree to float32
@@ -827,6 +830,25 @@ int v2p_mvae_step(const v2p_mvae_cfg* cfg, int64_t n, const v2p_mvae_weights* we
 int v2p_mvae_reset(const v2p_mvae_cfg* cfg, int64_t num_envs, const v2p_mvae_weights* weights, const v2p_mvae_buffers* buffers, const int64_t* env_ids,
                    int64_t n_ids, const float* init_feature /*[n_ids,288]*/, const float* root_xy /*[n_ids,2]*/, const float* joint_pos_bind_rel /*[24,3]*/,
                    void* stream);
+/* Where the start of a reset env comes from when v2p_mvae_reset_flagged is given no root_xy (`draw_root_xy`, mvae_player.py:230-236):
+ * V2P_MVAE_ROOT_CENTRE is (0, -13), the branch taken when not training with a test_mode other than `random`; V2P_MVAE_ROOT_DRAW is the
+ * kernel's own draw near it, in float32 with every operation rounded on its own: x = (u0 - 0.5) * 2 + 0, y = (u1 - 0.5) * 1.5 + (-13),
+ * u = (word >> 8) * 2^-24 of words 0 and 1 of Philox4x32-10 block 0 of stream 2 (csrc/philox.hpp PHILOX_STREAM_ROOT) under
+ * (seed, call, env): a draw depends on those three alone, never on which other envs are flagged.  `call` is the host's count of launches. */
+enum { V2P_MVAE_ROOT_CENTRE = 0, V2P_MVAE_ROOT_DRAW = 1 };
+typedef struct {
+    int32_t rule;            /* V2P_MVAE_ROOT_* */
+    uint64_t seed, call;
+} v2p_mvae_root_rule;
+/* v2p_mvae_reset for every env e of 0 .. num_envs-1 whose flags[e] is not 0 (device, [num_envs]; any non-zero value counts), in ONE
+ * launch over all envs: no id list, no host read.  init_feature is [num_envs,288] and row e belongs to env e (the player's initial
+ * frames read in place, without a gather); root_xy [num_envs,2] is nullable: where given, row e is env e's start, where null the start
+ * follows `rule` (required then).  Rows of envs whose flag is 0 keep every bit; the flags are only read.  Equal, bit for bit, to
+ * v2p_mvae_reset with env_ids = the flagged envs, ascending, and the gathered rows.  Refusals as v2p_mvae_reset, and: null flags /
+ * init_feature / joint_pos_bind_rel, num_envs above 2^31-1, no root_xy and no rule, an unknown rule.  num_envs = 0 is a no-op. */
+int v2p_mvae_reset_flagged(const v2p_mvae_cfg* cfg, int64_t num_envs, const v2p_mvae_weights* weights, const v2p_mvae_buffers* buffers, const int64_t* flags /*[N]*/,
+                           const float* init_feature /*[N,288]*/, const float* root_xy /*[N,2], nullable*/, const v2p_mvae_root_rule* rule /*nullable with root_xy*/,
+                           const float* joint_pos_bind_rel /*[24,3]*/, void* stream);
 
 /* ---- the motion generator of a two-player batch (`MVAEPlayer` with cfg `dual_mode: different`, mvae_player.py:23-57, 167-199): env 2k
  * is side 0 and env 2k+1 side 1; each side has its own decoder weights, normalisation statistics, playing hand and player rule, the
@@ -909,6 +931,12 @@ int v2p_mvae_target_step(const v2p_mvae_target_cfg* cfg, int64_t n, const v2p_mv
  * rb_state (v2p_env_push_state with_rb_state = 1 then puts the humanoid there).  Rows of other envs are not touched.  Refusals as the step. */
 int v2p_mvae_target_reset(const v2p_mvae_target_cfg* cfg, int64_t num_envs, const v2p_mvae_target_buffers* buffers, const int64_t* env_ids, int64_t n_ids,
                           void* stream);
+/* v2p_mvae_target_reset for every env e of 0 .. num_envs-1 whose flags[e] is not 0 (device, [num_envs]; only read), in ONE launch over
+ * all envs: the flagged envs' rows of `target` (the buffer the caller names: the previous target) and, where given, of root_states,
+ * dof_state and rb_state; every other row keeps every bit.  Equal, bit for bit, to v2p_mvae_target_reset with env_ids = the flagged
+ * envs.  Refusals as v2p_mvae_target_reset, and null flags.  num_envs = 0 is a no-op. */
+int v2p_mvae_target_reset_flagged(const v2p_mvae_target_cfg* cfg, int64_t num_envs, const v2p_mvae_target_buffers* buffers, const int64_t* flags /*[N]*/,
+                                  void* stream);
 /* `_action_to_pd_targets` (:693-703) before its clamp, for envs 0 .. n-1: actions_out[:, :69] = base + (no_scale_action ? 1 :
  * pd_action_scale[c]) * actions_in[:, :69], base = target's dof_pos / dof_state's dof_pos / pd_action_offset by pd_target_base; columns
  * 69..74 are copied.  The clamp to dof_pos +- pi/2 (:705-707) is the engine's pre-physics clamp with pd_tar_lim = pi/2.  actions_out may
@@ -1000,6 +1028,25 @@ int v2p_ctl_rollout_record(int64_t n, int64_t obs_dim, int32_t num_sub, float cl
                            const int64_t* terminate, const float* sub_rewards, float* next_obs_row /*[n,obs_dim]*/, float* rewards_row /*[n]*/,
                            float* dones_row /*[n]*/, float* terminated /*[n]*/, float* cur_rewards /*[n] in/out*/, float* cur_lengths /*[n] in/out*/,
                            double* acc /*[4] in/out*/, double* sub_acc /*[num_sub] in/out*/, void* stream);
+/* The controller's own bookkeeping around a reset by flags (`PhysicsMVAEController._reset_envs`, physics_mvae_controller.py:167-199):
+ * flags [n] int64 is the controller's `reset_buf`, any non-zero value means "reset this env"; rows of envs whose flag is 0 keep every
+ * bit.  v2p_ctl_reset_begin, for the flagged envs: progress = 0, terminate = 0, num_reset_reaction = 0, distance = 0, num_reset += 1.
+ * v2p_ctl_reset_end, for the flagged envs: reset_reaction = 0 and reset_recovery = 0, then flags[e] = 0 - the mask is the buffer that
+ * is cleared, so it goes last.  Between the two stand v2p_mvae_reset_flagged, v2p_mvae_target_reset_flagged,
+ * v2p_env_push_state_flagged and v2p_tennis_task_reset (by its own two flags): one fixed sequence of launches, whatever the number of
+ * flagged envs, with no host read of a device result.  Refused before any HIP call (V2P_ERR_INVALID, a message that names the call):
+ * n < 0, null flags or buffers, a null pointer among the buffers the call writes.  n = 0 is a no-op. */
+typedef struct {                    /* DEVICE buffers of the controller */
+    int64_t* progress;              /* [n] begin */
+    int64_t* terminate;             /* [n] begin */
+    int64_t* num_reset_reaction;    /* [n] begin */
+    int64_t* num_reset;             /* [n] begin */
+    float* distance;                /* [n] begin */
+    uint8_t* reset_reaction;        /* [n] end */
+    uint8_t* reset_recovery;        /* [n] end */
+} v2p_ctl_reset_buffers;
+int v2p_ctl_reset_begin(int64_t n, const int64_t* flags /*[n]*/, const v2p_ctl_reset_buffers* buffers, void* stream);
+int v2p_ctl_reset_end(int64_t n, int64_t* flags /*[n], cleared*/, const v2p_ctl_reset_buffers* buffers, void* stream);
 /* The loss head of V2PAgent.calc_gradients (v2p_agent.py:329-362, 395-397; learning/common_agent.py:442-450, 491-520 with clip_value
  * False; PhysicsMVAEController.get_aux_losses) under a fixed sigma, forward and backward.  With row r of the minibatch and
  * j = idx ? idx[r] : r its row of the epoch's dataset:

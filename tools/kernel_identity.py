@@ -15,13 +15,15 @@ too; the range is a few numbers wide.)
 The kernels of tennis_task.hip are known too (tennis_task_kernel<STEP, DUAL>, tennis_handover_kernel), and those of mvae_player.hip
 (mvae_step_kernel, mvae_reset_kernel and their mvae_dual_* forms; they live in an anonymous namespace, which the symbol pattern allows),
 and those of mvae_target.hip (mvae_target_kernel<RESET>, mvae_target_actions_kernel), tennis_reset.hip (tennis_reset_kernel) and
-controller_actions.hip (controller_actions_kernel).  A kernel that only the new listing has is
+controller_actions.hip (controller_actions_kernel), and the reset by flags (mvae_reset_flagged_kernel of mvae_player_flagged.hip;
+mvae_target_reset_flagged_kernel, env_push_state_flagged_kernel, ctl_reset_begin_kernel / _end_kernel of flag_reset.hip, next to
+env_push_state_kernel of task_ops.hip).  A kernel that only the new listing has is
 reported and does not count as a difference; one that only the old listing has does.
 usage: tools/kernel_identity.py <old.s>[,<old2.s>...] <new.s>[,<new2.s>...]   (a kernel is looked up in every listing of its side)"""
 import re
 import sys
 
-KERNELS = re.compile(r"^(_ZN\w*?(physics_ll_kernelI\w+?EEv|env_pre_kernelE|pair_scatter_kernelE|tennis_task_kernelI\w+?EEv|tennis_handover_kernelE|mvae_(?:dual_)?(?:step|reset)_kernelE|mvae_target_kernelI\w+?EEv|mvae_target_actions_kernelE|tennis_reset_kernelE|controller_actions_kernelE)\w*):")
+KERNELS = re.compile(r"^(_ZN\w*?(physics_ll_kernelI\w+?EEv|env_pre_kernelE|pair_scatter_kernelE|tennis_task_kernelI\w+?EEv|tennis_handover_kernelE|mvae_(?:dual_)?(?:step|reset)_kernelE|mvae_target_kernelI\w+?EEv|mvae_target_actions_kernelE|tennis_reset_kernelE|controller_actions_kernelE|mvae_reset_flagged_kernelE|mvae_target_reset_flagged_kernelE|env_push_state(?:_flagged)?_kernelE|ctl_reset_(?:begin|end)_kernelE)\w*):")
 # the enclosing namespaces: v2p, v2p::ll_lds, v2p::ll_regs, or v2p itself renamed with a suffix (how the register object was built
 # before the kernel had a namespace per build): _ZN3v2p17..., _ZN3v2p6ll_lds17..., _ZN3v2p7ll_regs17... -> _ZN@17...
 NAMESPACES = re.compile(r"_ZN\d+v2p(?:_[a-z]+)?(?:\d+ll_[a-z]+)?")

@@ -168,6 +168,22 @@ class MvaeBuffers(C.Structure):
     _fields_ = [(k, vp) for k in MVAE_BUFFER_NAMES]
 
 
+MVAE_ROOT_RULES = {"centre": 0, "draw": 1}  # V2P_MVAE_ROOT_*
+
+
+class MvaeRootRule(C.Structure):
+    """v2p_mvae_root_rule: where v2p_mvae_reset_flagged takes the start of a reset env from when no table is given."""
+    _fields_ = [("rule", C.c_int32), ("seed", C.c_uint64), ("call", C.c_uint64)]
+
+
+CTL_RESET_BUFFER_NAMES = ("progress", "terminate", "num_reset_reaction", "num_reset", "distance", "reset_reaction", "reset_recovery")
+
+
+class CtlResetBuffers(C.Structure):
+    """v2p_ctl_reset_buffers: the controller's bookkeeping around a reset by flags (v2p_ctl_reset_begin / _end)."""
+    _fields_ = [(k, vp) for k in CTL_RESET_BUFFER_NAMES]
+
+
 class MvaeRacket(C.Structure):
     """v2p_mvae_racket: the one racket object of a two-player batch (v2p_mvae_dual_reset)."""
     _fields_ = [("righthand", C.c_int32), ("dir", C.c_float * 3), ("normal", C.c_float * 3)]
@@ -282,6 +298,7 @@ def load():
         "v2p_env_export": [vp, vp],
         "v2p_env_post_physics": [vp, vp],
         "v2p_env_push_state": [vp, vp, C.c_int64, C.c_int, vp],
+        "v2p_env_push_state_flagged": [vp, vp, C.c_int, vp],
         "v2p_env_target_index": [vp],
         "v2p_env_kernel_build": [vp],
         "v2p_env_set_schedule": [vp, C.c_int],
@@ -303,10 +320,14 @@ def load():
         "v2p_controller_actions": [C.POINTER(ControllerActionsCfg), C.c_int64, C.POINTER(ControllerActionsBuffers), vp],
         "v2p_mvae_step": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, vp, vp],
         "v2p_mvae_reset": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, C.c_int64, vp, vp, vp, vp],
+        "v2p_mvae_reset_flagged": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, vp, vp, C.POINTER(MvaeRootRule), vp, vp],
         "v2p_mvae_dual_step": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), vp, vp, C.c_int32, vp],
         "v2p_mvae_dual_reset": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), C.POINTER(MvaeRacket), vp, C.c_int64, vp, vp, vp, C.c_int64, vp],
         "v2p_mvae_target_step": [C.POINTER(MvaeTargetCfg), C.c_int64, C.POINTER(MvaeTargetBuffers), vp],
         "v2p_mvae_target_reset": [C.POINTER(MvaeTargetCfg), C.c_int64, C.POINTER(MvaeTargetBuffers), vp, C.c_int64, vp],
+        "v2p_mvae_target_reset_flagged": [C.POINTER(MvaeTargetCfg), C.c_int64, C.POINTER(MvaeTargetBuffers), vp, vp],
+        "v2p_ctl_reset_begin": [C.c_int64, vp, C.POINTER(CtlResetBuffers), vp],
+        "v2p_ctl_reset_end": [C.c_int64, vp, C.POINTER(CtlResetBuffers), vp],
         "v2p_mvae_target_actions": [C.POINTER(MvaeTargetCfg), C.c_int64, vp, C.POINTER(MvaeTargetBuffers), vp, vp],
         "v2p_policy_input": [C.POINTER(PolicyInputCfg), C.c_int64, C.c_int64, vp, vp, vp],
         "v2p_ll_policy_input": [C.POINTER(PolicyInputCfg), C.c_int64, C.c_int64, C.POINTER(LLPolicySrc), vp, vp, vp],
@@ -338,6 +359,7 @@ EXPORTED_SYMBOLS = (
     "v2p_obs_imitation", "v2p_obs_imitation_packed", "v2p_policy_head", "v2p_policy_head_record", "v2p_obs_imitation_packed_w", "v2p_policy_head_w", "v2p_policy_head_record_w", "v2p_gae", "v2p_value_record", "v2p_rollout_record", "v2p_motion_tables_build", "v2p_shapes_compile", "v2p_env_create", "v2p_env_create_shapes", "v2p_env_destroy", "v2p_env_reset", "v2p_env_context", "v2p_env_set_context_transform", "v2p_env_step", "v2p_env_pre_physics", "v2p_env_physics", "v2p_env_export",
     "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_tennis_dual_step", "v2p_tennis_dual_handover", "v2p_controller_actions", "v2p_tennis_task_reset", "v2p_mvae_step", "v2p_mvae_reset", "v2p_mvae_dual_step", "v2p_mvae_dual_reset", "v2p_mvae_target_step", "v2p_mvae_target_reset", "v2p_mvae_target_actions", "v2p_policy_input", "v2p_ll_policy_input", "v2p_ll_policy_actions", "v2p_ctl_policy_head", "v2p_ctl_rollout_record", "v2p_ppo_loss", "v2p_last_error", "v2p_abi_version",
     "v2p_debug_guards", "v2p_debug_guards_selftest", "v2p_env_guard_counts",
+    "v2p_mvae_reset_flagged", "v2p_mvae_target_reset_flagged", "v2p_env_push_state_flagged", "v2p_ctl_reset_begin", "v2p_ctl_reset_end",
 )
 
 

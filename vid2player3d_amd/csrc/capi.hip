@@ -9,6 +9,7 @@
 
 #include "controller_actions.hpp"
 #include "ctl_ppo.hpp"
+#include "flag_reset.hpp"
 #include "mvae_player.hpp"
 #include "mvae_target.hpp"
 #include "policy_io.hpp"
@@ -445,6 +446,20 @@ int v2p_mvae_reset(const v2p_mvae_cfg* c, int64_t num_envs, const v2p_mvae_weigh
     return launch_mvae_reset(*c, num_envs, *w, *b, env_ids, n_ids, init_feature, root_xy, joint_pos_bind_rel, (hipStream_t)stream);
 }
 
+int v2p_mvae_reset_flagged(const v2p_mvae_cfg* c, int64_t num_envs, const v2p_mvae_weights* w, const v2p_mvae_buffers* b, const int64_t* flags, const float* init_feature,
+                           const float* root_xy, const v2p_mvae_root_rule* rule, const float* joint_pos_bind_rel, void* stream) {
+    const char* fn = "v2p_mvae_reset_flagged";
+    const int rc = mvae_check(fn, c, num_envs, w, b, false);
+    if (rc != V2P_OK) return rc;
+    if (num_envs > INT32_MAX) { set_error("%s: num_envs %lld above 2^31-1 (the generator's counter holds the env in 32 bits)", fn, (long long)num_envs); return V2P_ERR_INVALID; }
+    if (!flags || !init_feature || !joint_pos_bind_rel) { set_error("%s: null flags / init_feature / joint_pos_bind_rel", fn); return V2P_ERR_INVALID; }
+    if (!root_xy && !rule) { set_error("%s: neither root_xy nor a rule for the start", fn); return V2P_ERR_INVALID; }
+    if (rule && rule->rule != V2P_MVAE_ROOT_CENTRE && rule->rule != V2P_MVAE_ROOT_DRAW) { set_error("%s: unknown root rule %d", fn, rule->rule); return V2P_ERR_INVALID; }
+    if (num_envs == 0) return V2P_OK;
+    const v2p_mvae_root_rule none = {V2P_MVAE_ROOT_CENTRE, 0, 0};
+    return launch_mvae_reset_flagged(*c, num_envs, *w, *b, flags, init_feature, root_xy, rule ? *rule : none, joint_pos_bind_rel, (hipStream_t)stream);
+}
+
 // what both two-player entry points refuse: each side's own refusals, and sides that disagree on what the batch shares
 static int mvae_dual_check(const char* fn, const v2p_mvae_cfg* c, int64_t n, const v2p_mvae_weights* w, const v2p_mvae_buffers* b, bool step) {
     if (!c || !w || !b) { set_error("%s: null cfg / weights / buffers", fn); return V2P_ERR_INVALID; }
@@ -539,6 +554,37 @@ int v2p_mvae_target_reset(const v2p_mvae_target_cfg* c, int64_t num_envs, const 
     if (n_ids > 0 && !env_ids) { set_error("v2p_mvae_target_reset: null env_ids"); return V2P_ERR_INVALID; }
     if (n_ids == 0 || num_envs == 0) return V2P_OK;
     return launch_mvae_target_reset(*c, num_envs, *b, env_ids, n_ids, (hipStream_t)stream);
+}
+
+int v2p_mvae_target_reset_flagged(const v2p_mvae_target_cfg* c, int64_t num_envs, const v2p_mvae_target_buffers* b, const int64_t* flags, void* stream) {
+    const char* fn = "v2p_mvae_target_reset_flagged";
+    const int rc = mvae_target_check(fn, c, num_envs, b);
+    if (rc != V2P_OK) return rc;
+    if (!b->root_pos || !b->joint_rotmat || !b->joint_pos_bind || !b->target) { set_error("%s: null root_pos / joint_rotmat / joint_pos_bind / target", fn); return V2P_ERR_INVALID; }
+    if (!flags) { set_error("%s: null flags", fn); return V2P_ERR_INVALID; }
+    if (num_envs == 0) return V2P_OK;
+    return launch_mvae_target_reset_flagged(*c, num_envs, *b, flags, (hipStream_t)stream);
+}
+
+// what the two bookkeeping entry points of the reset by flags refuse; `begin`: which of the buffers the call writes
+static int ctl_reset_check(const char* fn, int64_t n, const int64_t* flags, const v2p_ctl_reset_buffers* b, bool begin) {
+    if (n < 0) { set_error("%s: n %lld < 0", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (!flags || !b) { set_error("%s: null flags / buffers", fn); return V2P_ERR_INVALID; }
+    const bool ok = begin ? (b->progress && b->terminate && b->num_reset_reaction && b->num_reset && b->distance) : (b->reset_reaction && b->reset_recovery);
+    if (!ok) { set_error(begin ? "%s: null progress / terminate / num_reset_reaction / num_reset / distance" : "%s: null reset_reaction / reset_recovery", fn); return V2P_ERR_INVALID; }
+    return V2P_OK;
+}
+
+int v2p_ctl_reset_begin(int64_t n, const int64_t* flags, const v2p_ctl_reset_buffers* b, void* stream) {
+    const int rc = ctl_reset_check("v2p_ctl_reset_begin", n, flags, b, true);
+    if (rc != V2P_OK || n == 0) return rc;
+    return launch_ctl_reset_begin(n, flags, *b, (hipStream_t)stream);
+}
+
+int v2p_ctl_reset_end(int64_t n, int64_t* flags, const v2p_ctl_reset_buffers* b, void* stream) {
+    const int rc = ctl_reset_check("v2p_ctl_reset_end", n, flags, b, false);
+    if (rc != V2P_OK || n == 0) return rc;
+    return launch_ctl_reset_end(n, flags, *b, (hipStream_t)stream);
 }
 
 int v2p_mvae_target_actions(const v2p_mvae_target_cfg* c, int64_t n, const float* actions_in, const v2p_mvae_target_buffers* b, float* actions_out, void* stream) {
@@ -786,6 +832,12 @@ int v2p_env_push_state(v2p_env* e, const int64_t* env_ids, int64_t n, int with_r
     if (!e || n < 0 || n > e->n) { set_error("v2p_env_push_state: bad argument"); return V2P_ERR_INVALID; }
     DeviceGuard g(e->device);
     return launch_env_push_state(e, env_ids, env_ids ? n : e->n, with_rb_state, (hipStream_t)stream);
+}
+
+int v2p_env_push_state_flagged(v2p_env* e, const int64_t* flags, int /*with_rb_state*/, void* stream) {
+    if (!e || !flags) { set_error("v2p_env_push_state_flagged: null batch / flags"); return V2P_ERR_INVALID; }
+    DeviceGuard g(e->device);
+    return launch_env_push_state_flagged(e, flags, (hipStream_t)stream);
 }
 
 int v2p_env_set_schedule(v2p_env* e, int schedule) {

@@ -32,7 +32,10 @@ HOW it is done here, none of it a difference in WHAT:
     (over all rows: a pass over a few rows is another GEMM shape and rounds differently in the last bit), which gives `values[n + 1]`;
     a step without such an env skips the second pass.  `reuse_next_values =
     False` runs the reference's two full passes; both fill `values` / `next_values` with the same numbers (tested),
-  * the list of done envs is obtained as the reference obtains it, `dones.nonzero()`; it comes back with the flags of the rows the reset can rewrite in the ONE host read per rollout step that is kept,
+  * the list of done envs is obtained as the reference obtains it, `dones.nonzero()`; it comes back with the flags of the rows the reset can rewrite in the ONE host read per rollout step that is kept
+    (`reset_mode = 'ids'`, the default).  `reset_mode = 'flags'` resets the done envs by `reset_buf` on the device instead
+    (`TennisControllerTask.reset_by_flags`: one fixed sequence of launches per step, no host read, no id list); the host then does not
+    know whether a row changed, so the second critic pass runs at every step but the last - the same numbers, bit for bit (tested),
   * the epoch's action noise is one `torch.randn` draw from the agent's generator (`noise_fn` for tests), GAE is `v2p_gae`,
   * the loss head of calc_gradients is one kernel, forward and backward (`v2p_ppo_loss` behind a `torch.autograd.Function`): it reads the
     epoch's dataset THROUGH the minibatch's frame indices, so only the observation rows are gathered.  `fused_loss = False` runs the
@@ -46,8 +49,7 @@ tests/test_gpu_ctl_ppo.py.
 
 Not built (each refused by name where a config asks for it): the two-player agent (`V2PBuilderDual`, `vid2player_dual_v2`, a sigma per
 side), data parallel over ranks (`multi_gpu`), mixed precision, a learned sigma, `clip_value`, a learning-rate schedule, a network with an
-inner normaliser (`use_running_obs`), the reset of done envs without the host read (a reset by mask through the task, the generator, the
-target and the engine's push: task-side entries, a later change), a fused or reduced-precision MLP, `train()`'s `_best` checkpoint and its
+inner normaliser (`use_running_obs`), a fused or reduced-precision MLP, `train()`'s `_best` checkpoint and its
 `_latest` save every `save_best_after` epochs, the window of past episodes behind `eps_len` and the mean reward, the observer's logging.
 """
 import ctypes as C
@@ -447,12 +449,22 @@ class ControllerPPOAgent:
     def __init__(self, ctl, horizon_length=32, gamma=0.99, tau=0.95, learning_rate=1e-5, e_clip=0.2, critic_coef=5.0, mini_epochs=3, minibatch_size=16384,
                  grad_norm=50.0, truncate_grads=True, entropy_coef=0.0, bounds_loss_coef=10.0, normalize_value=True, normalize_advantage=True,
                  clip_obs=math.inf, clip_actions=math.inf, units=(1024, 1024, 512), sigma_init=-2.9, discard_pretrained_sigma=False, seed=0,
-                 dof_res_weight=None, reuse_next_values=True, fused_loss=True):
+                 dof_res_weight=None, reuse_next_values=True, fused_loss=True, reset_mode="ids"):
+        # reset_mode 'ids' (default): the done envs are read back once per step and reset from their id list; 'flags': the controller
+        # resets them by `reset_buf` on the device (`reset_by_flags`), and the rollout step has no host read
+        if reset_mode not in ("ids", "flags"):
+            raise ValueError("ControllerPPOAgent: reset_mode %r is neither 'ids' nor 'flags'" % (reset_mode,))
+        if reset_mode == "flags" and getattr(getattr(ctl, "task", None), "racket_players", None) is not None:
+            raise NotImplementedError("ControllerPPOAgent: reset_mode 'flags' over a two-player controller is not built (resetting finished pairs by mask)")
+        if reset_mode == "flags" and not callable(getattr(ctl, "reset_by_flags", None)):
+            raise NotImplementedError("ControllerPPOAgent: reset_mode 'flags' needs a controller with reset_by_flags (TennisControllerTask with cfg v2p.task_reset "
+                                      "'device'); %s has none" % type(ctl).__name__)
         dev = torch.device(ctl.device)
         if dev.type != "cuda":
             raise RuntimeError("ControllerPPOAgent: the controller must live on a GPU (no CPU fallback)")
         if getattr(getattr(ctl, "task", None), "racket_players", None) is not None:
             raise NotImplementedError("ControllerPPOAgent: the two-player agent is not built")
+        self.reset_mode = reset_mode
         if entropy_coef != 0.0:
             raise NotImplementedError("ControllerPPOAgent: entropy_coef != 0 is not built (the entropy is a constant under the fixed sigma; all configs use 0)")
         self._lib = _lib.load()
@@ -673,14 +685,19 @@ class ControllerPPOAgent:
             self._policy_input(td["next_obses"][n], self.x)
             last = n + 1 == T
             self._value_record(self.model.critic(self.x), self.terminated, None if last or not self.reuse_next_values else td["values"][n + 1], td["next_values"][n])
-            done_ids, changed_ids = self._reset_lists(td["dones"][n])  # the ONE host read of the step (:259)
-            self._env_reset(done_ids)  # (:280)
+            if self.reset_mode == "flags":
+                ctl.reset_by_flags()  # (:280, by `reset_buf` on the device: no host read, one fixed sequence of launches)
+                changed = True  # (the host does not know whether a row changed: the second critic pass always runs, the same numbers)
+            else:
+                done_ids, changed_ids = self._reset_lists(td["dones"][n])  # the ONE host read of the step (:259)
+                self._env_reset(done_ids)  # (:280)
+                changed = changed_ids.numel() > 0
             if last:
                 break
             torch.clamp(ctl.obs_buf, -c, c, out=td["obses"][n + 1])
             # the reset rewrites observations: the actor of step n + 1 reads the new rows (one launch over all rows) ...
             self._policy_input(td["obses"][n + 1], self.x)
-            if self.reuse_next_values and changed_ids.numel() > 0:
+            if self.reuse_next_values and changed:
                 # ... and where the reset rewrote any row the critic runs again, over ALL rows: a pass over the changed rows alone is another
                 # GEMM shape, which rounds the same row differently in the last bit (measured: 113 of 1024 values at 64 envs)
                 self._value_record(self.model.critic(self.x), None, td["values"][n + 1], None)

@@ -13,7 +13,8 @@ import math
 
 import numpy as np
 
-STREAM_WALK, STREAM_RESET = 0, 1
+STREAM_WALK, STREAM_RESET, STREAM_ROOT = 0, 1, 2
+ROOT_XY_SCALE, ROOT_XY_OFFSET = (2.0, 1.5), (0.0, -13.0)  # `draw_root_xy` (mvae_player.py:230-236): the start of a reset player near the baseline's centre
 WHOLE_CALL = 0xFFFFFFFF
 M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 LARGEST_NORMAL = math.sqrt(48.0 * math.log(2.0))  # u1 = 2^-24: 5.768
@@ -77,3 +78,12 @@ def normals(words, dt=np.float32):
 def clamped_normals(words, bound, dt=np.float32):
     """torch.clamp(normals, -bound, bound)"""
     return np.clip(normals(words, dt), dt(-bound), dt(bound))
+
+
+def root_xy_reference(seed, call, n, envs=None):
+    """The start [n,2] float32 that `v2p_mvae_reset_flagged` draws for envs 0 .. n-1 (or `envs`) in call `call` under `seed`:
+    x = (u0 - 0.5) * 2 + 0, y = (u1 - 0.5) * 1.5 + (-13) in float32, every operation rounded on its own, u0 and u1 the uniforms of words 0
+    and 1 of block 0 of STREAM_ROOT.  A draw depends on (seed, call, env) alone."""
+    f = np.float32
+    u = uniform(philox_words(seed, call, STREAM_ROOT, n, 1, envs)[:, :2])
+    return ((u - f(0.5)) * np.array(ROOT_XY_SCALE, f) + np.array(ROOT_XY_OFFSET, f)).astype(f)

@@ -294,6 +294,13 @@ def mvae_reset_reference(st, avg, std, s, env_ids, init_feature, root_xy, joint_
     return o
 
 
+def mvae_reset_flagged_reference(st, avg, std, s, flags, init_feature, root_xy, joint_pos_bind_rel, dt=np.float32, probes=None):
+    """`v2p_mvae_reset_flagged` on arrays: mvae_reset_reference over the envs whose flag is not 0.  init_feature [N,288] and root_xy [N,2]
+    hold a row per ENV (root_xy: the caller's table, or `device_rng.root_xy_reference(seed, call, N)`, or the centre)."""
+    ids = np.flatnonzero(np.asarray(flags))
+    return mvae_reset_reference(st, avg, std, s, ids, np.asarray(init_feature)[ids], np.asarray(root_xy)[ids], joint_pos_bind_rel, dt, probes)
+
+
 def mvae_dual_step_reference(st, w, avg, std, s, latents, residual=None, dt=np.float32, probes=None):
     """`MVAEPlayer.step` under `_is_dual` (mvae_player.py:191-199) on arrays: mvae_step_reference of side 0 on the even rows and of side 1
     on the odd rows - st: player_settings(...) of `dual_mode: different`; w, avg, std: pairs - and then the reference's quirk: its non-init
@@ -411,6 +418,10 @@ class MotionVAEPlayer:
         self._swing_type = torch.full((n,), -1, **i64)
         self._swing_type_cycle = self._swing_type.clone()
         self._latents = None
+        # the key of the kernel's own draw (`reset_flagged` without a table) and the count of its launches: host numbers, never read
+        # back from the device
+        self.seed = int(self.cfg.get("seed", 0)) & (2 ** 64 - 1)
+        self._reset_calls = 0
 
     def _buffers(self):
         # (built per call: `_swing_type_cycle` may have become another task's tensor, TennisControllerTask.attach_motion_generator)
@@ -437,6 +448,34 @@ class MotionVAEPlayer:
         if ids.numel() == 0:
             return
         self._reset_rows(ids, self._init_data[ids.clamp(0, self.num_envs - 1)].contiguous(), root_xy)
+
+    def root_rule(self):
+        """'draw' or 'centre': the branch `draw_root_xy` takes, as `reset_flagged` hands it to the kernel."""
+        return "draw" if self._is_train or self.cfg.get("test_mode", "random") == "random" else "centre"
+
+    def reset_flagged(self, flags, root_xy=None):
+        """`reset(env_ids)` for the envs whose flag ([N] int64 on the device, non-zero = reset) is up, in one launch over all envs
+        (`v2p_mvae_reset_flagged`): no id list, no gather of `_init_data`, no host read.  root_xy [N,2] (row e: env e's start) stands in
+        for the draw; without it the kernel draws the start itself (`root_rule()`: or takes the centre) from (seed, call, env) - cfg
+        `seed`, and the count of such launches - as `device_rng.root_xy_reference` states it."""
+        if self._is_dual or self.cfg.get("dual_mode"):
+            raise NotImplementedError("MotionVAEPlayer.reset_flagged: the reset by flags is not built with dual_mode (pairs are reset by reset_dual, from an id list)")
+        n = self.num_envs
+        if not torch.is_tensor(flags) or flags.dtype != torch.int64 or flags.device != self.device or not flags.is_contiguous() or flags.numel() != n:
+            raise RuntimeError("MotionVAEPlayer.reset_flagged: flags must be a contiguous int64 tensor [%d] on %s" % (n, self.device))
+        xy, rule = None, None
+        if root_xy is not None:
+            xy = root_xy
+            if not torch.is_tensor(xy) or xy.dtype != torch.float32 or xy.device != self.device or not xy.is_contiguous() or tuple(xy.shape) != (n, 2):
+                raise RuntimeError("MotionVAEPlayer.reset_flagged: root_xy must be a contiguous float32 tensor [%d, 2] on %s" % (n, self.device))
+        else:
+            rule = _lib.MvaeRootRule(rule=_lib.MVAE_ROOT_RULES[self.root_rule()], seed=self.seed, call=self._reset_calls & (2 ** 64 - 1))
+            self._reset_calls += 1
+        b = self._buffers()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().v2p_mvae_reset_flagged(C.byref(self._cfg_struct), n, C.byref(self._weights_struct), C.byref(b), _lib.ptr(flags), _lib.ptr(self._init_data),
+                                                          _lib.ptr(xy), None if rule is None else C.byref(rule), _lib.ptr(self._joint_pos_bind_rel),
+                                                          _lib.current_stream(self.device)), "v2p_mvae_reset_flagged")
 
     def reset_dual(self, reset_reaction_env_ids, reset_recovery_env_ids, root_xy=None):
         """`reset_dual` (mvae_player.py:167-182) with `dual_mode: True` or 'different': the envs of both lists, in ascending order, start from the ready

@@ -113,6 +113,17 @@ def launch_reset(st, tensors, num_envs, env_ids, num_shapes=1):
                    "v2p_mvae_target_reset")
 
 
+def launch_reset_flagged(st, tensors, num_envs, flags, num_shapes=1):
+    """v2p_mvae_target_reset_flagged: the reset of the envs whose flag ([num_envs] int64, non-zero) is up, one launch over all envs."""
+    dev = tensors["target"].device
+    if flags.dtype != torch.int64 or flags.device != dev or not flags.is_contiguous() or flags.numel() != int(num_envs):
+        raise RuntimeError("imitation target: flags must be a contiguous int64 tensor [%d] on %s" % (num_envs, dev))
+    c, b = cfg_struct(st, num_shapes), buffers_struct(tensors)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().v2p_mvae_target_reset_flagged(C.byref(c), int(num_envs), C.byref(b), _lib.ptr(flags), _lib.current_stream(dev)),
+                   "v2p_mvae_target_reset_flagged")
+
+
 def launch_actions(st, tensors, n, actions_in, actions_out, num_shapes=1):
     dev = actions_in.device
     c, b = cfg_struct(st, num_shapes), buffers_struct(tensors)
@@ -287,6 +298,11 @@ def target_reset_reference(st, s, env_ids, dt=np.float32, probes=None):
     return out
 
 
+def target_reset_flagged_reference(st, s, flags, dt=np.float32, probes=None):
+    """`v2p_mvae_target_reset_flagged` on arrays: target_reset_reference over the envs whose flag is not 0."""
+    return target_reset_reference(st, s, np.flatnonzero(np.asarray(flags)), dt, probes)
+
+
 def target_actions_reference(st, actions, target=None, dof_state=None, pd_action_scale=None, pd_action_offset=None, dt=np.float32, probes=None):
     """`_action_to_pd_targets` (:693-703) before its clamp: [n,75] -> [n,75], columns 69.. copied."""
     a = np.asarray(actions, dtype=dt)
@@ -378,6 +394,13 @@ class ImitationTarget:
         t = self.task
         launch_reset(self.settings, self._tensors(t._target_bufs[1 - t._cur]), self.num_envs, ids, len(self._joint_pos_bind))
         t._reset_env_tensors(ids, with_rb_state=True)
+
+    def reset_flagged(self, flags):
+        """`reset(env_ids)` for the envs whose flag ([N] int64 on the device, non-zero = reset) is up: two launches over all envs
+        (`v2p_mvae_target_reset_flagged`, `v2p_env_push_state_flagged`), no id list and no host read."""
+        t = self.task
+        launch_reset_flagged(self.settings, self._tensors(t._target_bufs[1 - t._cur]), self.num_envs, flags, len(self._joint_pos_bind))
+        t._reset_env_tensors_flagged(flags, with_rb_state=True)
 
     def actions(self, a):
         """`_action_to_pd_targets` before its clamp (the engine's pre-physics clamps): [N,75] -> [N,75] (a buffer of this object)."""

@@ -809,6 +809,12 @@ class HumanoidSMPLIM:
         n = self.num_envs if env_ids is None else env_ids.shape[0]
         _lib.check(self._lib.v2p_env_push_state(self._h_env, _lib.ptr(env_ids), n, int(with_rb_state), self._stream()), "v2p_env_push_state")
 
+    def _reset_env_tensors_flagged(self, flags, with_rb_state=False):
+        """`_reset_env_tensors` for the envs whose flag ([N] int64 on the device, non-zero = push) is up, indexed by env: no id list."""
+        if flags.dtype != torch.int64 or not flags.is_cuda or not flags.is_contiguous() or flags.numel() != self.num_envs:
+            raise RuntimeError("_reset_env_tensors_flagged: flags must be a contiguous int64 GPU tensor [%d]" % self.num_envs)
+        _lib.check(self._lib.v2p_env_push_state_flagged(self._h_env, _lib.ptr(flags), int(with_rb_state), self._stream()), "v2p_env_push_state_flagged")
+
     def set_schedule(self, name):
         """'link_per_lane' (default) or 'env_per_lane': two GPU schedules of the same physics model."""
         kind = {"link_per_lane": 0, "env_per_lane": 1}[name]

@@ -37,6 +37,12 @@ With cfg v2p `task_reset: 'device'` the flag-driven half of `_reset_envs` - ball
 the same generator (stream RESET), with the same departure.  The default `'torch'` is the indexed torch code with torch's own random
 stream, as before.  `'device'` needs the task's ball generator to be a `TennisBallGeneratorOffline` on the task's device.
 
+Under `'device'` the humanoid half runs by flags too: `reset_by_flags()` resets the envs whose `reset_buf` is up - the controller's
+bookkeeping, the generator's initial frame, the target's pose, the engine's push (csrc/flag_reset.hip, csrc/mvae_player_flagged.hip) around
+that launch - as one fixed sequence of six launches over all envs, without an id list or a host read.  `reset(env_ids)` stays as it is
+and is the default of the PPO agent (`reset_mode`).  `_reset_root_xy` [N,2] (default None) gives every env a start that stands in for
+the generator's draw in both.
+
 `task_step_reference` is a numpy statement of the same step on arrays - the checker of the tests, as `ball_traj.resample_reference`
 and `body_shapes` have theirs; the product never calls it.  There is no CPU path: a CPU device or a missing library is a RuntimeError.
 """
@@ -551,6 +557,7 @@ class TennisControllerTask:
             raise ValueError("TennisControllerTask: cfg v2p.task_reset %r is neither 'torch' nor 'device'" % (self._task_reset,))
         self._reset_calls = 0
         self._no_ids = torch.zeros(0, **i64)
+        self._reset_root_xy = None  # [N,2]: a per-env start that stands in for the generator's draw, in `reset(env_ids)` and `reset_by_flags()` alike
         if self._task_reset == "device":
             self._init_device_reset(v2p)
 
@@ -756,7 +763,7 @@ class TennisControllerTask:
         if some:
             self._reset_env_tensors(env_ids, keep_flags=True)
             if self._mvae_player is not None:
-                self._mvae_player.reset(env_ids)
+                self._mvae_player.reset(env_ids, self._root_xy_rows(env_ids))
                 if self._imitation_target is not None:
                     self._imitation_target.reset(env_ids)
             self._num_reset[env_ids] += 1
@@ -769,6 +776,47 @@ class TennisControllerTask:
             self._reset_recovery_buf[env_ids] = False
         self._has_init = True
 
+    def _root_xy_rows(self, env_ids):
+        """the rows of the per-env start table `_reset_root_xy` ([N,2], default None: the generator draws) for env_ids"""
+        return None if self._reset_root_xy is None else self._reset_root_xy[env_ids]
+
+    def _ctl_reset_buffers(self):
+        t = dict(progress=self.progress_buf, terminate=self._terminate_buf, num_reset_reaction=self._num_reset_reaction, num_reset=self._num_reset,
+                 distance=self._distance, reset_reaction=self._reset_reaction_buf, reset_recovery=self._reset_recovery_buf)
+        for k, v in t.items():
+            if not v.is_cuda or not v.is_contiguous() or v.numel() != self.num_envs:
+                raise RuntimeError("TennisControllerTask.reset_by_flags: %s must be a contiguous GPU tensor [%d]" % (k, self.num_envs))
+        return _lib.CtlResetBuffers(**{k: v.data_ptr() for k, v in t.items()})
+
+    def reset_by_flags(self):
+        """`reset(done ids)` for the envs whose `reset_buf` is up, without knowing them on the host: `_reset_envs_device` as ONE fixed
+        sequence of launches over all envs, the same whether 0 or N envs are done - `v2p_ctl_reset_begin` (the bookkeeping),
+        `v2p_mvae_reset_flagged` (the generator), `v2p_mvae_target_reset_flagged` and `v2p_env_push_state_flagged` (the target and the
+        engine), `v2p_tennis_task_reset` (by its own two flags), `v2p_ctl_reset_end` (the two flags of the reset envs, then `reset_buf`).
+        No host read of a device result, no id list, no allocation, no torch op.  `_reset_root_xy` [N,2] stands in for the generator's
+        draw, as in `reset(env_ids)`; without it the generator's kernel draws (`MotionVAEPlayer.reset_flagged`)."""
+        if self._task_reset != "device":
+            raise NotImplementedError("TennisControllerTask.reset_by_flags: the reset by flags needs cfg v2p.task_reset 'device' (a flag form of the "
+                                      "'torch' task reset is not built); got %r" % (self._task_reset,))
+        lib, flags, n = _lib.load(), self.reset_buf, self.num_envs
+        if flags.dtype != torch.int64 or not flags.is_contiguous():
+            raise RuntimeError("TennisControllerTask.reset_by_flags: reset_buf must be a contiguous int64 tensor")
+        b = self._ctl_reset_buffers()
+        stream = lambda: _lib.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.v2p_ctl_reset_begin(n, _lib.ptr(flags), C.byref(b), stream()), "v2p_ctl_reset_begin")
+        if self._mvae_player is not None:
+            self._mvae_player.reset_flagged(flags, self._reset_root_xy)
+            if self._imitation_target is not None:
+                self._imitation_target.reset_flagged(flags)
+        gen = self.task._ball_generator
+        launch_reset(dict(self.settings, **self.reset_settings), self._tensors(), n, self._pool, self._num_reset_reaction,
+                     sample_idx=None if gen.sample_random else gen.sample_idx, call=self._reset_calls)
+        self._reset_calls += 1
+        with torch.cuda.device(self.device):
+            _lib.check(lib.v2p_ctl_reset_end(n, _lib.ptr(flags), C.byref(b), stream()), "v2p_ctl_reset_end")
+        self._has_init = True
+
     def _reset_envs(self, env_ids):
         if self._task_reset == "device":
             return self._reset_envs_device(env_ids)
@@ -778,7 +826,7 @@ class TennisControllerTask:
         if len(env_ids) > 0:
             self._reset_env_tensors(env_ids)
             if self._mvae_player is not None:
-                self._mvae_player.reset(env_ids)  # (:182-183)
+                self._mvae_player.reset(env_ids, self._root_xy_rows(env_ids))  # (:182-183)
                 if self._imitation_target is not None:
                     self._imitation_target.reset(env_ids)  # (`_reset_actors` of the physics player's task, :186)
             self._num_reset[env_ids] += 1

@@ -276,6 +276,9 @@ class DualTennisControllerTask(tc.TennisControllerTask):
         raise ValueError("DualTennisControllerTask: cfg v2p.dual_mode True goes with a single-player racket + ball task, 'different' with a "
                          "two-player one; got dual_mode %r over %s" % (mode, "a two-player task" if players is not None else "a single-player task"))
 
+    def reset_by_flags(self):
+        raise NotImplementedError("DualTennisControllerTask.reset_by_flags: resetting finished pairs by mask is not built (the single-player controller's is)")
+
     def attach_motion_generator(self, player):
         """As `TennisControllerTask.attach_motion_generator`; the player's mode is the task's: one generator for both sides under
         `dual_mode: True`, a weight set per side under 'different'."""
