@@ -879,6 +879,19 @@ int v2p_mvae_dual_step(const v2p_mvae_cfg* cfg /*[2]*/, int64_t n, const v2p_mva
 int v2p_mvae_dual_reset(const v2p_mvae_cfg* cfg /*[2]*/, int64_t num_envs, const v2p_mvae_weights* weights /*[2]*/, const v2p_mvae_buffers* buffers,
                         const v2p_mvae_racket* racket, const int64_t* env_ids, int64_t n_ids, const float* init_feature /*[n_ids,288]*/,
                         const float* root_xy /*[n_ids,2]*/, const float* joint_pos_bind_rel /*[bind_rows,24,3]*/, int64_t bind_rows, void* stream);
+/* v2p_mvae_dual_reset for every env e of 0 .. num_envs-1 (even) whose flags[e] is not 0, in ONE launch over all envs: no id list, no
+ * host read.  The caller raises both flags of a pair (v2p_ctl_pair_reset_begin does).  init_feature is [num_envs,288] and row e belongs
+ * to env e: the caller interleaves the serve and ready frames by parity and serve_from once.  root_xy [num_envs,2] and rule: as
+ * v2p_mvae_reset_flagged (the same stream and law under (seed, call, env)).  joint_pos_bind_rel is ONE [24,3] row: the id-list form
+ * reads the row of a pair's POSITION in the list, which without a list would need a prefix count of the flagged pairs - bind_rows > 1
+ * is refused with V2P_ERR_UNSUPPORTED and a message.  Rows of envs whose flag is 0 keep every bit; the flags are only read.  Equal, bit
+ * for bit, to v2p_mvae_dual_reset with env_ids = the flagged envs, ascending, and the gathered rows.  Refusals as v2p_mvae_dual_reset,
+ * and: an odd num_envs or one above 2^31-1, null flags / init_feature / joint_pos_bind_rel, no root_xy and no rule, an unknown rule,
+ * bind_rows < 1.  num_envs = 0 is a no-op. */
+int v2p_mvae_dual_reset_flagged(const v2p_mvae_cfg* cfg /*[2]*/, int64_t num_envs, const v2p_mvae_weights* weights /*[2]*/, const v2p_mvae_buffers* buffers,
+                                const v2p_mvae_racket* racket, const int64_t* flags /*[N]*/, const float* init_feature /*[N,288]*/,
+                                const float* root_xy /*[N,2], nullable*/, const v2p_mvae_root_rule* rule /*nullable with root_xy*/,
+                                const float* joint_pos_bind_rel /*[bind_rows,24,3]*/, int64_t bind_rows, void* stream);
 
 /* ---- the imitation target from the motion generator's pose (vid2player/env/tasks/humanoid_smpl_im_mvae.py): what turns the root
  * position and the 24 local joint matrices that v2p_mvae_step writes into the packed target row [331] (layout of v2p_env_buffers.target)
@@ -1047,6 +1060,39 @@ typedef struct {                    /* DEVICE buffers of the controller */
 } v2p_ctl_reset_buffers;
 int v2p_ctl_reset_begin(int64_t n, const int64_t* flags /*[n]*/, const v2p_ctl_reset_buffers* buffers, void* stream);
 int v2p_ctl_reset_end(int64_t n, int64_t* flags /*[n], cleared*/, const v2p_ctl_reset_buffers* buffers, void* stream);
+/* ---- the two-player controller's reset of finished PAIRS by flags (`PhysicsMVAEControllerDual._reset_envs`,
+ * physics_mvae_controller_dual.py:22-66, `HumanoidSMPLIMMVAEDual._reset_balls`, humanoid_smpl_im_mvae_dual.py:52-63).  Envs 2k and 2k+1
+ * are a pair; a pair is flagged when EITHER of its two words of flags [n] int64 (the controller's `reset_buf`) is non-zero - the dual
+ * step's law raises both, accepting either makes the entry total without a check on the host.  A pair that is not flagged keeps every
+ * bit.  serve_from says who receives: V2P_SERVE_FROM_NEAR the even env of a pair (the odd env serves, :31-36), V2P_SERVE_FROM_FAR the
+ * odd env.  The sequence, the same launches whether 0 or n / 2 pairs are done and with no host read of a device result:
+ *   v2p_ctl_pair_reset_begin       one thread per pair: a word that is 0 in a flagged pair becomes 1 (the per-env flagged entries that
+ *                                  follow then see a whole mask; a non-zero word keeps its value); for both envs progress = 0,
+ *                                  terminate = 0, num_reset_reaction = 0, distance = 0, num_reset += 1; the receiver gets
+ *                                  reset_reaction = 1, reset_recovery = 0 and the server reset_reaction = 0, reset_recovery = 1 (:31-38)
+ *   v2p_mvae_dual_reset_flagged    (`dual_mode: different`; with one generator for both sides: v2p_mvae_reset_flagged on a per-env table
+ *                                  of serve / ready frames)
+ *   v2p_mvae_target_reset_flagged, v2p_env_push_state_flagged
+ *   v2p_tennis_dual_serve_flagged  one thread per pair, after the generator's entry (which writes racket_pos): for the server s of a
+ *                                  flagged pair ball_state[s,0:3] = racket_pos[s], ball_state[s,10:13] = (-40, 0, 0),
+ *                                  ball_state[s,7:10] = u * (4, 4, 3) + (-2, 28, 5), product and sum each rounded in float32; columns
+ *                                  3:7 are not touched.  u = row s >> 1 of draws [n/2,3] or, where draws is null, (word >> 8) * 2^-24 of
+ *                                  words 0..2 of Philox4x32-10 block 0 of stream 3 (csrc/philox.hpp PHILOX_STREAM_SERVE) under
+ *                                  (rule->seed, rule->call, s): a draw never depends on which other pairs are flagged
+ *   v2p_tennis_dual_handover       as it is: the two flags that begin wrote make the serve the receiver's incoming ball
+ *   v2p_ctl_pair_reset_end         flags[e] = 0 where it is not 0, and nothing else: reset_reaction and reset_recovery stay up as they
+ *                                  do after the id-list reset (the next step overwrites them; v2p_ctl_reset_end clears them)
+ * Equal, bit for bit, to the id-list reset of the flagged pairs.  Refused before any HIP call (V2P_ERR_INVALID, a message that names
+ * the call): n < 0, an odd n, an unknown serve_from, a null flags / buffers / required pointer, the serve with neither draws nor a
+ * rule, n above 2^31-1 where the env is a counter word.  n = 0 is a no-op. */
+enum { V2P_SERVE_FROM_NEAR = 0, V2P_SERVE_FROM_FAR = 1 };
+typedef struct {
+    uint64_t seed, call;     /* `call` is the host's count of serve launches that draw */
+} v2p_serve_rule;
+int v2p_ctl_pair_reset_begin(int64_t n, int64_t* flags /*[n], made whole*/, const v2p_ctl_reset_buffers* buffers /*all seven*/, int32_t serve_from, void* stream);
+int v2p_tennis_dual_serve_flagged(int64_t n, const int64_t* flags /*[n]*/, int32_t serve_from, const float* racket_pos /*[n,3]*/, float* ball_state /*[n,13]*/,
+                                  const float* draws /*[n/2,3], nullable*/, const v2p_serve_rule* rule /*nullable with draws*/, void* stream);
+int v2p_ctl_pair_reset_end(int64_t n, int64_t* flags /*[n], cleared*/, void* stream);
 /* The loss head of V2PAgent.calc_gradients (v2p_agent.py:329-362, 395-397; learning/common_agent.py:442-450, 491-520 with clip_value
  * False; PhysicsMVAEController.get_aux_losses) under a fixed sigma, forward and backward.  With row r of the minibatch and
  * j = idx ? idx[r] : r its row of the epoch's dataset:

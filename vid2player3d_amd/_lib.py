@@ -184,6 +184,14 @@ class CtlResetBuffers(C.Structure):
     _fields_ = [(k, vp) for k in CTL_RESET_BUFFER_NAMES]
 
 
+SERVE_FROM = {"near": 0, "far": 1}  # V2P_SERVE_FROM_*: the even / the odd env of a pair receives
+
+
+class ServeRule(C.Structure):
+    """v2p_serve_rule: the key of the serve velocity that v2p_tennis_dual_serve_flagged draws when no table is given."""
+    _fields_ = [("seed", C.c_uint64), ("call", C.c_uint64)]
+
+
 class MvaeRacket(C.Structure):
     """v2p_mvae_racket: the one racket object of a two-player batch (v2p_mvae_dual_reset)."""
     _fields_ = [("righthand", C.c_int32), ("dir", C.c_float * 3), ("normal", C.c_float * 3)]
@@ -328,6 +336,11 @@ def load():
         "v2p_mvae_target_reset_flagged": [C.POINTER(MvaeTargetCfg), C.c_int64, C.POINTER(MvaeTargetBuffers), vp, vp],
         "v2p_ctl_reset_begin": [C.c_int64, vp, C.POINTER(CtlResetBuffers), vp],
         "v2p_ctl_reset_end": [C.c_int64, vp, C.POINTER(CtlResetBuffers), vp],
+        "v2p_ctl_pair_reset_begin": [C.c_int64, vp, C.POINTER(CtlResetBuffers), C.c_int32, vp],
+        "v2p_ctl_pair_reset_end": [C.c_int64, vp, vp],
+        "v2p_tennis_dual_serve_flagged": [C.c_int64, vp, C.c_int32, vp, vp, vp, C.POINTER(ServeRule), vp],
+        "v2p_mvae_dual_reset_flagged": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), C.POINTER(MvaeRacket), vp, vp, vp, C.POINTER(MvaeRootRule), vp,
+                                        C.c_int64, vp],
         "v2p_mvae_target_actions": [C.POINTER(MvaeTargetCfg), C.c_int64, vp, C.POINTER(MvaeTargetBuffers), vp, vp],
         "v2p_policy_input": [C.POINTER(PolicyInputCfg), C.c_int64, C.c_int64, vp, vp, vp],
         "v2p_ll_policy_input": [C.POINTER(PolicyInputCfg), C.c_int64, C.c_int64, C.POINTER(LLPolicySrc), vp, vp, vp],
@@ -360,6 +373,7 @@ EXPORTED_SYMBOLS = (
     "v2p_env_post_physics", "v2p_env_push_state", "v2p_env_target_index", "v2p_env_kernel_build", "v2p_env_set_schedule", "v2p_env_debug_contacts", "v2p_env_debug_contacts_substeps", "v2p_env_debug_pairing", "v2p_env_attach_ball", "v2p_env_set_racket_shapes", "v2p_env_check", "v2p_env_check_async", "v2p_env_job_recoveries", "v2p_env_jobs_skipped", "v2p_env_profile_begin", "v2p_env_profile_begin_sampled", "v2p_env_profile_end", "v2p_ball_rollout", "v2p_tennis_task_step", "v2p_tennis_task_obs", "v2p_tennis_dual_step", "v2p_tennis_dual_handover", "v2p_controller_actions", "v2p_tennis_task_reset", "v2p_mvae_step", "v2p_mvae_reset", "v2p_mvae_dual_step", "v2p_mvae_dual_reset", "v2p_mvae_target_step", "v2p_mvae_target_reset", "v2p_mvae_target_actions", "v2p_policy_input", "v2p_ll_policy_input", "v2p_ll_policy_actions", "v2p_ctl_policy_head", "v2p_ctl_rollout_record", "v2p_ppo_loss", "v2p_last_error", "v2p_abi_version",
     "v2p_debug_guards", "v2p_debug_guards_selftest", "v2p_env_guard_counts",
     "v2p_mvae_reset_flagged", "v2p_mvae_target_reset_flagged", "v2p_env_push_state_flagged", "v2p_ctl_reset_begin", "v2p_ctl_reset_end",
+    "v2p_ctl_pair_reset_begin", "v2p_ctl_pair_reset_end", "v2p_tennis_dual_serve_flagged", "v2p_mvae_dual_reset_flagged",
 )
 
 

@@ -12,6 +12,7 @@
 #include "flag_reset.hpp"
 #include "mvae_player.hpp"
 #include "mvae_target.hpp"
+#include "pair_reset.hpp"
 #include "policy_io.hpp"
 #include "tennis_reset.hpp"
 #include "tennis_task.hpp"
@@ -585,6 +586,74 @@ int v2p_ctl_reset_end(int64_t n, int64_t* flags, const v2p_ctl_reset_buffers* b,
     const int rc = ctl_reset_check("v2p_ctl_reset_end", n, flags, b, false);
     if (rc != V2P_OK || n == 0) return rc;
     return launch_ctl_reset_end(n, flags, *b, (hipStream_t)stream);
+}
+
+// ---- the two-player controller's pair reset by flags (pair_reset.hip, mvae_player_dual_flagged.hip)
+static int pair_check(const char* fn, int64_t n, int32_t serve_from) {
+    if (n < 0) { set_error("%s: n %lld < 0", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (n & 1) { set_error("%s: n %lld is odd (envs 2k and 2k+1 are a pair)", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (serve_from != V2P_SERVE_FROM_NEAR && serve_from != V2P_SERVE_FROM_FAR) { set_error("%s: unknown serve_from %d", fn, serve_from); return V2P_ERR_INVALID; }
+    return V2P_OK;
+}
+
+int v2p_ctl_pair_reset_begin(int64_t n, int64_t* flags, const v2p_ctl_reset_buffers* b, int32_t serve_from, void* stream) {
+    const char* fn = "v2p_ctl_pair_reset_begin";
+    const int rc = pair_check(fn, n, serve_from);
+    if (rc != V2P_OK) return rc;
+    if (!flags || !b) { set_error("%s: null flags / buffers", fn); return V2P_ERR_INVALID; }
+    if (!b->progress || !b->terminate || !b->num_reset_reaction || !b->num_reset || !b->distance || !b->reset_reaction || !b->reset_recovery) {
+        set_error("%s: null progress / terminate / num_reset_reaction / num_reset / distance / reset_reaction / reset_recovery", fn);
+        return V2P_ERR_INVALID;
+    }
+    if (n == 0) return V2P_OK;
+    return launch_ctl_pair_reset_begin(n, flags, *b, serve_from, (hipStream_t)stream);
+}
+
+int v2p_ctl_pair_reset_end(int64_t n, int64_t* flags, void* stream) {
+    const char* fn = "v2p_ctl_pair_reset_end";
+    const int rc = pair_check(fn, n, V2P_SERVE_FROM_NEAR);
+    if (rc != V2P_OK) return rc;
+    if (!flags) { set_error("%s: null flags", fn); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    return launch_ctl_pair_reset_end(n, flags, (hipStream_t)stream);
+}
+
+int v2p_tennis_dual_serve_flagged(int64_t n, const int64_t* flags, int32_t serve_from, const float* racket_pos, float* ball_state, const float* draws,
+                                  const v2p_serve_rule* rule, void* stream) {
+    const char* fn = "v2p_tennis_dual_serve_flagged";
+    const int rc = pair_check(fn, n, serve_from);
+    if (rc != V2P_OK) return rc;
+    if (n > INT32_MAX) { set_error("%s: n %lld above 2^31-1 (the generator's counter holds the env in 32 bits)", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (!flags || !racket_pos || !ball_state) { set_error("%s: null flags / racket_pos / ball_state", fn); return V2P_ERR_INVALID; }
+    if (!draws && !rule) { set_error("%s: neither draws nor a rule for the serve velocity", fn); return V2P_ERR_INVALID; }
+    if (n == 0) return V2P_OK;
+    const v2p_serve_rule none = {0, 0};
+    return launch_tennis_dual_serve_flagged(n, flags, serve_from, racket_pos, ball_state, draws, rule ? *rule : none, (hipStream_t)stream);
+}
+
+int v2p_mvae_dual_reset_flagged(const v2p_mvae_cfg* c, int64_t num_envs, const v2p_mvae_weights* w, const v2p_mvae_buffers* b, const v2p_mvae_racket* racket,
+                                const int64_t* flags, const float* init_feature, const float* root_xy, const v2p_mvae_root_rule* rule, const float* joint_pos_bind_rel,
+                                int64_t bind_rows, void* stream) {
+    const char* fn = "v2p_mvae_dual_reset_flagged";
+    const int rc = mvae_dual_check(fn, c, num_envs, w, b, false);
+    if (rc != V2P_OK) return rc;
+    if (num_envs & 1) { set_error("%s: num_envs %lld is odd (envs 2k and 2k+1 are a pair)", fn, (long long)num_envs); return V2P_ERR_INVALID; }
+    if (num_envs > INT32_MAX) { set_error("%s: num_envs %lld above 2^31-1 (the generator's counter holds the env in 32 bits)", fn, (long long)num_envs); return V2P_ERR_INVALID; }
+    if (!racket) { set_error("%s: null racket", fn); return V2P_ERR_INVALID; }
+    if (!flags || !init_feature || !joint_pos_bind_rel) { set_error("%s: null flags / init_feature / joint_pos_bind_rel", fn); return V2P_ERR_INVALID; }
+    if (!root_xy && !rule) { set_error("%s: neither root_xy nor a rule for the start", fn); return V2P_ERR_INVALID; }
+    if (rule && rule->rule != V2P_MVAE_ROOT_CENTRE && rule->rule != V2P_MVAE_ROOT_DRAW) { set_error("%s: unknown root rule %d", fn, rule->rule); return V2P_ERR_INVALID; }
+    if (bind_rows < 1) { set_error("%s: joint_pos_bind_rel has %lld rows", fn, (long long)bind_rows); return V2P_ERR_INVALID; }
+    if (bind_rows > 1) {
+        set_error("%s: joint_pos_bind_rel has %lld rows: the id-list reset reads the row of a pair's position in the list, which without a list is a prefix count of the "
+                  "flagged pairs - not built; one [24,3] row", fn, (long long)bind_rows);
+        return V2P_ERR_UNSUPPORTED;
+    }
+    if (num_envs == 0) return V2P_OK;
+    const v2p_mvae_root_rule none = {V2P_MVAE_ROOT_CENTRE, 0, 0};
+    const v2p_mvae_cfg (&c2)[2] = *reinterpret_cast<const v2p_mvae_cfg(*)[2]>(c);
+    const v2p_mvae_weights (&w2)[2] = *reinterpret_cast<const v2p_mvae_weights(*)[2]>(w);
+    return launch_mvae_dual_reset_flagged(c2, num_envs, w2, *b, *racket, flags, init_feature, root_xy, rule ? *rule : none, joint_pos_bind_rel, (hipStream_t)stream);
 }
 
 int v2p_mvae_target_actions(const v2p_mvae_target_cfg* c, int64_t n, const float* actions_in, const v2p_mvae_target_buffers* b, float* actions_out, void* stream) {

@@ -6,7 +6,7 @@
 // A draw depends on (seed, call, env, block) alone, not on which other envs draw in the same launch:
 //     key     = (seed_lo, seed_hi)
 //     counter = (env, block | stream << 28, call_lo, call_hi)
-// `stream` keeps the uses apart (the random walk of pre_physics_step, the task reset, the start of a reset player), `call` is the host's count of launches of that use
+// `stream` keeps the uses apart (the random walk of pre_physics_step, the task reset, the start of a reset player, the serve of a reset pair), `call` is the host's count of launches of that use
 // and `block` numbers the four-word outputs of one env in one call (below 2^28).  env = PHILOX_WHOLE_CALL is the one draw that all envs
 // of a call share.
 //
@@ -29,7 +29,7 @@
 
 namespace v2p {
 
-constexpr uint32_t PHILOX_STREAM_WALK = 0, PHILOX_STREAM_RESET = 1, PHILOX_STREAM_ROOT = 2;
+constexpr uint32_t PHILOX_STREAM_WALK = 0, PHILOX_STREAM_RESET = 1, PHILOX_STREAM_ROOT = 2, PHILOX_STREAM_SERVE = 3;
 constexpr uint32_t PHILOX_WHOLE_CALL = 0xffffffffu;
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
 

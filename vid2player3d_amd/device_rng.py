@@ -13,8 +13,9 @@ import math
 
 import numpy as np
 
-STREAM_WALK, STREAM_RESET, STREAM_ROOT = 0, 1, 2
+STREAM_WALK, STREAM_RESET, STREAM_ROOT, STREAM_SERVE = 0, 1, 2, 3
 ROOT_XY_SCALE, ROOT_XY_OFFSET = (2.0, 1.5), (0.0, -13.0)  # `draw_root_xy` (mvae_player.py:230-236): the start of a reset player near the baseline's centre
+SERVE_VEL_SCALE, SERVE_VEL_OFFSET = (4.0, 4.0, 3.0), (-2.0, 28.0, 5.0)  # `_reset_balls` (humanoid_smpl_im_mvae_dual.py:61-63): the velocity of a serve
 WHOLE_CALL = 0xFFFFFFFF
 M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 LARGEST_NORMAL = math.sqrt(48.0 * math.log(2.0))  # u1 = 2^-24: 5.768
@@ -87,3 +88,12 @@ def root_xy_reference(seed, call, n, envs=None):
     f = np.float32
     u = uniform(philox_words(seed, call, STREAM_ROOT, n, 1, envs)[:, :2])
     return ((u - f(0.5)) * np.array(ROOT_XY_SCALE, f) + np.array(ROOT_XY_OFFSET, f)).astype(f)
+
+
+def serve_vel_reference(seed, call, n, envs=None):
+    """The serve velocity [n,3] float32 that `v2p_tennis_dual_serve_flagged` draws for the balls of envs 0 .. n-1 (or `envs`: the servers'
+    env ids) in call `call` under `seed`: u * (4, 4, 3) + (-2, 28, 5) in float32, the product and the sum each rounded on its own, u the
+    uniforms of words 0..2 of block 0 of STREAM_SERVE.  A draw depends on (seed, call, the server's env id) alone."""
+    f = np.float32
+    u = uniform(philox_words(seed, call, STREAM_SERVE, n, 1, envs)[:, :3])
+    return (u * np.array(SERVE_VEL_SCALE, f) + np.array(SERVE_VEL_OFFSET, f)).astype(f)

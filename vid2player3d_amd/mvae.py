@@ -8,6 +8,8 @@ reference runs the decoder under autocast on CUDA - a reduced-precision path is 
 is built: frame 288, latent 32, hidden 256, 6 experts, gate 64, one condition frame, one prediction, predicted phase.  Both dual modes are
 built: `True` (one generator for both sides, `reset_dual`) and `different` (a weight set, statistics, hand and player rule per side: env 2k
 is side 0, env 2k+1 side 1; `v2p_mvae_dual_step` / `v2p_mvae_dual_reset`, csrc/mvae_player_dual.hip).
+`reset_dual_flagged` resets the pairs whose flags are up in one launch over all envs, under either mode (`v2p_mvae_dual_reset_flagged`,
+csrc/mvae_player_dual_flagged.hip; `v2p_mvae_reset_flagged` on the per-env table of serve and ready frames).
 
 `mvae_step_reference` / `mvae_reset_reference` (and `mvae_dual_step_reference` / `mvae_dual_reset_reference`, which apply them row-wise
 by parity) are the numpy statement of the same calls on arrays - the checker of the tests, as
@@ -336,6 +338,19 @@ def mvae_dual_reset_reference(st, avg, std, s, env_ids, init_feature, root_xy, j
     return o
 
 
+def mvae_dual_reset_flagged_reference(st, avg, std, s, flags, init_feature, root_xy, joint_pos_bind_rel, dt=np.float32, probes=None):
+    """`v2p_mvae_dual_reset_flagged` on arrays: mvae_dual_reset_reference over the envs whose flag is not 0 - whole pairs, as
+    `v2p_ctl_pair_reset_begin` leaves the mask.  init_feature [N,288] and root_xy [N,2] hold a row per ENV (init_feature: the serve and
+    ready frames interleaved by parity and serve_from; root_xy: the caller's table, or `device_rng.root_xy_reference(seed, call, N)`);
+    joint_pos_bind_rel is one [24,3] row."""
+    ids = np.flatnonzero(np.asarray(flags))
+    if not whole_pairs(ids):
+        raise ValueError("mvae_dual_reset_flagged_reference: the flags of a pair (2k, 2k+1) must both be up or both be 0; flagged: %s" % ids.tolist())
+    if np.asarray(joint_pos_bind_rel).size != NUM_JOINTS * 3:
+        raise ValueError("mvae_dual_reset_flagged_reference: joint_pos_bind_rel is one [24,3] row (a row per pair is read by list position: not built by flags)")
+    return mvae_dual_reset_reference(st, avg, std, s, ids, np.asarray(init_feature)[ids], np.asarray(root_xy)[ids], joint_pos_bind_rel, dt, probes)
+
+
 def whole_pairs(ids):
     """Is the ascending list `ids` made of whole pairs (2k, 2k+1)?"""
     ids = np.asarray(ids, dtype=np.int64).reshape(-1)
@@ -422,6 +437,7 @@ class MotionVAEPlayer:
         # back from the device
         self.seed = int(self.cfg.get("seed", 0)) & (2 ** 64 - 1)
         self._reset_calls = 0
+        self._dual_init_tables = {}  # serve_from -> [N,288]: `dual_init_table`
 
     def _buffers(self):
         # (built per call: `_swing_type_cycle` may have become another task's tensor, TennisControllerTask.attach_motion_generator)
@@ -476,6 +492,57 @@ class MotionVAEPlayer:
             _lib.check(_lib.load().v2p_mvae_reset_flagged(C.byref(self._cfg_struct), n, C.byref(self._weights_struct), C.byref(b), _lib.ptr(flags), _lib.ptr(self._init_data),
                                                           _lib.ptr(xy), None if rule is None else C.byref(rule), _lib.ptr(self._joint_pos_bind_rel),
                                                           _lib.current_stream(self.device)), "v2p_mvae_reset_flagged")
+
+    def dual_init_table(self, serve_from=None):
+        """[N,288] by env: the ready frame where the env receives, the serve frame where it serves - of every pair the even env receives
+        with serve_from 'near' and the odd env with 'far' (physics_mvae_controller_dual.py:31-36).  Built once per serve_from (default:
+        the player's cfg `serve_from`, 'near' where it has none)."""
+        if self._init_data_ready is None:
+            raise RuntimeError("MotionVAEPlayer.dual_init_table: the player was not made with cfg dual_mode: True or 'different'")
+        serve_from = self.cfg.get("serve_from", "near") if serve_from is None else serve_from
+        if serve_from not in _lib.SERVE_FROM:
+            raise ValueError("MotionVAEPlayer: serve_from %r is neither 'near' nor 'far'" % (serve_from,))
+        tables = self._dual_init_tables
+        if serve_from not in tables:
+            receives = (torch.arange(self.num_envs, device=self.device) % 2 == _lib.SERVE_FROM[serve_from]).view(-1, 1)
+            tables[serve_from] = torch.where(receives, self._init_data_ready, self._init_data_serve).contiguous()
+        return tables[serve_from]
+
+    def reset_dual_flagged(self, flags, root_xy=None, serve_from=None):
+        """`reset_dual(receivers, servers)` for the pairs whose flags ([N] int64 on the device, non-zero = reset; BOTH words of a pair up,
+        as `v2p_ctl_pair_reset_begin` leaves them) are up, in one launch over all envs: `v2p_mvae_dual_reset_flagged` under `dual_mode:
+        different`, `v2p_mvae_reset_flagged` on the per-env table of serve and ready frames (`dual_init_table`) under `dual_mode: True`.
+        No id list, no gather, no host read.  root_xy [N,2] (row e: env e's start) stands in for the draw; without it the kernel draws
+        the start itself from (seed, call, env) as `device_rng.root_xy_reference` states it - always a draw, never the centre:
+        `draw_root_xy` draws whenever `dual_mode` is set.  joint_pos_bind_rel with a row per pair is refused (the id-list form reads
+        the row of a pair's position in the list)."""
+        if self._init_data_ready is None:
+            raise RuntimeError("MotionVAEPlayer.reset_dual_flagged: the player was not made with cfg dual_mode: True or 'different'")
+        n = self.num_envs
+        if not torch.is_tensor(flags) or flags.dtype != torch.int64 or flags.device != self.device or not flags.is_contiguous() or flags.numel() != n:
+            raise RuntimeError("MotionVAEPlayer.reset_dual_flagged: flags must be a contiguous int64 tensor [%d] on %s" % (n, self.device))
+        xy, rule = None, None
+        if root_xy is not None:
+            xy = root_xy
+            if not torch.is_tensor(xy) or xy.dtype != torch.float32 or xy.device != self.device or not xy.is_contiguous() or tuple(xy.shape) != (n, 2):
+                raise RuntimeError("MotionVAEPlayer.reset_dual_flagged: root_xy must be a contiguous float32 tensor [%d, 2] on %s" % (n, self.device))
+        bind = self._joint_pos_bind_rel
+        if self._is_dual and len(bind) > 1:
+            raise NotImplementedError("MotionVAEPlayer.reset_dual_flagged: joint_pos_bind_rel has %d rows; the id-list reset reads the row of a pair's position in the "
+                                      "list, which by flags would need a prefix count of the flagged pairs: not built (one [24,3] row is)" % len(bind))
+        table = self.dual_init_table(serve_from)
+        if xy is None:
+            rule = _lib.MvaeRootRule(rule=_lib.MVAE_ROOT_RULES["draw"], seed=self.seed, call=self._reset_calls & (2 ** 64 - 1))
+            self._reset_calls += 1
+        b = self._buffers()
+        stream, rule_p = _lib.current_stream(self.device), None if rule is None else C.byref(rule)
+        with torch.cuda.device(self.device):
+            if self._is_dual:
+                _lib.check(_lib.load().v2p_mvae_dual_reset_flagged(self._cfg_struct, n, self._weights_struct, C.byref(b), C.byref(self._racket_struct), _lib.ptr(flags),
+                                                                   _lib.ptr(table), _lib.ptr(xy), rule_p, _lib.ptr(bind), len(bind), stream), "v2p_mvae_dual_reset_flagged")
+            else:
+                _lib.check(_lib.load().v2p_mvae_reset_flagged(C.byref(self._cfg_struct), n, C.byref(self._weights_struct), C.byref(b), _lib.ptr(flags), _lib.ptr(table),
+                                                              _lib.ptr(xy), rule_p, _lib.ptr(bind), stream), "v2p_mvae_reset_flagged")
 
     def reset_dual(self, reset_reaction_env_ids, reset_recovery_env_ids, root_xy=None):
         """`reset_dual` (mvae_player.py:167-182) with `dual_mode: True` or 'different': the envs of both lists, in ascending order, start from the ready

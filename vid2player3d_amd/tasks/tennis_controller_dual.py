@@ -11,9 +11,17 @@ reference has two `.nonzero()`, `terminate.sum() > 0`, `index.cpu()` and a gathe
 
 `dual_step_reference` and `handover_reference` are the numpy statements of the two launches - the checkers of the tests; the product
 never calls them.  `DualTennisControllerTask` is the reference-shaped object.  Training-mode semantics: the extra
-`_update_state_from_sim()` "for vis" when not training (humanoid_smpl_im_mvae_dual.py:46-48) is not built.  Not built either: resetting
-finished pairs by mask without a host list (`reset(ids)` takes ids).  Under `dual_mode: different` the attached motion generator is the
-two-player one (a weight set per side, `v2p_mvae_dual_step` / `_reset`) and the imitation target takes a body shape per side.
+`_update_state_from_sim()` "for vis" when not training (humanoid_smpl_im_mvae_dual.py:46-48) is not built.  Under `dual_mode: different`
+the attached motion generator is the two-player one (a weight set per side, `v2p_mvae_dual_step` / `_reset`) and the imitation target
+takes a body shape per side.
+
+Finished pairs are reset in one of two ways.  `reset(ids)` takes the id list of whole pairs, checks it and gathers by it: the host reads
+device results.  `reset_pairs_by_flags()` takes `reset_buf` as the mask - a pair is flagged when either of its two words is up - and is
+one fixed sequence of launches over all envs, the same whether 0 or N/2 pairs are done: `v2p_ctl_pair_reset_begin`, the generator's
+flagged reset, `v2p_mvae_target_reset_flagged`, `v2p_env_push_state_flagged`, `v2p_tennis_dual_serve_flagged`, the hand-over,
+`v2p_ctl_pair_reset_end`; no id list, no host read, no allocation, and the same bits as `reset(ids)` of those pairs.
+`pair_reset_begin_reference`, `serve_flagged_reference` and `pair_reset_end_reference` are the numpy statements of the three new
+launches.  `match.MatchPlayer` is the loop around either.
 """
 import ctypes as C
 import math
@@ -243,6 +251,95 @@ def handover_reference(st, s, dt=np.float32):
     return o
 
 
+# ------------------------------------------------------------------------------------------------------------------ pairs by flags
+def _receiver_side(serve_from):
+    if serve_from not in _lib.SERVE_FROM:
+        raise ValueError("serve_from %r is neither 'near' nor 'far'" % (serve_from,))
+    return _lib.SERVE_FROM[serve_from]  # 'near': the even env of a pair receives and the odd env serves (:31-36)
+
+
+def pair_flags_reference(flags):
+    """(mask made whole [n] int64, pair flagged [n] bool): a pair (2k, 2k+1) is flagged when either word is not 0; its zero word becomes
+    1, a non-zero word keeps its value."""
+    f = np.array(flags, dtype=np.int64).reshape(-1, 2)
+    up = (f != 0).any(1)
+    return np.where(up[:, None] & (f == 0), 1, f).reshape(-1), np.repeat(up, 2)
+
+
+def pair_reset_begin_reference(s, flags, serve_from="near"):
+    """`v2p_ctl_pair_reset_begin` on arrays (names of _lib.CTL_RESET_BUFFER_NAMES): returns (the seven arrays after, the flags after)."""
+    whole, up = pair_flags_reference(flags)
+    receives = np.arange(len(whole)) % 2 == _receiver_side(serve_from)
+    o = {k: np.array(v) for k, v in s.items()}
+    for k in ("progress", "terminate", "num_reset_reaction", "distance"):
+        o[k][up] = 0
+    o["num_reset"][up] += 1
+    o["reset_reaction"] = np.where(up, receives, o["reset_reaction"].astype(bool))
+    o["reset_recovery"] = np.where(up, ~receives, o["reset_recovery"].astype(bool))
+    return o, whole
+
+
+def serve_flagged_reference(flags, serve_from, racket_pos, ball_state, draws):
+    """`v2p_tennis_dual_serve_flagged` on arrays: `_reset_balls` (humanoid_smpl_im_mvae_dual.py:56-63) for the servers of the flagged
+    pairs.  draws [n/2,3]: a row per PAIR (the caller's table, or `device_rng.uniform` of the words `serve_vel_reference` reads)."""
+    from ..device_rng import SERVE_VEL_OFFSET, SERVE_VEL_SCALE
+
+    _, up = pair_flags_reference(flags)
+    n = len(up)
+    servers = np.flatnonzero(up & (np.arange(n) % 2 != _receiver_side(serve_from)))
+    ball = np.array(ball_state, dtype=_f)
+    ball[servers, 0:3] = np.asarray(racket_pos, dtype=_f)[servers]
+    ball[servers, 10:13] = np.array([-40.0, 0.0, 0.0], _f)
+    ball[servers, 7:10] = np.asarray(draws, dtype=_f).reshape(-1, 3)[servers >> 1] * np.array(SERVE_VEL_SCALE, _f) + np.array(SERVE_VEL_OFFSET, _f)
+    return ball
+
+
+def pair_reset_end_reference(flags):
+    """`v2p_ctl_pair_reset_end` on arrays: the mask, cleared."""
+    return np.zeros_like(np.asarray(flags, dtype=np.int64))
+
+
+def _stream(t):
+    return _lib.current_stream(t.device)
+
+
+def _need(t, shape, dtype, what):
+    """a kernel indexes `t` by env or by pair: anything but a contiguous GPU tensor of that shape is refused here"""
+    if not torch.is_tensor(t) or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape) or (dtype is not None and t.dtype != dtype):
+        raise RuntimeError("%s must be a contiguous %sGPU tensor %s" % (what, "" if dtype is None else str(dtype).replace("torch.", "") + " ", list(shape)))
+
+
+def launch_pair_reset_begin(n, flags, tensors, serve_from="near"):
+    """v2p_ctl_pair_reset_begin on a dict of device tensors (names of _lib.CTL_RESET_BUFFER_NAMES; None = NULL)."""
+    _need(flags, (n,), torch.int64, "v2p_ctl_pair_reset_begin: flags")
+    for k, v in tensors.items():
+        if v is not None:
+            _need(v, (n,), None, "v2p_ctl_pair_reset_begin: " + k)
+    b = _lib.CtlResetBuffers(**{k: v.data_ptr() for k, v in tensors.items() if v is not None})
+    with torch.cuda.device(flags.device):
+        _lib.check(_lib.load().v2p_ctl_pair_reset_begin(int(n), _lib.ptr(flags), C.byref(b), _receiver_side(serve_from), _stream(flags)), "v2p_ctl_pair_reset_begin")
+
+
+def launch_serve_flagged(n, flags, serve_from, racket_pos, ball_state, draws=None, seed=0, call=0):
+    """v2p_tennis_dual_serve_flagged; draws [n/2,3] (None: the kernel draws under (seed, call, server))."""
+    who = "v2p_tennis_dual_serve_flagged: "
+    _need(flags, (n,), torch.int64, who + "flags")
+    _need(racket_pos, (n, 3), torch.float32, who + "racket_pos")
+    _need(ball_state, (n, 13), torch.float32, who + "ball_state")
+    if draws is not None:
+        _need(draws, (n // 2, 3), torch.float32, who + "draws")
+    rule = None if draws is not None else _lib.ServeRule(seed=int(seed) & (2 ** 64 - 1), call=int(call) & (2 ** 64 - 1))
+    with torch.cuda.device(flags.device):
+        _lib.check(_lib.load().v2p_tennis_dual_serve_flagged(int(n), _lib.ptr(flags), _receiver_side(serve_from), _lib.ptr(racket_pos), _lib.ptr(ball_state), _lib.ptr(draws),
+                                                             None if rule is None else C.byref(rule), _stream(flags)), "v2p_tennis_dual_serve_flagged")
+
+
+def launch_pair_reset_end(n, flags):
+    _need(flags, (n,), torch.int64, "v2p_ctl_pair_reset_end: flags")
+    with torch.cuda.device(flags.device):
+        _lib.check(_lib.load().v2p_ctl_pair_reset_end(int(n), _lib.ptr(flags), _stream(flags)), "v2p_ctl_pair_reset_end")
+
+
 # ------------------------------------------------------------------------------------------------------------------ the task
 class DualTennisControllerTask(tc.TennisControllerTask):
     """`PhysicsMVAEControllerDual` on top of a racket + ball batch: cfg v2p `dual_mode: True` over a single-player task (both sides of a
@@ -250,7 +347,9 @@ class DualTennisControllerTask(tc.TennisControllerTask):
     `grip` list, its own grip).  On top of `TennisControllerTask`'s cfg: `ball_traj_in_file` (a file name or an array [B,F,2]),
     `serve_from` (see `reset`); `traj_in_params`: the in-estimator's grids.  Both task
     flags start at zero (:16-17).  `post_physics_step()` is `v2p_tennis_dual_step`; `reset([])` is `v2p_tennis_dual_handover` alone - the
-    rally path, no synchronisation; `reset(ids)` with whole sorted pairs resets their actors first."""
+    rally path, no synchronisation; `reset(ids)` with whole sorted pairs resets their actors first; `reset_pairs_by_flags()` does the same
+    for the pairs whose `reset_buf` is up, without a list and without a host read.  `_reset_root_xy` [N,2] and `_reset_serve_draws`
+    [N/2,3] (both default None: drawn) stand in for the draws of either."""
 
     def __init__(self, task, cfg, params=traj_out_params, traj_in_params=traj_in_params, seed=None):
         super().__init__(task, cfg, params, seed=seed)
@@ -266,6 +365,10 @@ class DualTennisControllerTask(tc.TennisControllerTask):
         self._reset_reaction_buf[:] = False
         self._reset_recovery_buf[:] = False
         self._target_draw = torch.zeros(n, dtype=torch.float32, device=dev)
+        # [N/2,3]: a uniform draw per PAIR that stands in for the serve's, in `reset_pairs_by_flags()`; `match.MatchPlayer` hands
+        # `reset(ids)` its rows.  Without it the serve kernel draws under (seed, the count of such launches, the server's env id)
+        self._reset_serve_draws = None
+        self._serve_calls = 0
 
     def _check_mode(self, task, v2p):
         mode, players = v2p.get("dual_mode"), getattr(task, "racket_players", None)
@@ -346,6 +449,43 @@ class DualTennisControllerTask(tc.TennisControllerTask):
             self._reset_reaction_buf[receivers] = True
             self._reset_recovery_buf[servers] = True
         self.handover()
+
+    def reset_pairs_by_flags(self):
+        """`reset(ids of the done pairs)` for the pairs whose `reset_buf` is up (either word of a pair), without knowing them on the
+        host: ONE fixed sequence of launches over all envs, the same whether 0 or N/2 pairs are done - `v2p_ctl_pair_reset_begin` (the
+        mask made whole, the bookkeeping, the pair's reaction / recovery flags), the generator's flagged reset
+        (`MotionVAEPlayer.reset_dual_flagged`), `v2p_mvae_target_reset_flagged` and `v2p_env_push_state_flagged`,
+        `v2p_tennis_dual_serve_flagged`, the hand-over (with its `_target_draw.uniform_()` under use_random_ball_target),
+        `v2p_ctl_pair_reset_end` (the mask).  No host read of a device result, no id list, no allocation.  `_reset_root_xy` [N,2] and
+        `_reset_serve_draws` [N/2,3] stand in for the generator's and the serve's draw; without them the kernels draw.  Without a motion
+        generator the generator, target and serve launches are left out, as in `reset(ids)`."""
+        who, flags, n = "DualTennisControllerTask.reset_pairs_by_flags", self.reset_buf, self.num_envs
+        serve_from = self.cfg_v2p.get("serve_from", "near")
+        _receiver_side(serve_from)
+        _need(flags, (n,), torch.int64, who + ": reset_buf")
+        t = dict(progress=self.progress_buf, terminate=self._terminate_buf, num_reset_reaction=self._num_reset_reaction, num_reset=self._num_reset,
+                 distance=self._distance, reset_reaction=self._reset_reaction_buf, reset_recovery=self._reset_recovery_buf)
+        for k, v in t.items():
+            _need(v, (n,), None, who + ": " + k)
+        player, draws = self._mvae_player, self._reset_serve_draws
+        if player is not None:
+            if player._is_dual and len(player._joint_pos_bind_rel) > 1:
+                raise NotImplementedError("%s: the attached generator has %d rows of joint_pos_bind_rel; a row per pair is read by list position, which is not built "
+                                          "by flags (reset(ids) is)" % (who, len(player._joint_pos_bind_rel)))
+            ball = self.task._ball_root_states
+            _need(ball, (n, 13), torch.float32, who + ": the task's _ball_root_states")
+            if draws is not None:
+                _need(draws, (n // 2, 3), torch.float32, who + ": _reset_serve_draws")
+        launch_pair_reset_begin(n, flags, t, serve_from)
+        if player is not None:
+            player.reset_dual_flagged(flags, self._reset_root_xy, serve_from)
+            if self._imitation_target is not None:
+                self._imitation_target.reset_flagged(flags)
+            launch_serve_flagged(n, flags, serve_from, player._racket_pos, ball, draws, self.seed, self._serve_calls)
+            if draws is None:
+                self._serve_calls += 1
+        self.handover()
+        launch_pair_reset_end(n, flags)
 
     def _reset_envs(self, env_ids):
         self.reset(env_ids)
