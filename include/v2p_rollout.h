@@ -633,6 +633,50 @@ int v2p_tennis_task_step(const v2p_tennis_cfg* cfg, int64_t n, const v2p_tennis_
 int v2p_tennis_task_obs(const v2p_tennis_cfg* cfg, int64_t num_envs, const v2p_tennis_buffers* buffers, const int64_t* env_ids, int64_t n_ids,
                         void* stream);
 
+/* ---- the controller's evaluation step (vid2player/env/tasks/mvae_controller_vis.py: MVAEControllerVis, what `run.py --test` runs):
+ * v2p_tennis_task_step with the test-mode episode law (`_compute_reset`, :64-79) in place of the training law, the four per-env meters
+ * of `_compute_stats` (:81-95, AverageMeterUnSync of utils/common.py:34-63) and one frame of the record the evaluation hands on
+ * (:140-146) - in the same ONE launch, without a host read (the reference: a nonzero(), up to eight .cpu() copies for the meters, six
+ * more and a growing torch.cat for the record).  v2p_tennis_cfg / v2p_tennis_buffers are the step's, unchanged; of the cfg
+ * max_episode_length, enable_early_termination, court_min and court_max are not read, of the buffers `distance` is neither read nor
+ * written.
+ *   terminate = reset = progress > episode_length (after the increment); in_time = tar_time >= tar_time_total
+ *   reaction = (hit & tar_action == 0 & has_bounce & in_time) | (~hit & in_time)
+ *   recovery = tar_action == 1 & (hit | ball_y < root_y - 1 | |ball_vy| < 2);   where reset: reaction = 1, recovery = 0
+ * A NaN in the observation row, a root outside the court end nothing.  An env whose recovery flag is up updates its meters with hit,
+ * swing_type_cycle == 1, est_bounce_in and - only where est_bounce_in - ||est_bounce_pos - target_bounce_pos||, est_* being this
+ * step's: sum += v, count += 1, avg = sum / float(count), max = v > max ? v : max.  An env owns its meters: no atomics, one order. */
+enum { V2P_TENNIS_METER_HIT_RATE = 0, V2P_TENNIS_METER_FH_RATIO = 1, V2P_TENNIS_METER_BOUNCE_IN_RATE = 2, V2P_TENNIS_METER_BOUNCE_IN_POS_ERROR = 3 };
+#define V2P_TENNIS_METERS 4
+typedef struct {
+    int64_t episode_length;         /* cfg env.episodeLength (the reference's default: 600); the test is strict */
+    int64_t num_frames;             /* F of the record's arrays (not read without a record) */
+    int32_t body_of_smpl[24];       /* `_mujoco_2_smpl`: the engine's body of SMPL joint s; [0] = 0, a permutation (not read without a record) */
+} v2p_tennis_eval_cfg;
+typedef struct {                    /* DEVICE buffers */
+    /* the meters, read and written, in the order V2P_TENNIS_METER_*: before the first update avg is 1, sum, count and max are 0 */
+    float* meter_sum[V2P_TENNIS_METERS];     /* each [N] */
+    int64_t* meter_count[V2P_TENNIS_METERS];
+    float* meter_avg[V2P_TENNIS_METERS];
+    float* meter_max[V2P_TENNIS_METERS];
+    /* the record: all six arrays and dof_state, or none (all NULL: nothing is written).  Frame-major, so that a step's stores are
+     * contiguous; the reference's [N, F, ...] is a permuted view */
+    const float* dof_state;         /* [N,69,2] read only: the engine's DoF (position, velocity) pairs, body order; the positions are read */
+    float* joint_rot;               /* [F,N,24,3] `_joint_rot` of `_update_state_from_sim` with `_is_train` false (humanoid_smpl_im_mvae.py:813-820):
+                                     * joint 0 = quaternion_to_angle_axis of the root link's (x,y,z,w) as (w,x,y,z), joints 1..23 = the DoF positions */
+    float* root_pos;                /* [F,N,3] */
+    float* ball_pos;                /* [F,N,3] */
+    float* target_pos;              /* [F,N,3] */
+    float* phase;                   /* [F,N] */
+    int64_t* swing_type_cycle;      /* [F,N] */
+} v2p_tennis_eval_buffers;
+/* One evaluation step of envs 0 .. n-1; with a record, frame `frame` (a count the caller keeps on the host) of its arrays is written.
+ * Refused before any HIP call (V2P_ERR_INVALID, a message that names the call): n <= 0, a null meter array, null swing_type_cycle, a
+ * record with some of its seven pointers null, a frame outside [0, num_frames), body_of_smpl that is no permutation with [0] = 0, and
+ * what v2p_tennis_task_step refuses. */
+int v2p_tennis_eval_step(const v2p_tennis_cfg* cfg, const v2p_tennis_eval_cfg* eval_cfg, int64_t n, const v2p_tennis_buffers* buffers,
+                         const v2p_tennis_eval_buffers* eval_buffers, int64_t frame, const char** sub_rewards_names, void* stream);
+
 /* ---- the two-player rally (vid2player/env/tasks/physics_mvae_controller_dual.py: PhysicsMVAEControllerDual; envs 2k and 2k+1 are
  * opponents, utils/common.py:111-115): the task step with the dual reset law, and the ball hand-over that turns one player's hit into
  * the other's incoming ball (humanoid_smpl_im_mvae_dual.py:65-79 `_reset_balls`, utils/tennis_ball_in_estimator.py:48-79 `estimate`).

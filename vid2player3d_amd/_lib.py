@@ -110,6 +110,20 @@ class TennisBuffers(C.Structure):
     _fields_ = [(k, vp) for k in TENNIS_BUFFER_NAMES]
 
 
+TENNIS_METER_NAMES = ("hit_rate", "fh_ratio", "bounce_in_rate", "bounce_in_pos_error")  # V2P_TENNIS_METER_*
+
+
+class TennisEvalCfg(C.Structure):
+    """v2p_tennis_eval_cfg: what the evaluation step (v2p_tennis_eval_step) needs on top of v2p_tennis_cfg."""
+    _fields_ = [("episode_length", C.c_int64), ("num_frames", C.c_int64), ("body_of_smpl", C.c_int32 * 24)]
+
+
+class TennisEvalBuffers(C.Structure):
+    """v2p_tennis_eval_buffers: the four meters (sum, count, avg, max of each, in the order of TENNIS_METER_NAMES) and the record."""
+    _fields_ = [("meter_sum", vp * 4), ("meter_count", vp * 4), ("meter_avg", vp * 4), ("meter_max", vp * 4), ("dof_state", vp), ("joint_rot", vp), ("root_pos", vp),
+                ("ball_pos", vp), ("target_pos", vp), ("phase", vp), ("swing_type_cycle", vp)]
+
+
 class TennisDualCfg(C.Structure):
     """v2p_tennis_dual_cfg: what the two-player step and hand-over need on top of v2p_tennis_cfg."""
     _fields_ = [("grip_normal", (C.c_float * 3) * 2), ("in_grid", (C.c_double * 3) * 4), ("in_rows", C.c_int64), ("in_frames", C.c_int32)]
@@ -322,6 +336,8 @@ def load():
         "v2p_ball_rollout": [C.POINTER(BallSim), C.c_int64, vp, vp, vp, C.POINTER(BallRolloutOut), vp],
         "v2p_tennis_task_step": [C.POINTER(TennisCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(C.c_char_p), vp],
         "v2p_tennis_task_obs": [C.POINTER(TennisCfg), C.c_int64, C.POINTER(TennisBuffers), vp, C.c_int64, vp],
+        "v2p_tennis_eval_step": [C.POINTER(TennisCfg), C.POINTER(TennisEvalCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(TennisEvalBuffers), C.c_int64,
+                                 C.POINTER(C.c_char_p), vp],
         "v2p_tennis_dual_step": [C.POINTER(TennisCfg), C.POINTER(TennisDualCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(C.c_char_p), vp],
         "v2p_tennis_dual_handover": [C.POINTER(TennisCfg), C.POINTER(TennisDualCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(TennisDualBuffers), vp],
         "v2p_tennis_task_reset": [C.POINTER(TennisCfg), C.POINTER(TennisResetCfg), C.c_int64, C.POINTER(TennisBuffers), C.POINTER(TennisResetBuffers), vp],
@@ -374,6 +390,7 @@ EXPORTED_SYMBOLS = (
     "v2p_debug_guards", "v2p_debug_guards_selftest", "v2p_env_guard_counts",
     "v2p_mvae_reset_flagged", "v2p_mvae_target_reset_flagged", "v2p_env_push_state_flagged", "v2p_ctl_reset_begin", "v2p_ctl_reset_end",
     "v2p_ctl_pair_reset_begin", "v2p_ctl_pair_reset_end", "v2p_tennis_dual_serve_flagged", "v2p_mvae_dual_reset_flagged",
+    "v2p_tennis_eval_step",
 )
 
 

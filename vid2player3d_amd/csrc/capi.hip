@@ -14,6 +14,7 @@
 #include "mvae_target.hpp"
 #include "pair_reset.hpp"
 #include "policy_io.hpp"
+#include "tennis_eval.hpp"
 #include "tennis_reset.hpp"
 #include "tennis_task.hpp"
 #include "v2p_internal.hpp"
@@ -301,6 +302,33 @@ int v2p_tennis_task_obs(const v2p_tennis_cfg* c, int64_t num_envs, const v2p_ten
     if (num_envs < 0 || (n_ids > 0 && !env_ids)) { set_error("v2p_tennis_task_obs: num_envs %lld < 0 or null env_ids", (long long)num_envs); return V2P_ERR_INVALID; }
     if (n_ids == 0 || num_envs == 0) return V2P_OK;
     return launch_tennis_task_obs(*c, num_envs, *b, env_ids, n_ids, (hipStream_t)stream);
+}
+
+int v2p_tennis_eval_step(const v2p_tennis_cfg* c, const v2p_tennis_eval_cfg* ec, int64_t n, const v2p_tennis_buffers* b, const v2p_tennis_eval_buffers* x, int64_t frame,
+                         const char** names, void* stream) {
+    const char* fn = "v2p_tennis_eval_step";
+    if (!ec || !x) { set_error("%s: null eval cfg / eval buffers", fn); return V2P_ERR_INVALID; }
+    if (n <= 0) { set_error("%s: n %lld <= 0", fn, (long long)n); return V2P_ERR_INVALID; }
+    const int rc = tennis_check(fn, c, n, b, true);
+    if (rc != V2P_OK) return rc;
+    if (!b->swing_type_cycle) { set_error("%s: null swing_type_cycle (the fh_ratio meter reads it under every reward law)", fn); return V2P_ERR_INVALID; }
+    for (int m = 0; m < V2P_TENNIS_METERS; ++m)
+        if (!x->meter_sum[m] || !x->meter_count[m] || !x->meter_avg[m] || !x->meter_max[m]) { set_error("%s: null array of meter %d", fn, m); return V2P_ERR_INVALID; }
+    const int given = (x->dof_state != nullptr) + (x->joint_rot != nullptr) + (x->root_pos != nullptr) + (x->ball_pos != nullptr) + (x->target_pos != nullptr) +
+                      (x->phase != nullptr) + (x->swing_type_cycle != nullptr);
+    if (given != 0 && given != 7) { set_error("%s: a record needs dof_state and all six of its arrays (%d of 7 given)", fn, given); return V2P_ERR_INVALID; }
+    if (given) {
+        if (frame < 0 || frame >= ec->num_frames) { set_error("%s: frame %lld outside [0, %lld)", fn, (long long)frame, (long long)ec->num_frames); return V2P_ERR_INVALID; }
+        uint32_t seen = 0;
+        for (int s = 0; s < V2P_NUM_BODIES; ++s) {
+            const int body = ec->body_of_smpl[s];
+            if (body < 0 || body >= V2P_NUM_BODIES || (seen >> body & 1u)) { set_error("%s: body_of_smpl[%d] = %d: not a permutation of 0..%d", fn, s, body, V2P_NUM_BODIES - 1); return V2P_ERR_INVALID; }
+            seen |= 1u << body;
+        }
+        if (ec->body_of_smpl[0] != 0) { set_error("%s: body_of_smpl[0] = %d: SMPL joint 0 must be the root body", fn, ec->body_of_smpl[0]); return V2P_ERR_INVALID; }
+    }
+    if (names) *names = c->reward_type == V2P_TENNIS_REWARD_REACH ? "pos_reward" : "pos_reward,ball_pos_reward";
+    return launch_tennis_eval_step(*c, *ec, n, *b, *x, frame, (hipStream_t)stream);
 }
 
 // what both entry points of the two-player batch refuse

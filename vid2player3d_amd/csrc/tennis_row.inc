@@ -1,5 +1,6 @@
 // Two pieces of an env's row that the task-step kernel and the hand-over kernel of tennis_task.hip both need, as TEXT: the step kernel
-// includes them into its body, the hand-over through two device functions.  They are text and not functions of the step kernel because
+// includes them into its body, the hand-over through two device functions; the evaluation step (tennis_eval.hip) includes them like the
+// step kernel.  They are text and not functions of the step kernel because
 // the existing instantiations of tennis_task_kernel must stay the machine code they were (tools/kernel_identity.py), and moving
 // either piece into a function call - inlined or not - moves their instruction streams.  A change that is allowed to move the old
 // kernels' code should turn both pieces into __device__ functions: as text they lean on a dozen names of the including scope.

@@ -65,15 +65,18 @@ def rotmat_to_quat_reference(m, dt=np.float32, probes=None):
     return q.astype(dt)
 
 
-def quat_to_angle_axis_reference(q, dt=np.float32, probes=None):
-    """quaternion_to_angle_axis (utils/konia_transform.py:557-628) of (w, x, y, z)."""
+def quat_to_angle_axis_reference(q, dt=np.float32, probes=None, wide_atan2=False):
+    """quaternion_to_angle_axis (utils/konia_transform.py:557-628) of (w, x, y, z).  wide_atan2: the one arctangent is evaluated in float64
+    and rounded once to dt - the correctly rounded value for all but one argument in some 2^29, which no float32 library promises and
+    which a kernel that does the same reproduces bit for bit (csrc/tennis_eval.hip)."""
     q = np.asarray(q, dtype=dt)
     w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
     two, eps = dt(2), dt(1e-6)
     with np.errstate(invalid="ignore", divide="ignore"):
         s2 = x * x + y * y + z * z
         s = np.sqrt(np.maximum(s2, eps))
-        two_theta = two * np.where(w < 0, np.arctan2(-s, -w), np.arctan2(s, w))  # (s >= 1e-3: torch_safe_atan2 never shifts)
+        at = (lambda y, x: np.arctan2(y.astype(np.float64), x.astype(np.float64)).astype(dt)) if wide_atan2 else np.arctan2
+        two_theta = two * np.where(w < 0, at(-s, -w), at(s, w))  # (s >= 1e-3: torch_safe_atan2 never shifts)
         k = np.where(s2 > 0, szd(two_theta, s, dt), two)
     _record(probes, quat_w=w, sin2=s2)
     return (q[..., 1:] * k[..., None]).astype(dt)

@@ -43,6 +43,15 @@ that launch - as one fixed sequence of six launches over all envs, without an id
 and is the default of the PPO agent (`reset_mode`).  `_reset_root_xy` [N,2] (default None) gives every env a start that stands in for
 the generator's draw in both.
 
+Evaluation (`run.py --test`) is `TennisControllerEval`, the reference's `MVAEControllerVis` (env/tasks/mvae_controller_vis.py) without
+the viewer: the same task with the test-mode episode law (:64-79: an episode ends only past `episodeLength`; the reaction flag waits for
+the bounce of a returned ball, the recovery flag also rises on a slow ball), the four per-env meters `hit_rate`, `fh_ratio`,
+`bounce_in_rate`, `bounce_in_pos_error` (:81-95) and the record the evaluation hands on (:140-146, `_joint_rot` of the simulated body
+included) - all in the step's ONE launch, `v2p_tennis_eval_step` (csrc/tennis_eval.hip), without a host read.  `select_best()` and
+`summary()` read them after the run; `eval_player.ControllerEvalPlayer` is the loop.  `eval_step_reference` / `eval_record_reference`
+state it in numpy.  Not built: rendering, video and HTML output, `fix_two_hand_backhand_post`, `vis_pd_target`, `MVAEControllerVisDual`,
+the reference's frame 0 of the record (taken after the first reset, before any step).
+
 `task_step_reference` is a numpy statement of the same step on arrays - the checker of the tests, as `ball_traj.resample_reference`
 and `body_shapes` have theirs; the product never calls it.  There is no CPU path: a CPU device or a missing library is a RuntimeError.
 """
@@ -305,6 +314,120 @@ def task_step_reference(st, s):
     if not st["use_history"]:
         o["traj_cursor"] = np.minimum(np.clip(A("traj_cursor", np.int64), 0, TRAJ_FRAMES) + 1, TRAJ_FRAMES).astype(np.int32)
     return o
+
+
+# ------------------------------------------------------------------------------------------------------------------ the evaluation step
+METER_NAMES = _lib.TENNIS_METER_NAMES  # the order of v2p_tennis_eval_buffers.meter_*: hit_rate, fh_ratio, bounce_in_rate, bounce_in_pos_error
+METER_FIELDS = ("meter_sum", "meter_count", "meter_avg", "meter_max")
+RECORD_NAMES = ("joint_rot", "root_pos", "ball_pos", "target_pos", "phase", "swing_type_cycle")
+
+
+def eval_settings(episode_length=600, body_of_smpl=None):
+    """The settings of `v2p_tennis_eval_step` on top of task_settings(...), as a plain dict.  episode_length: cfg env.episodeLength
+    (mvae_controller_vis.py:66, default 600); body_of_smpl [24]: `_mujoco_2_smpl`, the engine's body of SMPL joint s - the record needs it."""
+    if body_of_smpl is not None:
+        body_of_smpl = tuple(int(b) for b in body_of_smpl)
+        if sorted(body_of_smpl) != list(range(24)) or body_of_smpl[0] != 0:
+            raise ValueError("eval_settings: body_of_smpl must be a permutation of 0..23 with the root first")
+    return dict(episode_length=int(episode_length), body_of_smpl=body_of_smpl)
+
+
+def meters_reset(n):
+    """The four meters before their first update (`AverageMeterUnSync.reset`, utils/common.py:46-50) as arrays [4,n]: avg 1, the rest 0."""
+    return dict(meter_sum=np.zeros((4, n), _f), meter_count=np.zeros((4, n), np.int64), meter_avg=np.ones((4, n), _f), meter_max=np.zeros((4, n), _f))
+
+
+def eval_step_reference(st, est, s, dt=np.float32):
+    """One evaluation step on arrays: `task_step_reference` with `MVAEControllerVis._compute_reset` (mvae_controller_vis.py:64-79) in
+    place of the training law and `_compute_stats` (:81-95) in place of the `_distance` sum.  `est`: eval_settings(...); `s`: the
+    arrays of task_step_reference plus the four meter arrays [4,n] (METER_FIELDS, rows in the order of METER_NAMES).  dt float64 states
+    the float meter values (bounce error, sums, avg) in double.  Returns every array the step writes; nothing in `s` is modified."""
+    A = lambda k, t=None: np.array(s[k], dtype=t)
+    o = task_step_reference(dict(st, early_termination=False), s)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        hit, tar_action = o["has_racket_contact"].astype(bool), A("tar_action", np.int64)
+        ball, root = A("ball_state", _f), A("rb_state", _f).reshape(len(hit), 24, 13)[:, 0, 0:3]
+        terminate = o["progress"] > est["episode_length"]
+        in_time = o["tar_time"] >= A("tar_time_total", np.int64)
+        reaction = (hit & (tar_action == 0) & A("has_bounce").astype(bool) & in_time) | (~hit & in_time)
+        recovery = (tar_action == 1) & (hit | (ball[:, 1] < root[:, 1] - _f(1)) | (np.abs(ball[:, 8]) < _f(2)))
+        reaction, recovery = reaction | terminate, recovery & ~terminate
+        est_in = o["est_bounce_in"].astype(bool)
+        g = o["est_bounce_pos"].astype(dt) - A("target_bounce_pos", dt)
+        err = np.sqrt(g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1] + g[:, 2] * g[:, 2])
+        vals = [hit.astype(dt), (A("swing_type_cycle", np.int64) == 1).astype(dt), est_in.astype(dt), err]
+        m = {k: A(k, np.int64 if k == "meter_count" else dt) for k in METER_FIELDS}
+        for k, (val, on) in enumerate(zip(vals, (recovery, recovery, recovery, recovery & est_in))):
+            m["meter_sum"][k] = np.where(on, m["meter_sum"][k] + val, m["meter_sum"][k])
+            m["meter_count"][k] += on
+            m["meter_avg"][k] = np.where(on, m["meter_sum"][k] / m["meter_count"][k].astype(dt), m["meter_avg"][k])
+            m["meter_max"][k] = np.where(on & (val > m["meter_max"][k]), val, m["meter_max"][k])
+    o.update(m, reset=terminate.astype(np.int64), terminate=terminate.astype(np.int64), reset_reaction=reaction, reset_recovery=recovery, distance=A("distance", _f))
+    return o
+
+
+def eval_record_reference(est, s, dt=np.float32):
+    """The frame the evaluation keeps of a step (mvae_controller_vis.py:140-146) on arrays: `_joint_rot` of `_update_state_from_sim` with
+    `_is_train` false (humanoid_smpl_im_mvae.py:813-820) from `rb_state` and `dof_pos` [n,69], root, ball and target positions, phase and
+    swing type.  Returns a dict under RECORD_NAMES, arrays [n, ...]."""
+    from ..ref_rotations import quat_to_angle_axis_reference
+
+    if est["body_of_smpl"] is None:
+        raise ValueError("eval_record_reference: eval_settings(body_of_smpl=...) is required for the record")
+    rb = np.asarray(s["rb_state"], dtype=_f).reshape(-1, 24, 13)
+    n = len(rb)
+    root_rot = quat_to_angle_axis_reference(rb[:, 0][:, [6, 3, 4, 5]], dt, wide_atan2=True)  # (as the kernel: one rounding, whatever the library)
+    joints = np.concatenate([root_rot[:, None], np.asarray(s["dof_pos"], dtype=_f).reshape(n, 23, 3).astype(dt)], 1)[:, list(est["body_of_smpl"])]
+    return dict(joint_rot=joints, root_pos=rb[:, 0, 0:3].copy(), ball_pos=np.array(s["ball_state"], dtype=_f)[:, 0:3], target_pos=np.array(s["target_bounce_pos"], dtype=_f),
+                phase=np.array(s["phase_pred"], dtype=_f), swing_type_cycle=np.array(s["swing_type_cycle"], dtype=np.int64))
+
+
+def eval_structs(est, n, meters, record=None, dof_state=None):
+    """(v2p_tennis_eval_cfg, v2p_tennis_eval_buffers) of eval_settings(...), the four meter tensors [4,n] (dict under METER_FIELDS) and,
+    for a record, its six tensors [F,n,...] (dict under RECORD_NAMES) with the engine's `dof_state` [n,69,2].  Every size is checked against
+    n here: the kernel trusts them."""
+    want = dict(meter_sum=torch.float32, meter_count=torch.int64, meter_avg=torch.float32, meter_max=torch.float32)
+    for k, dtype in want.items():
+        t = meters.get(k)
+        if t is None:
+            raise ValueError("evaluation step: meter array %s is missing" % k)
+        if not t.is_cuda or not t.is_contiguous() or t.dtype != dtype or tuple(t.shape) != (4, n):
+            raise RuntimeError("evaluation step: %s must be a contiguous %s GPU tensor [4,%d] (there is no CPU path)" % (k, dtype, n))
+    ec = _lib.TennisEvalCfg(episode_length=est["episode_length"], num_frames=0)
+    x = _lib.TennisEvalBuffers()
+    for k in METER_FIELDS:
+        getattr(x, k)[:] = [meters[k][i].data_ptr() for i in range(4)]
+    if record is not None:
+        if est["body_of_smpl"] is None or dof_state is None:
+            raise ValueError("evaluation step: a record needs eval_settings(body_of_smpl=...) and the engine's dof_state")
+        F = int(record["phase"].shape[0])
+        shapes = dict(joint_rot=(F, n, 24, 3), root_pos=(F, n, 3), ball_pos=(F, n, 3), target_pos=(F, n, 3), phase=(F, n), swing_type_cycle=(F, n), dof_state=(n * 69, 2))
+        for k, t in list(record.items()) + [("dof_state", dof_state)]:
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != (torch.int64 if k == "swing_type_cycle" else torch.float32):
+                raise RuntimeError("evaluation step: %s must be a contiguous GPU tensor of its type (there is no CPU path)" % k)
+            if t.numel() != int(np.prod(shapes[k])) or (k != "dof_state" and tuple(t.shape) != shapes[k]):
+                raise ValueError("evaluation step: %s is %s, not %s" % (k, tuple(t.shape), shapes[k]))
+        ec.num_frames = F
+        ec.body_of_smpl[:] = est["body_of_smpl"]
+        x.dof_state = dof_state.data_ptr()
+        for k in RECORD_NAMES:
+            setattr(x, k, record[k].data_ptr())
+    return ec, x
+
+
+def launch_eval_step(st, est, tensors, n, meters, record=None, dof_state=None, frame=0, structs=None):
+    """v2p_tennis_eval_step on a dict of device tensors named like v2p_tennis_buffers; returns the names string of the reward law.
+    structs: what `eval_structs` made of the same meters and record before (a caller that steps every frame keeps it)."""
+    lib = _lib.load()
+    ec, x = structs or eval_structs(est, int(n), meters, record, dof_state)  # (refusals first: nothing below touches a device)
+    c = cfg_struct(st, tensors["traj_out_x"].shape, tensors["traj_out_y"].shape)
+    b = buffers_struct(tensors)
+    names = C.c_char_p()
+    dev = tensors["obs"].device
+    with torch.cuda.device(dev):
+        _lib.check(lib.v2p_tennis_eval_step(C.byref(c), C.byref(ec), int(n), C.byref(b), C.byref(x), int(frame), C.byref(names), _lib.current_stream(dev)),
+                   "v2p_tennis_eval_step")
+    return names.value.decode()
 
 
 # ------------------------------------------------------------------------------------------------------------------ the actions
@@ -901,3 +1024,99 @@ class TennisControllerTask:
         self.extras["terminate"] = self._terminate_buf
         self.extras["sub_rewards"] = self._sub_rewards
         self.extras["sub_rewards_names"] = self._sub_rewards_names
+
+
+# ------------------------------------------------------------------------------------------------------------------ the evaluation
+class Meter:
+    """One `AverageMeterUnSync` (utils/common.py:34-63) of the evaluation: `.sum`, `.avg`, `.max` float32 and `.count` int64, device
+    tensors [N] - rows of the controller's four [4,N] arrays, which the step kernel updates."""
+
+    def __init__(self, sum, count, avg, max):
+        self.sum, self.count, self.avg, self.max = sum, count, avg, max
+
+
+class TennisControllerEval(TennisControllerTask):
+    """`MVAEControllerVis` (vid2player/env/tasks/mvae_controller_vis.py, what `run.py --test` builds) without the viewer: the training task
+    with the test-mode episode law, the four meters `hit_rate`, `fh_ratio`, `bounce_in_rate`, `bounce_in_pos_error` and the record of
+    what the evaluation hands on, all in the step's one launch (`v2p_tennis_eval_step`).  cfg env.episodeLength (default 600) is the
+    strict bound of the law; enableEarlyTermination is refused - the law ignores it.  Everything else is `TennisControllerTask`'s: the
+    generator (built with is_train false), the target, the low-level policy, `reset(ids)`, `reset_by_flags()`.  The meters are not
+    zeroed when an env resets (the reference does not); `_distance` stands still."""
+
+    def __init__(self, task, cfg, params=traj_out_params, seed=None):
+        env = dict(cfg.get("env") or {})
+        if env.get("enableEarlyTermination"):
+            raise ValueError("TennisControllerEval: cfg env.enableEarlyTermination is set, and the test-mode episode law (MVAEControllerVis._compute_reset) "
+                             "ignores it: an episode ends only when progress_buf > episodeLength")
+        env.setdefault("episodeLength", 600)
+        super().__init__(task, dict(cfg, env=env), params, seed)
+        from ..mvae_target import tree_from_model
+
+        smpl_of_body = tree_from_model(task.body_names, task.body_model.parents)[1]
+        self.eval_settings = eval_settings(self._max_episode_length, [smpl_of_body.index(j) for j in range(24)])
+        n = self.num_envs
+        self._meters = {k: torch.as_tensor(v, device=self.device) for k, v in meters_reset(n).items()}
+        for i, name in enumerate(METER_NAMES):
+            setattr(self, name, Meter(*(self._meters[k][i] for k in METER_FIELDS)))
+        self.frame_index = 0
+        self._record = self._eval_structs = None
+
+    def start_record(self, num_frames):
+        """Allocate the record for `num_frames` steps (cfg env.num_rec_frames of the reference) and start at frame 0; rows of frames not
+        yet written are NaN / -1.  The arrays are frame-major [F,N,...]: the `*_all` properties give the reference's [N,f,...] views."""
+        F, n = int(num_frames), self.num_envs
+        if F < 1:
+            raise ValueError("start_record: num_frames %d < 1" % F)
+        f = dict(dtype=torch.float32, device=self.device)
+        nan = float("nan")
+        self._record = dict(joint_rot=torch.full((F, n, 24, 3), nan, **f), root_pos=torch.full((F, n, 3), nan, **f), ball_pos=torch.full((F, n, 3), nan, **f),
+                            target_pos=torch.full((F, n, 3), nan, **f), phase=torch.full((F, n), nan, **f),
+                            swing_type_cycle=torch.full((F, n), -1, dtype=torch.long, device=self.device))
+        self.frame_index, self._eval_structs = 0, None
+
+    def _launch_step(self):
+        rec = self._record
+        if rec is not None and self.frame_index >= rec["phase"].shape[0]:
+            raise RuntimeError("TennisControllerEval: the record holds %d frames and all are written (start_record)" % rec["phase"].shape[0])
+        if self._eval_structs is None:  # (the meters and the record stay where they are between two `start_record`s)
+            self._eval_structs = eval_structs(self.eval_settings, self.num_envs, self._meters, rec, None if rec is None else self.task._dof_state)
+        names = launch_eval_step(self.settings, self.eval_settings, self._tensors(), self.num_envs, self._meters, frame=self.frame_index, structs=self._eval_structs)
+        self.frame_index += 1  # (a host count, as the reference's)
+        return names
+
+    def _frames(self, name):
+        if self._record is None:
+            raise RuntimeError("TennisControllerEval: no record (start_record)")
+        t = self._record[name][:self.frame_index]
+        return t.permute(1, 0, *range(2, t.dim()))
+
+    joint_rot_all = property(lambda self: self._frames("joint_rot"))      # [N,f,24,3]
+    root_pos_all = property(lambda self: self._frames("root_pos"))        # [N,f,3]
+    ball_pos_all = property(lambda self: self._frames("ball_pos"))
+    target_pos_all = property(lambda self: self._frames("target_pos"))
+    phase_all = property(lambda self: self._frames("phase"))              # [N,f]
+    swing_type_all = property(lambda self: self._frames("swing_type_cycle"))
+
+    def select_best(self):
+        """The candidate env ids of mvae_controller_vis.py:149-156 (device tensor): envs with `bounce_in_rate.avg > 0.95` and
+        `fh_ratio.avg < 0.6`, sorted by the distance their root travelled over the record, descending.  Torch, once, after the run."""
+        return select_best(self.root_pos_all, self.bounce_in_rate.avg, self.fh_ratio.avg)
+
+    def summary(self):
+        """{meter: mean of its `avg` over the envs with count > 0 (NaN without one), meter + '_envs': their number} - how a controller is
+        judged.  One host read, after the run."""
+        on = self._meters["meter_count"] > 0
+        envs = on.sum(1)
+        mean = (self._meters["meter_avg"].double() * on).sum(1) / envs
+        got = torch.cat([mean, envs.double()]).cpu().tolist()
+        out = {name: got[i] for i, name in enumerate(METER_NAMES)}
+        out.update({name + "_envs": int(got[4 + i]) for i, name in enumerate(METER_NAMES)})
+        return out
+
+
+def select_best(root_pos_all, bounce_in_rate_avg, fh_ratio_avg):
+    """mvae_controller_vis.py:151-154 on tensors: root_pos_all [N,f,3], the two `avg` rows [N]."""
+    dist = (root_pos_all[:, 1:] - root_pos_all[:, :-1]).norm(dim=-1).sum(dim=-1)
+    candidates = (bounce_in_rate_avg > 0.95) & (fh_ratio_avg < 0.6)
+    ids = candidates.nonzero(as_tuple=False).flatten()
+    return ids[torch.argsort(dist[candidates], descending=True)]
