@@ -1137,6 +1137,69 @@ int v2p_ctl_pair_reset_begin(int64_t n, int64_t* flags /*[n], made whole*/, cons
 int v2p_tennis_dual_serve_flagged(int64_t n, const int64_t* flags /*[n]*/, int32_t serve_from, const float* racket_pos /*[n,3]*/, float* ball_state /*[n,13]*/,
                                   const float* draws /*[n/2,3], nullable*/, const v2p_serve_rule* rule /*nullable with draws*/, void* stream);
 int v2p_ctl_pair_reset_end(int64_t n, int64_t* flags /*[n], cleared*/, void* stream);
+
+/* ---- the record of a match run (vid2player/env/tasks/mvae_controller_vis_dual.py:156-195: MVAEControllerVisDual.render_vis with cfg
+ * env.record, called once after the first reset and after every control step, players/v2p_player.py:142,150) without a host read (the
+ * reference: six .cpu() copies per step, a nonzero() and Python lists).
+ *   frame   env e's frame goes to slot p = progress[e] of its own L = record_length slots of the six env-major arrays: `_joint_rot`
+ *           (the row of v2p_tennis_eval_buffers.joint_rot, the same device lines), root and ball position, phase, swing type,
+ *           tar_action.  p outside [0, L) (the reference would raise, or wrap below zero): nothing is stored and overflow[e] = 1.
+ *           `target_pos_all` is allocated by the reference and never written in the dual class: it is left out.
+ *   select  a pair (2k, 2k+1) is finished when either word of `reset` is not 0; d = distance[2k] + distance[2k+1] (one float32 add;
+ *           a NaN sum is no candidate).  The candidate is the lowest finished pair that reaches the maximum of d - only this one pair
+ *           is considered in a step.  It is inserted iff the list is empty or d > the last entry's, strict - so a candidate no better
+ *           than the current worst is dropped even while the list holds fewer than num_best - in front of the first entry with
+ *           d > entry (equal entries stay ahead); the list is cut to num_best.  best_distance / best_pair / best_nframes are by rank,
+ *           best first; best_slot[rank] is the storage slot holding the rank's frames (a free one, or the evicted entry's), so frames
+ *           are never shifted.  nframes = min(progress[2k], L); slots [0, nframes) of both envs are copied to
+ *           best_*[slot, 0..1, 0..nframes-1] - the slot written this very step lies outside, as in the reference; what a storage slot
+ *           held behind nframes stays.  decision = {pair, storage slot, nframes}, or {-1, -1, 0} without an insertion.
+ * No atomics: two runs give the same bits. */
+#define V2P_MATCH_RECORD_MAX_BEST 16
+#define V2P_MATCH_RECORD_MAX_LENGTH (1 << 20)
+typedef struct {
+    int64_t record_length;          /* L, 1..V2P_MATCH_RECORD_MAX_LENGTH (the reference's hard-coded 1800) */
+    int32_t num_best;               /* cfg env.num_eg, 1..V2P_MATCH_RECORD_MAX_BEST */
+    int32_t body_of_smpl[24];       /* `_mujoco_2_smpl`: the engine's body of SMPL joint s; [0] = 0, a permutation */
+} v2p_match_record_cfg;
+typedef struct {                    /* DEVICE buffers, all required */
+    /* read only */
+    const float* rb_state;          /* [N,24,13] */
+    const float* dof_state;         /* [N,69,2] the engine's DoF (position, velocity) pairs, body order */
+    const float* ball_state;        /* [N,13] */
+    const float* phase_pred;        /* [N] */
+    const int64_t* swing_type_cycle; /* [N] */
+    const int64_t* tar_action;      /* [N] */
+    const int64_t* progress;        /* [N] after the step's increment */
+    const int64_t* reset;           /* [N] */
+    const float* distance;          /* [N] */
+    /* the record, written by frame and read by select */
+    float* joint_rot_all;           /* [N,L,24,3] */
+    float* root_pos_all;            /* [N,L,3] */
+    float* ball_pos_all;            /* [N,L,3] */
+    float* phase_all;               /* [N,L] */
+    int64_t* swing_type_all;        /* [N,L] */
+    int64_t* tar_action_all;        /* [N,L] */
+    int32_t* overflow;              /* [N] */
+    /* the best list, read and written by select; best_count 0 before the first insertion */
+    float* best_distance;           /* [num_best] by rank */
+    int32_t* best_pair;             /* [num_best] */
+    int32_t* best_nframes;          /* [num_best] */
+    int32_t* best_slot;             /* [num_best] rank -> storage slot */
+    int32_t* best_count;            /* [1] */
+    int32_t* decision;              /* [3] */
+    float* best_joint_rot;          /* [num_best,2,L,24,3] by storage slot */
+    float* best_root_pos;           /* [num_best,2,L,3] */
+    float* best_ball_pos;           /* [num_best,2,L,3] */
+    float* best_phase;              /* [num_best,2,L] */
+    int64_t* best_swing_type;       /* [num_best,2,L] */
+    int64_t* best_tar_action;       /* [num_best,2,L] */
+} v2p_match_record_buffers;
+/* Refused before any HIP call (V2P_ERR_INVALID, a message that names the call): a null cfg / buffers, n <= 0, an odd n, n above 2^31-1,
+ * a null array, record_length or num_best outside their ranges, body_of_smpl that is no permutation with [0] = 0.  select launches the
+ * selection (one workgroup) and the copy (a grid for 2 L frames, which returns at once without an insertion). */
+int v2p_match_record_frame(const v2p_match_record_cfg* cfg, int64_t n, const v2p_match_record_buffers* buffers, void* stream);
+int v2p_match_record_select(const v2p_match_record_cfg* cfg, int64_t n, const v2p_match_record_buffers* buffers, void* stream);
 /* The loss head of V2PAgent.calc_gradients (v2p_agent.py:329-362, 395-397; learning/common_agent.py:442-450, 491-520 with clip_value
  * False; PhysicsMVAEController.get_aux_losses) under a fixed sigma, forward and backward.  With row r of the minibatch and
  * j = idx ? idx[r] : r its row of the epoch's dataset:

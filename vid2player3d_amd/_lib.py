@@ -124,6 +124,25 @@ class TennisEvalBuffers(C.Structure):
                 ("ball_pos", vp), ("target_pos", vp), ("phase", vp), ("swing_type_cycle", vp)]
 
 
+MATCH_RECORD_MAX_BEST, MATCH_RECORD_MAX_LENGTH = 16, 1 << 20  # V2P_MATCH_RECORD_MAX_*
+
+
+class MatchRecordCfg(C.Structure):
+    """v2p_match_record_cfg: the settings of the match record (v2p_match_record_frame / _select)."""
+    _fields_ = [("record_length", C.c_int64), ("num_best", C.c_int32), ("body_of_smpl", C.c_int32 * 24)]
+
+
+MATCH_RECORD_INPUT_NAMES = ("rb_state", "dof_state", "ball_state", "phase_pred", "swing_type_cycle", "tar_action", "progress", "reset", "distance")
+MATCH_RECORD_FRAME_NAMES = ("joint_rot", "root_pos", "ball_pos", "phase", "swing_type", "tar_action")  # the six `*_all` arrays and their `best_*` storage
+MATCH_RECORD_TABLE_NAMES = ("best_distance", "best_pair", "best_nframes", "best_slot", "best_count", "decision")
+MATCH_RECORD_BUFFER_NAMES = (MATCH_RECORD_INPUT_NAMES + tuple(k + "_all" for k in MATCH_RECORD_FRAME_NAMES) + ("overflow",) + MATCH_RECORD_TABLE_NAMES +
+                             tuple("best_" + k for k in MATCH_RECORD_FRAME_NAMES))
+
+
+class MatchRecordBuffers(C.Structure):
+    _fields_ = [(k, vp) for k in MATCH_RECORD_BUFFER_NAMES]
+
+
 class TennisDualCfg(C.Structure):
     """v2p_tennis_dual_cfg: what the two-player step and hand-over need on top of v2p_tennis_cfg."""
     _fields_ = [("grip_normal", (C.c_float * 3) * 2), ("in_grid", (C.c_double * 3) * 4), ("in_rows", C.c_int64), ("in_frames", C.c_int32)]
@@ -354,6 +373,8 @@ def load():
         "v2p_ctl_reset_end": [C.c_int64, vp, C.POINTER(CtlResetBuffers), vp],
         "v2p_ctl_pair_reset_begin": [C.c_int64, vp, C.POINTER(CtlResetBuffers), C.c_int32, vp],
         "v2p_ctl_pair_reset_end": [C.c_int64, vp, vp],
+        "v2p_match_record_frame": [C.POINTER(MatchRecordCfg), C.c_int64, C.POINTER(MatchRecordBuffers), vp],
+        "v2p_match_record_select": [C.POINTER(MatchRecordCfg), C.c_int64, C.POINTER(MatchRecordBuffers), vp],
         "v2p_tennis_dual_serve_flagged": [C.c_int64, vp, C.c_int32, vp, vp, vp, C.POINTER(ServeRule), vp],
         "v2p_mvae_dual_reset_flagged": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), C.POINTER(MvaeRacket), vp, vp, vp, C.POINTER(MvaeRootRule), vp,
                                         C.c_int64, vp],
@@ -391,6 +412,7 @@ EXPORTED_SYMBOLS = (
     "v2p_mvae_reset_flagged", "v2p_mvae_target_reset_flagged", "v2p_env_push_state_flagged", "v2p_ctl_reset_begin", "v2p_ctl_reset_end",
     "v2p_ctl_pair_reset_begin", "v2p_ctl_pair_reset_end", "v2p_tennis_dual_serve_flagged", "v2p_mvae_dual_reset_flagged",
     "v2p_tennis_eval_step",
+    "v2p_match_record_frame", "v2p_match_record_select",
 )
 
 

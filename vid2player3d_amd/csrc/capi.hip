@@ -10,6 +10,7 @@
 #include "controller_actions.hpp"
 #include "ctl_ppo.hpp"
 #include "flag_reset.hpp"
+#include "match_record.hpp"
 #include "mvae_player.hpp"
 #include "mvae_target.hpp"
 #include "pair_reset.hpp"
@@ -682,6 +683,43 @@ int v2p_mvae_dual_reset_flagged(const v2p_mvae_cfg* c, int64_t num_envs, const v
     const v2p_mvae_cfg (&c2)[2] = *reinterpret_cast<const v2p_mvae_cfg(*)[2]>(c);
     const v2p_mvae_weights (&w2)[2] = *reinterpret_cast<const v2p_mvae_weights(*)[2]>(w);
     return launch_mvae_dual_reset_flagged(c2, num_envs, w2, *b, *racket, flags, init_feature, root_xy, rule ? *rule : none, joint_pos_bind_rel, (hipStream_t)stream);
+}
+
+// ---- the record of a match run (match_record.hip)
+static int match_record_check(const char* fn, const v2p_match_record_cfg* c, int64_t n, const v2p_match_record_buffers* b) {
+    if (!c || !b) { set_error("%s: null cfg / buffers", fn); return V2P_ERR_INVALID; }
+    if (n <= 0) { set_error("%s: n %lld <= 0", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (n & 1) { set_error("%s: n %lld is odd (envs 2k and 2k+1 are a pair)", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (n > INT32_MAX) { set_error("%s: n %lld above 2^31-1 (best_pair holds the pair in 32 bits)", fn, (long long)n); return V2P_ERR_INVALID; }
+    if (c->record_length < 1 || c->record_length > V2P_MATCH_RECORD_MAX_LENGTH) {
+        set_error("%s: record_length %lld outside 1..%d", fn, (long long)c->record_length, V2P_MATCH_RECORD_MAX_LENGTH);
+        return V2P_ERR_INVALID;
+    }
+    if (c->num_best < 1 || c->num_best > V2P_MATCH_RECORD_MAX_BEST) { set_error("%s: num_best %d outside 1..%d", fn, c->num_best, V2P_MATCH_RECORD_MAX_BEST); return V2P_ERR_INVALID; }
+    const int fault = match_record_body_fault(*c);
+    if (fault >= 0) {
+        set_error("%s: body_of_smpl[%d] = %d: not a permutation of 0..%d with the root body first", fn, fault, c->body_of_smpl[fault], V2P_NUM_BODIES - 1);
+        return V2P_ERR_INVALID;
+    }
+    const void* arrays[] = {b->rb_state, b->dof_state, b->ball_state, b->phase_pred, b->swing_type_cycle, b->tar_action, b->progress, b->reset, b->distance,
+                            b->joint_rot_all, b->root_pos_all, b->ball_pos_all, b->phase_all, b->swing_type_all, b->tar_action_all, b->overflow,
+                            b->best_distance, b->best_pair, b->best_nframes, b->best_slot, b->best_count, b->decision,
+                            b->best_joint_rot, b->best_root_pos, b->best_ball_pos, b->best_phase, b->best_swing_type, b->best_tar_action};
+    for (size_t i = 0; i < sizeof(arrays) / sizeof(arrays[0]); ++i)
+        if (!arrays[i]) { set_error("%s: null array (field %d of v2p_match_record_buffers)", fn, (int)i); return V2P_ERR_INVALID; }
+    return V2P_OK;
+}
+
+int v2p_match_record_frame(const v2p_match_record_cfg* c, int64_t n, const v2p_match_record_buffers* b, void* stream) {
+    const int rc = match_record_check("v2p_match_record_frame", c, n, b);
+    if (rc != V2P_OK) return rc;
+    return launch_match_record_frame(*c, n, *b, (hipStream_t)stream);
+}
+
+int v2p_match_record_select(const v2p_match_record_cfg* c, int64_t n, const v2p_match_record_buffers* b, void* stream) {
+    const int rc = match_record_check("v2p_match_record_select", c, n, b);
+    if (rc != V2P_OK) return rc;
+    return launch_match_record_select(*c, n, *b, (hipStream_t)stream);
 }
 
 int v2p_mvae_target_actions(const v2p_mvae_target_cfg* c, int64_t n, const float* actions_in, const v2p_mvae_target_buffers* b, float* actions_out, void* stream) {

@@ -10,14 +10,12 @@
 // `distance` is not touched (`_compute_stats` replaces the training task's), a NaN in the row and a root outside the court end nothing.
 #include "ref_rotations.hpp"
 #include "tennis_eval.hpp"
+#include "tennis_pose_dev.hpp"
 #include "tennis_task_dev.hpp"
 
 namespace v2p {
 
 namespace {
-
-constexpr int TE_JOINTS = 24;
-constexpr int TE_PACK = 12;  // joints per 64-bit word of the packed joint table, 5 bits each
 
 struct TennisEvalArgs {
     TennisArgs a;
@@ -37,20 +35,6 @@ __device__ inline void te_meter(const v2p_tennis_eval_buffers& x, int m, int64_t
     x.meter_count[m][e] = count;
     x.meter_avg[m][e] = sum / (float)count;
     x.meter_max[m][e] = val > top ? val : top;
-}
-
-// quaternion_to_angle_axis of (w, x, y, z) as ref_quat_to_angle_axis states it, with its one arctangent evaluated in double and rounded
-// once.  atan2f is correctly rounded in no library, and the device's and a host's differ in the last bits of one result in six; the
-// double's rounding is the correctly rounded float for all but one argument in some 2^29, so the record's joint 0 is the same bits
-// here and in the numpy statement (ref_rotations.py, wide_atan2).  One value per env and step.  (torch_safe_atan2's shift never
-// applies: s >= 1e-3.)
-__device__ inline void te_quat_to_angle_axis(const float* q, float* aa) {
-    const float s2 = q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-    const float s = sqrtf(ref_clamp_min(s2, 1e-6f));
-    const float at = q[0] < 0.f ? (float)atan2(-(double)s, -(double)q[0]) : (float)atan2((double)s, (double)q[0]);
-    const float two_theta = 2.f * at;
-    const float k = s2 > 0.f ? ref_szd(two_theta, s) : 2.f;
-    aa[0] = q[1] * k; aa[1] = q[2] * k; aa[2] = q[3] * k;
 }
 
 __global__ __launch_bounds__(TT_WAVE* TT_WPB) void tennis_eval_kernel(const TennisEvalArgs h) {
@@ -180,16 +164,7 @@ __global__ __launch_bounds__(TT_WAVE* TT_WPB) void tennis_eval_kernel(const Tenn
     // ---- the record's frame (:140-146): the lanes write the env's 72 floats of `_joint_rot`, lanes 0..2 the three positions
     if (x.joint_rot) {
         const int64_t at = h.frame * a.rows + e;
-        const float q[4] = {rb[6], rb[3], rb[4], rb[5]};  // the root link's (x, y, z, w) read as (w, x, y, z)
-        float aa[3];
-        te_quat_to_angle_axis(q, aa);
-        for (int i = lane; i < TE_JOINTS * 3; i += TT_WAVE) {
-            const int j = i / 3, ax = i % 3;
-            const int body = (int)((j < TE_PACK ? h.body_of_smpl[0] : h.body_of_smpl[1]) >> (5 * (j % TE_PACK))) & 31;
-            float v = ax == 0 ? aa[0] : (ax == 1 ? aa[1] : aa[2]);
-            if (body > 0) v = x.dof_state[(e * (3 * (TE_JOINTS - 1)) + (body - 1) * 3 + ax) * 2];
-            x.joint_rot[at * (TE_JOINTS * 3) + i] = v;
-        }
+        te_pose_row(rb, x.dof_state, e, h.body_of_smpl, lane, TT_WAVE, x.joint_rot, at);  // (tennis_pose_dev.hpp)
         if (lane < 3) {
             x.root_pos[at * 3 + lane] = rb[lane];
             x.ball_pos[at * 3 + lane] = ball[lane];
@@ -232,10 +207,7 @@ int launch_tennis_eval_step(const v2p_tennis_cfg& c, const v2p_tennis_eval_cfg& 
     h.x = x;
     h.episode_length = ec.episode_length;
     h.frame = frame;
-    for (int w = 0; w < TE_JOINTS / TE_PACK; ++w) {
-        h.body_of_smpl[w] = 0;
-        for (int j = 0; j < TE_PACK; ++j) h.body_of_smpl[w] |= (uint64_t)(ec.body_of_smpl[w * TE_PACK + j] & 31) << (5 * j);
-    }
+    te_pack_body_of_smpl(ec.body_of_smpl, h.body_of_smpl);
     const dim3 grid((unsigned)((n + TT_WPB - 1) / TT_WPB)), block(TT_WAVE * TT_WPB);
     hipLaunchKernelGGL(tennis_eval_kernel, grid, block, 0, s, h);
     return check_hip(hipGetLastError(), "tennis_eval_kernel");

@@ -366,18 +366,26 @@ def eval_step_reference(st, est, s, dt=np.float32):
     return o
 
 
+def pose_row_reference(body_of_smpl, rb_state, dof_pos, dt=np.float32):
+    """`_joint_rot` [n,24,3] of `_update_state_from_sim` with `_is_train` false (humanoid_smpl_im_mvae.py:813-820) from `rb_state`
+    [n,24,13] and `dof_pos` [n,69]: joint 0 from the root link's quaternion, joints 1..23 the DoF positions of body_of_smpl[j].  The one
+    statement of the device lines in csrc/tennis_pose_dev.hpp, which the evaluation step and the match record share."""
+    from ..ref_rotations import quat_to_angle_axis_reference
+
+    rb = np.asarray(rb_state, dtype=_f).reshape(-1, 24, 13)
+    n = len(rb)
+    root_rot = quat_to_angle_axis_reference(rb[:, 0][:, [6, 3, 4, 5]], dt, wide_atan2=True)  # (as the kernel: one rounding, whatever the library)
+    return np.concatenate([root_rot[:, None], np.asarray(dof_pos, dtype=_f).reshape(n, 23, 3).astype(dt)], 1)[:, list(body_of_smpl)]
+
+
 def eval_record_reference(est, s, dt=np.float32):
     """The frame the evaluation keeps of a step (mvae_controller_vis.py:140-146) on arrays: `_joint_rot` of `_update_state_from_sim` with
     `_is_train` false (humanoid_smpl_im_mvae.py:813-820) from `rb_state` and `dof_pos` [n,69], root, ball and target positions, phase and
     swing type.  Returns a dict under RECORD_NAMES, arrays [n, ...]."""
-    from ..ref_rotations import quat_to_angle_axis_reference
-
     if est["body_of_smpl"] is None:
         raise ValueError("eval_record_reference: eval_settings(body_of_smpl=...) is required for the record")
     rb = np.asarray(s["rb_state"], dtype=_f).reshape(-1, 24, 13)
-    n = len(rb)
-    root_rot = quat_to_angle_axis_reference(rb[:, 0][:, [6, 3, 4, 5]], dt, wide_atan2=True)  # (as the kernel: one rounding, whatever the library)
-    joints = np.concatenate([root_rot[:, None], np.asarray(s["dof_pos"], dtype=_f).reshape(n, 23, 3).astype(dt)], 1)[:, list(est["body_of_smpl"])]
+    joints = pose_row_reference(est["body_of_smpl"], rb, s["dof_pos"], dt)
     return dict(joint_rot=joints, root_pos=rb[:, 0, 0:3].copy(), ball_pos=np.array(s["ball_state"], dtype=_f)[:, 0:3], target_pos=np.array(s["target_bounce_pos"], dtype=_f),
                 phase=np.array(s["phase_pred"], dtype=_f), swing_type_cycle=np.array(s["swing_type_cycle"], dtype=np.int64))
 
