@@ -1200,6 +1200,47 @@ typedef struct {                    /* DEVICE buffers, all required */
  * selection (one workgroup) and the copy (a grid for 2 L frames, which returns at once without an insertion). */
 int v2p_match_record_frame(const v2p_match_record_cfg* cfg, int64_t n, const v2p_match_record_buffers* buffers, void* stream);
 int v2p_match_record_select(const v2p_match_record_cfg* cfg, int64_t n, const v2p_match_record_buffers* buffers, void* stream);
+
+/* ---- the two-hand backhand fix of a record (vid2player/env/tasks/humanoid_smpl_im_mvae.py:948-1031, optimize_two_hand_backhand with
+ * single=True, called as render_one_result calls it under cfg v2p fix_two_hand_backhand_post: mvae_controller_vis.py:181-190,
+ * mvae_controller_vis_dual.py:213-231).  T tracks of L slots each, one workgroup per track, one launch:
+ *   flags    frame f < nframes[t] of track t is flagged when swing_type == 2 and 2 < phase < 5; the F flagged frames are compacted in
+ *            frame order.  Frames that are not flagged are copied to `out`; slots behind nframes[t] are neither read nor written.
+ *   pose     all 24 joints of a flagged frame go angle_axis_to_rotation_matrix and rotation_matrix_to_angle_axis; the free arm's four
+ *            joints (wrist, elbow, shoulder, collar: SMPL 20, 18, 16, 13 for righthand != 0, else 21, 19, 17, 14) get delta added
+ *            in between.  Compacted frame i reads bind row i % num_bind (the reference's joint_pos_bind[:batch_size]).
+ *   law      target = 2 rb_pos[hand] - rb_pos[wrist] - rb_pos[0] (bodies 23, 22 / 18, 17) from the input pose with root position 0;
+ *            loss = mean|p_free - target| + 0.2 mean|delta| + 0.5 mean|delta[1:] - delta[:-1].detach()| (free hand: body 18 / 23);
+ *            num_iters steps of Adam (lr 0.005, betas 0.9 / 0.999, eps 1e-8) as torch's single-tensor form runs it, from delta = 0.
+ * Every float operation is the one of the numpy statement (two_hand_fix.two_hand_fix_reference) in its order, sine / cosine / the
+ * closing arctangent evaluated in double and rounded once: the same bits.  No atomics, no host read, no allocation.
+ * A track holds at most V2P_TWO_HAND_FIX_MAX_FRAMES flagged frames - V2P_TWO_HAND_FIX_FRAMES_PER_THREAD per thread of its workgroup,
+ * whose delta and Adam moments stay in registers (at the cap the exchange of delta between neighbours takes 96 KB of the 160 KB of
+ * LDS).  A track above the cap is copied whole and overflow[t] = F; else overflow[t] = 0. */
+#define V2P_TWO_HAND_FIX_THREADS 256
+#define V2P_TWO_HAND_FIX_FRAMES_PER_THREAD 8
+#define V2P_TWO_HAND_FIX_MAX_FRAMES (V2P_TWO_HAND_FIX_THREADS * V2P_TWO_HAND_FIX_FRAMES_PER_THREAD)
+typedef struct {
+    int32_t num_iters;              /* >= 0 (the reference: 500) */
+    int32_t num_bind;               /* R >= 1, rows of `bind` */
+    int32_t smpl_parents[24];       /* the SMPL tree in SMPL joint order, root -1, a parent before its children */
+    int32_t smpl_of_body[24];       /* `_smpl_2_mujoco`: the SMPL joint of the engine's body b; [0] = 0, a permutation */
+} v2p_two_hand_fix_cfg;
+typedef struct {                    /* DEVICE buffers, all required */
+    const float* joint_rot;         /* [T,L,24,3] */
+    const float* phase;             /* [T,L] */
+    const int64_t* swing_type;      /* [T,L] */
+    const int32_t* nframes;         /* [T], clamped to 0..L */
+    const int32_t* righthand;       /* [T] */
+    const float* bind;              /* [num_bind,24,3] */
+    float* out;                     /* [T,L,24,3], no overlap with joint_rot */
+    int32_t* overflow;              /* [T] */
+} v2p_two_hand_fix_buffers;
+/* Refused before any HIP call (V2P_ERR_INVALID, a message that names the call): a null cfg / buffers / array, T < 0, L < 1 or above
+ * 2^31-1, num_iters < 0, num_bind < 1, a tree or a body table that is none, an arm that is not the chain collar - shoulder - elbow -
+ * wrist - hand of the law's joints, a chain from the root longer than 12 joints, an `out` that is or overlaps joint_rot (the other
+ * arrays are the caller's to keep apart from `out`).  T = 0 is a no-op. */
+int v2p_two_hand_fix(const v2p_two_hand_fix_cfg* cfg, int64_t num_tracks, int64_t track_length, const v2p_two_hand_fix_buffers* buffers, void* stream);
 /* The loss head of V2PAgent.calc_gradients (v2p_agent.py:329-362, 395-397; learning/common_agent.py:442-450, 491-520 with clip_value
  * False; PhysicsMVAEController.get_aux_losses) under a fixed sigma, forward and backward.  With row r of the minibatch and
  * j = idx ? idx[r] : r its row of the epoch's dataset:

@@ -20,13 +20,13 @@ mvae_target_reset_flagged_kernel, env_push_state_flagged_kernel, ctl_reset_begin
 env_push_state_kernel of task_ops.hip), and the pair reset by flags (mvae_dual_reset_flagged_kernel of mvae_player_dual_flagged.hip;
 ctl_pair_reset_begin_kernel / _end_kernel, tennis_dual_serve_flagged_kernel of pair_reset.hip), and the evaluation step
 (tennis_eval_kernel of tennis_eval.hip), and the match record (match_record_frame_kernel, match_record_select_kernel,
-match_record_copy_kernel of match_record.hip).  A kernel that only the new listing has is
+match_record_copy_kernel of match_record.hip), and the two-hand backhand fix (two_hand_fix_kernel of two_hand_fix.hip).  A kernel that only the new listing has is
 reported and does not count as a difference; one that only the old listing has does.
 usage: tools/kernel_identity.py <old.s>[,<old2.s>...] <new.s>[,<new2.s>...]   (a kernel is looked up in every listing of its side)"""
 import re
 import sys
 
-KERNELS = re.compile(r"^(_ZN\w*?(physics_ll_kernelI\w+?EEv|env_pre_kernelE|pair_scatter_kernelE|tennis_task_kernelI\w+?EEv|tennis_handover_kernelE|mvae_(?:dual_)?(?:step|reset)_kernelE|mvae_target_kernelI\w+?EEv|mvae_target_actions_kernelE|tennis_reset_kernelE|controller_actions_kernelE|mvae_reset_flagged_kernelE|mvae_target_reset_flagged_kernelE|env_push_state(?:_flagged)?_kernelE|ctl_reset_(?:begin|end)_kernelE|mvae_dual_reset_flagged_kernelE|ctl_pair_reset_(?:begin|end)_kernelE|tennis_dual_serve_flagged_kernelE|tennis_eval_kernelE|match_record_(?:frame|select|copy)_kernelE)\w*):")
+KERNELS = re.compile(r"^(_ZN\w*?(physics_ll_kernelI\w+?EEv|env_pre_kernelE|pair_scatter_kernelE|tennis_task_kernelI\w+?EEv|tennis_handover_kernelE|mvae_(?:dual_)?(?:step|reset)_kernelE|mvae_target_kernelI\w+?EEv|mvae_target_actions_kernelE|tennis_reset_kernelE|controller_actions_kernelE|mvae_reset_flagged_kernelE|mvae_target_reset_flagged_kernelE|env_push_state(?:_flagged)?_kernelE|ctl_reset_(?:begin|end)_kernelE|mvae_dual_reset_flagged_kernelE|ctl_pair_reset_(?:begin|end)_kernelE|tennis_dual_serve_flagged_kernelE|tennis_eval_kernelE|match_record_(?:frame|select|copy)_kernelE|two_hand_fix_kernelE)\w*):")
 # the enclosing namespaces: v2p, v2p::ll_lds, v2p::ll_regs, or v2p itself renamed with a suffix (how the register object was built
 # before the kernel had a namespace per build): _ZN3v2p17..., _ZN3v2p6ll_lds17..., _ZN3v2p7ll_regs17... -> _ZN@17...
 NAMESPACES = re.compile(r"_ZN\d+v2p(?:_[a-z]+)?(?:\d+ll_[a-z]+)?")

@@ -143,6 +143,22 @@ class MatchRecordBuffers(C.Structure):
     _fields_ = [(k, vp) for k in MATCH_RECORD_BUFFER_NAMES]
 
 
+TWO_HAND_FIX_THREADS, TWO_HAND_FIX_FRAMES_PER_THREAD = 256, 8  # V2P_TWO_HAND_FIX_*
+TWO_HAND_FIX_MAX_FRAMES = TWO_HAND_FIX_THREADS * TWO_HAND_FIX_FRAMES_PER_THREAD
+
+
+class TwoHandFixCfg(C.Structure):
+    """v2p_two_hand_fix_cfg: the settings of the two-hand backhand fix (v2p_two_hand_fix)."""
+    _fields_ = [("num_iters", C.c_int32), ("num_bind", C.c_int32), ("smpl_parents", C.c_int32 * 24), ("smpl_of_body", C.c_int32 * 24)]
+
+
+TWO_HAND_FIX_BUFFER_NAMES = ("joint_rot", "phase", "swing_type", "nframes", "righthand", "bind", "out", "overflow")
+
+
+class TwoHandFixBuffers(C.Structure):
+    _fields_ = [(k, vp) for k in TWO_HAND_FIX_BUFFER_NAMES]
+
+
 class TennisDualCfg(C.Structure):
     """v2p_tennis_dual_cfg: what the two-player step and hand-over need on top of v2p_tennis_cfg."""
     _fields_ = [("grip_normal", (C.c_float * 3) * 2), ("in_grid", (C.c_double * 3) * 4), ("in_rows", C.c_int64), ("in_frames", C.c_int32)]
@@ -375,6 +391,7 @@ def load():
         "v2p_ctl_pair_reset_end": [C.c_int64, vp, vp],
         "v2p_match_record_frame": [C.POINTER(MatchRecordCfg), C.c_int64, C.POINTER(MatchRecordBuffers), vp],
         "v2p_match_record_select": [C.POINTER(MatchRecordCfg), C.c_int64, C.POINTER(MatchRecordBuffers), vp],
+        "v2p_two_hand_fix": [C.POINTER(TwoHandFixCfg), C.c_int64, C.c_int64, C.POINTER(TwoHandFixBuffers), vp],
         "v2p_tennis_dual_serve_flagged": [C.c_int64, vp, C.c_int32, vp, vp, vp, C.POINTER(ServeRule), vp],
         "v2p_mvae_dual_reset_flagged": [C.POINTER(MvaeCfg), C.c_int64, C.POINTER(MvaeWeights), C.POINTER(MvaeBuffers), C.POINTER(MvaeRacket), vp, vp, vp, C.POINTER(MvaeRootRule), vp,
                                         C.c_int64, vp],
@@ -413,6 +430,7 @@ EXPORTED_SYMBOLS = (
     "v2p_ctl_pair_reset_begin", "v2p_ctl_pair_reset_end", "v2p_tennis_dual_serve_flagged", "v2p_mvae_dual_reset_flagged",
     "v2p_tennis_eval_step",
     "v2p_match_record_frame", "v2p_match_record_select",
+    "v2p_two_hand_fix",
 )
 
 

@@ -11,8 +11,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libv2p_rollout.so")
-SOURCES = ["capi.hip", "device_owner.hip", "model_compile.hip", "env.hip", "motion_state.hip", "task_ops.hip", "shape_compile.hip", "motion_build.hip", "physics.hip", "physics_ll.hip", "physics_ll_host.hip", "ball_rollout.hip", "tennis_task.hip", "tennis_eval.hip", "tennis_reset.hip", "controller_actions.hip", "mvae_player.hip", "mvae_player_dual.hip", "mvae_target.hip", "policy_io.hip", "ctl_ppo.hip", "mvae_player_flagged.hip", "flag_reset.hip", "mvae_player_dual_flagged.hip", "pair_reset.hip", "match_record.hip"]
-HEADERS = ["v2p_internal.hpp", "device_guards.hpp", "ll_schedule.hpp", "ll_forms.hpp", "ll_contact_setup.inc", "v2p_dev.hpp", "v2p_math.inc", "phys_math.hpp", "phys_common.hpp", "motion_sample.inc", "hull_gjk.hpp", "post_ops.inc", "strict_ops.inc", "tennis_task.hpp", "tennis_task_dev.hpp", "tennis_eval.hpp", "tennis_pose_dev.hpp", "match_record.hpp", "tennis_row.inc", "tennis_reset.hpp", "controller_actions.hpp", "philox.hpp", "mvae_player.hpp", "mvae_player_dev.hpp", "mvae_rows.inc", "mvae_target.hpp", "mvae_target_dev.hpp", "mvae_target_row.inc", "flag_reset.hpp", "pair_reset.hpp", "policy_io.hpp", "ctl_ppo.hpp", "obs_imitation_row.inc", "ref_rotations.hpp", os.path.join("..", "..", "include", "v2p_rollout.h")]
+SOURCES = ["capi.hip", "device_owner.hip", "model_compile.hip", "env.hip", "motion_state.hip", "task_ops.hip", "shape_compile.hip", "motion_build.hip", "physics.hip", "physics_ll.hip", "physics_ll_host.hip", "ball_rollout.hip", "tennis_task.hip", "tennis_eval.hip", "tennis_reset.hip", "controller_actions.hip", "mvae_player.hip", "mvae_player_dual.hip", "mvae_target.hip", "policy_io.hip", "ctl_ppo.hip", "mvae_player_flagged.hip", "flag_reset.hip", "mvae_player_dual_flagged.hip", "pair_reset.hip", "match_record.hip", "two_hand_fix.hip"]
+HEADERS = ["v2p_internal.hpp", "device_guards.hpp", "ll_schedule.hpp", "ll_forms.hpp", "ll_contact_setup.inc", "v2p_dev.hpp", "v2p_math.inc", "phys_math.hpp", "phys_common.hpp", "motion_sample.inc", "hull_gjk.hpp", "post_ops.inc", "strict_ops.inc", "tennis_task.hpp", "tennis_task_dev.hpp", "tennis_eval.hpp", "tennis_pose_dev.hpp", "match_record.hpp", "two_hand_fix.hpp", "tennis_row.inc", "tennis_reset.hpp", "controller_actions.hpp", "philox.hpp", "mvae_player.hpp", "mvae_player_dev.hpp", "mvae_rows.inc", "mvae_target.hpp", "mvae_target_dev.hpp", "mvae_target_row.inc", "flag_reset.hpp", "pair_reset.hpp", "policy_io.hpp", "ctl_ppo.hpp", "obs_imitation_row.inc", "ref_rotations.hpp", os.path.join("..", "..", "include", "v2p_rollout.h")]
 ARCH = "gfx950"
 
 
@@ -74,7 +74,7 @@ def compile_flags(source, regs=False):
     fl = list(BASE_FLAGS)
     if regs:
         fl += LL_REGS_FLAGS
-    if source in ("motion_state.hip", "task_ops.hip", "shape_compile.hip", "motion_build.hip", "tennis_task.hip", "tennis_eval.hip", "tennis_reset.hip", "controller_actions.hip", "mvae_player.hip", "mvae_player_dual.hip", "mvae_target.hip", "policy_io.hip", "ctl_ppo.hip", "mvae_player_flagged.hip", "flag_reset.hip", "mvae_player_dual_flagged.hip", "pair_reset.hip", "match_record.hip"):
+    if source in ("motion_state.hip", "task_ops.hip", "shape_compile.hip", "motion_build.hip", "tennis_task.hip", "tennis_eval.hip", "tennis_reset.hip", "controller_actions.hip", "mvae_player.hip", "mvae_player_dual.hip", "mvae_target.hip", "policy_io.hip", "ctl_ppo.hip", "mvae_player_flagged.hip", "flag_reset.hip", "mvae_player_dual_flagged.hip", "pair_reset.hip", "match_record.hip", "two_hand_fix.hip"):
         # the task-side kernels restate torch elementwise code: no FMA contraction, so that ill-conditioned spots of the
         # reference itself (acos of a dot product next to 1 in slerp / angle-axis) round the way torch rounds them
         fl = [f if f != "-ffp-contract=fast" else "-ffp-contract=off" for f in fl]

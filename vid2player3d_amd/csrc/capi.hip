@@ -16,6 +16,7 @@
 #include "pair_reset.hpp"
 #include "policy_io.hpp"
 #include "tennis_eval.hpp"
+#include "two_hand_fix.hpp"
 #include "tennis_reset.hpp"
 #include "tennis_task.hpp"
 #include "v2p_internal.hpp"
@@ -720,6 +721,28 @@ int v2p_match_record_select(const v2p_match_record_cfg* c, int64_t n, const v2p_
     const int rc = match_record_check("v2p_match_record_select", c, n, b);
     if (rc != V2P_OK) return rc;
     return launch_match_record_select(*c, n, *b, (hipStream_t)stream);
+}
+
+// ---- the two-hand backhand fix of a record (two_hand_fix.hip)
+int v2p_two_hand_fix(const v2p_two_hand_fix_cfg* c, int64_t num_tracks, int64_t track_length, const v2p_two_hand_fix_buffers* b, void* stream) {
+    const char* fn = "v2p_two_hand_fix";
+    if (!c || !b) { set_error("%s: null cfg / buffers", fn); return V2P_ERR_INVALID; }
+    if (num_tracks < 0 || num_tracks > INT32_MAX) { set_error("%s: num_tracks %lld outside 0..2^31-1", fn, (long long)num_tracks); return V2P_ERR_INVALID; }
+    if (track_length < 1 || track_length > INT32_MAX) { set_error("%s: track_length %lld outside 1..2^31-1", fn, (long long)track_length); return V2P_ERR_INVALID; }
+    if (c->num_iters < 0) { set_error("%s: num_iters %d < 0", fn, c->num_iters); return V2P_ERR_INVALID; }
+    if (c->num_bind < 1) { set_error("%s: num_bind %d < 1", fn, c->num_bind); return V2P_ERR_INVALID; }
+    if (const char* why = two_hand_fix_cfg_fault(*c)) { set_error("%s: %s", fn, why); return V2P_ERR_INVALID; }
+    const void* arrays[] = {b->joint_rot, b->phase, b->swing_type, b->nframes, b->righthand, b->bind, b->out, b->overflow};
+    for (size_t i = 0; i < sizeof(arrays) / sizeof(arrays[0]); ++i)
+        if (!arrays[i]) { set_error("%s: null array (field %d of v2p_two_hand_fix_buffers)", fn, (int)i); return V2P_ERR_INVALID; }
+    if (b->out == b->joint_rot) { set_error("%s: out is joint_rot (the fix works on a copy)", fn); return V2P_ERR_INVALID; }
+    if (num_tracks == 0) return V2P_OK;
+    {   // the rows of `out` are the frames' workspace during the steps: no byte of it may be one of joint_rot's
+        const uintptr_t bytes = (uintptr_t)num_tracks * (uintptr_t)track_length * 24u * 3u * sizeof(float);
+        const uintptr_t in0 = (uintptr_t)b->joint_rot, out0 = (uintptr_t)b->out;
+        if (in0 < out0 + bytes && out0 < in0 + bytes) { set_error("%s: out overlaps joint_rot (the fix works on a copy)", fn); return V2P_ERR_INVALID; }
+    }
+    return launch_two_hand_fix(*c, num_tracks, track_length, *b, (hipStream_t)stream);
 }
 
 int v2p_mvae_target_actions(const v2p_mvae_target_cfg* c, int64_t n, const float* actions_in, const v2p_mvae_target_buffers* b, float* actions_out, void* stream) {

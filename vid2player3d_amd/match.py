@@ -18,8 +18,8 @@ finish the `num_best` rallies with the largest summed `_distance` are kept, on t
 `v2p_match_record_select`, csrc/match_record.hip) - no `.cpu()`, no `nonzero()`, no host list.  `match_record_reference(rec, s)` states
 the law once in numpy; `MatchPlayer(..., recorder=...)` records a run; `MatchRecorder.best()` is the one host read and
 `ball_track(entry)` the ball a viewer would show (render_one_result:278-285).  `target_pos_all`, which the reference allocates and the
-dual class never writes, is left out.  Not built: the SMPL mesh, video / HTML output, `fix_two_hand_backhand_post` and the on-screen
-viewer branch of `render_vis`."""
+dual class never writes, is left out.  `best(fix_two_hand=...)` applies the two-hand backhand fix of cfg v2p `fix_two_hand_backhand_post`
+(two_hand_fix.py).  Not built: the SMPL mesh, video / HTML output and the on-screen viewer branch of `render_vis`."""
 import ctypes as C
 
 import numpy as np
@@ -252,14 +252,62 @@ class MatchRecorder:
         launch_record_frame(structs, self.num_envs, self.device)
         launch_record_select(structs, self.num_envs, self.device)
 
-    def best(self):
+    def best(self, fix_two_hand=None, num_iters=None):
         """The kept rallies, best first, as dicts {pair, distance, nframes, joint_rot [2,nframes,24,3], root_pos, ball_pos, phase,
-        swing_type, tar_action} of device tensors (views of the storage).  The one host read: the four tables and the count."""
+        swing_type, tar_action} of device tensors (views of the storage).  The one host read: the four tables and the count.
+        fix_two_hand: the two-hand backhand fix of `render_one_result` (mvae_controller_vis_dual.py:213-231) on `joint_rot`, one launch
+        for every kept rally and side (`two_hand_fix.fix_two_hand_backhand`, num_iters None: its 500); None follows cfg v2p
+        `fix_two_hand_backhand_post`.  A fixed `joint_rot` is a new tensor, the storage stays as recorded."""
         names = tuple(TABLE_DTYPES)
         host = torch.cat([self._arrays[k].view(torch.int32) for k in names] + [self.best_count]).cpu().numpy()
         K = self.num_best
         tables = {k: host[i * K:(i + 1) * K].view(TABLE_DTYPES[k]) for i, k in enumerate(names)}
-        return best_of(dict(self._arrays, best_count=host[4 * K:], **tables))
+        entries = best_of(dict(self._arrays, best_count=host[4 * K:], **tables))
+        if fix_two_hand is None:
+            fix_two_hand = bool(self.ctl.cfg_v2p.get("fix_two_hand_backhand_post"))
+        if fix_two_hand and entries:
+            self._fix_two_hand(entries, [int(tables["best_slot"][r]) for r in range(len(entries))], num_iters)
+        return entries
+
+    def fix_sides(self):
+        """[(skipped, righthand)] of the two sides, the reference's rule (mvae_controller_vis_dual.py:217-224): with `dual_mode:
+        different` cfg v2p `player[j]` and `righthand[j]`, else `player` and `righthand` (default True) for both; a side whose player
+        name starts with `federer` is skipped."""
+        from .two_hand_fix import skips_fix
+
+        v2p = self.ctl.cfg_v2p
+        sides = []
+        for j in range(2):
+            if v2p.get("dual_mode") == "different":
+                player, righthand = v2p["player"][j], v2p["righthand"][j]
+            else:
+                player, righthand = v2p.get("player"), v2p.get("righthand", True)
+            sides.append((skips_fix(player), bool(righthand)))
+        return sides
+
+    def fix_bind_rows(self):
+        """The reference's `_smpl.joint_pos_bind` [N,24,3], a row per env, from the attached imitation target."""
+        target = self.ctl._imitation_target
+        if target is None:
+            raise RuntimeError("MatchRecorder: the two-hand fix reads joint_pos_bind of the controller's imitation target, and none is attached")
+        from .two_hand_fix import bind_rows_of
+
+        return bind_rows_of(target)
+
+    def _fix_two_hand(self, entries, slots, num_iters):
+        from . import two_hand_fix as thf
+
+        K, L, sides = self.num_best, self.record_length, self.fix_sides()
+        nframes, righthand = np.zeros(2 * K, np.int32), np.zeros(2 * K, np.int32)
+        for e, slot in zip(entries, slots):
+            for j, (skipped, rh) in enumerate(sides):
+                nframes[2 * slot + j], righthand[2 * slot + j] = (0 if skipped else e["nframes"]), int(rh)
+        st = thf.fix_settings(self.ctl.task.body_names, self.ctl.task.body_model.parents)
+        dev = lambda a: torch.as_tensor(a, device=self.device)
+        out = thf.fix_two_hand_backhand(self.best_joint_rot.view(2 * K, L, 24, 3), self.best_phase.view(2 * K, L), self.best_swing_type.view(2 * K, L), dev(nframes),
+                                        dev(righthand), self.fix_bind_rows(), thf.NUM_ITERS if num_iters is None else num_iters, settings=st)
+        for e, slot in zip(entries, slots):
+            e["joint_rot"] = torch.stack([e["joint_rot"][j].clone() if skipped else out[2 * slot + j, :e["nframes"]] for j, (skipped, _) in enumerate(sides)])
 
     ball_track = staticmethod(ball_track)
 

@@ -15,7 +15,7 @@ There is no CPU path: a CPU device or a missing library is a RuntimeError.
 
 A two-player task (`dual_mode: different`, env i is player i % 2) takes joint_pos_bind [2,24,3] - the task's `_env_shape_ids` are the
 parities - and `smpl_beta` as a list of two; `pd_action_scale` / `pd_action_offset` stay one [69] pair for the batch, as in the reference.
-Not built: per-clip body shapes x two players (refused by the task), `obs_type: joint_pos`, `optimize_two_hand_backhand`, `update_mvae_from_sim`; `pd_action_scale` / `pd_action_offset`
+Not built: per-clip body shapes x two players (refused by the task), `obs_type: joint_pos`, `update_mvae_from_sim` (`optimize_two_hand_backhand` with single=True is two_hand_fix.py); `pd_action_scale` / `pd_action_offset`
 are the caller's arrays (the reference derives them from the actors' DoF limits, humanoid_smpl.py:368-410).
 """
 import ctypes as C

@@ -82,20 +82,26 @@ def quat_to_angle_axis_reference(q, dt=np.float32, probes=None, wide_atan2=False
     return (q[..., 1:] * k[..., None]).astype(dt)
 
 
-def rotmat_to_angle_axis_reference(m, dt=np.float32, probes=None):
-    """rotation_matrix_to_angle_axis (utils/konia_transform.py:631-655, through the wxyz quaternion): [..., 3, 3] -> [..., 3]."""
-    return quat_to_angle_axis_reference(rotmat_to_quat_reference(m, dt, probes), dt, probes)
+def rotmat_to_angle_axis_reference(m, dt=np.float32, probes=None, wide_atan2=False):
+    """rotation_matrix_to_angle_axis (utils/konia_transform.py:631-655, through the wxyz quaternion): [..., 3, 3] -> [..., 3].
+    wide_atan2: as quat_to_angle_axis_reference's."""
+    return quat_to_angle_axis_reference(rotmat_to_quat_reference(m, dt, probes), dt, probes, wide_atan2)
 
 
-def angle_axis_to_rotmat_reference(aa, dt=np.float32, probes=None):
-    """angle_axis_to_rotation_matrix (utils/konia_transform.py:282-333): [..., 3] -> [..., 3, 3]."""
+def angle_axis_to_rotmat_reference(aa, dt=np.float32, probes=None, wide_trig=False):
+    """angle_axis_to_rotation_matrix (utils/konia_transform.py:282-333): [..., 3] -> [..., 3, 3].  wide_trig: sine and cosine are
+    evaluated in float64 and rounded once to dt, as wide_atan2 does for the arctangent - what a kernel that does the same reproduces bit
+    for bit (csrc/two_hand_fix.hip)."""
     aa = np.asarray(aa, dtype=dt)
     rx, ry, rz = aa[..., 0], aa[..., 1], aa[..., 2]
     theta2 = rx * rx + ry * ry + rz * rz
     eps, one = dt(1e-6), dt(1)
     theta = np.sqrt(np.maximum(theta2, eps))
     wx, wy, wz = rx / (theta + eps), ry / (theta + eps), rz / (theta + eps)
-    c, s = np.cos(theta), np.sin(theta)
+    if wide_trig:
+        c, s = np.cos(theta.astype(np.float64)).astype(dt), np.sin(theta.astype(np.float64)).astype(dt)
+    else:
+        c, s = np.cos(theta), np.sin(theta)
     t = one - c
     normal = np.stack([c + wx * wx * t, wx * wy * t - wz * s, wy * s + wx * wz * t, wz * s + wx * wy * t, c + wy * wy * t, -wx * s + wy * wz * t,
                        -wy * s + wx * wz * t, wx * s + wy * wz * t, c + wz * wz * t], -1)

@@ -17,7 +17,7 @@ What turns the generator's kinematic pose into the imitation target of the low-l
 `attach_imitation_target(target)`, `pre_physics_step` ends with `post_mvae_step()`, the reset puts the humanoid into the generator's
 pose, and `physics_step(ll_actions)` steps the wrapped task on the PD targets of the low-level policy's actions: `pre_physics_step` ->
 `physics_step` -> `post_physics_step` is vid2player's control step.  Without one, every path is as before.  The dual controller is
-`tasks.tennis_controller_dual.DualTennisControllerTask`.  Not built: `optimize_two_hand_backhand`, `update_mvae_from_sim`.
+`tasks.tennis_controller_dual.DualTennisControllerTask`.  `optimize_two_hand_backhand` (single=True) is two_hand_fix.py.  Not built: `update_mvae_from_sim`.
 
 The low-level policy network is `vid2player3d_amd.policies.LowLevelPolicy` (two launches around the dense layers).  Attached with
 `attach_low_level_policy(policy)`, `physics_step()` takes no argument: the policy computes the imitation observation in place, runs its
@@ -49,7 +49,7 @@ the bounce of a returned ball, the recovery flag also rises on a slow ball), the
 `bounce_in_rate`, `bounce_in_pos_error` (:81-95) and the record the evaluation hands on (:140-146, `_joint_rot` of the simulated body
 included) - all in the step's ONE launch, `v2p_tennis_eval_step` (csrc/tennis_eval.hip), without a host read.  `select_best()` and
 `summary()` read them after the run; `eval_player.ControllerEvalPlayer` is the loop.  `eval_step_reference` / `eval_record_reference`
-state it in numpy.  Not built: rendering, video and HTML output, `fix_two_hand_backhand_post`, `vis_pd_target`, `MVAEControllerVisDual`,
+state it in numpy; `fixed_joint_rot(env_ids)` is cfg v2p `fix_two_hand_backhand_post` (two_hand_fix.py).  Not built: rendering, video and HTML output, `vis_pd_target`, `MVAEControllerVisDual`,
 the reference's frame 0 of the record (taken after the first reset, before any step).
 
 `task_step_reference` is a numpy statement of the same step on arrays - the checker of the tests, as `ball_traj.resample_reference`
@@ -1109,6 +1109,25 @@ class TennisControllerEval(TennisControllerTask):
         """The candidate env ids of mvae_controller_vis.py:149-156 (device tensor): envs with `bounce_in_rate.avg > 0.95` and
         `fh_ratio.avg < 0.6`, sorted by the distance their root travelled over the record, descending.  Torch, once, after the run."""
         return select_best(self.root_pos_all, self.bounce_in_rate.avg, self.fh_ratio.avg)
+
+    def fixed_joint_rot(self, env_ids, num_iters=None):
+        """`joint_rot_all[env_ids]` [T,f,24,3] with the two-hand backhand fix of `render_one_result` (mvae_controller_vis.py:181-190,
+        cfg v2p `fix_two_hand_backhand_post`) applied, for the envs `select_best()` names: one launch for all of them
+        (`two_hand_fix.fix_two_hand_backhand`, num_iters None: its 500), cfg v2p `righthand` (default True) for every env.  A new
+        tensor; the record stays as written."""
+        from .. import two_hand_fix as thf
+
+        target = self._imitation_target
+        if target is None:
+            raise RuntimeError("TennisControllerEval: the two-hand fix reads joint_pos_bind of the imitation target, and none is attached")
+        ids = torch.as_tensor(env_ids, device=self.device, dtype=torch.long).reshape(-1)
+        joint_rot = self.joint_rot_all[ids].contiguous()
+        T, f = joint_rot.shape[0], joint_rot.shape[1]
+        i32 = dict(dtype=torch.int32, device=self.device)
+        st = thf.fix_settings(self.task.body_names, self.task.body_model.parents)
+        bind = thf.bind_rows_of(target)
+        return thf.fix_two_hand_backhand(joint_rot, self.phase_all[ids].contiguous(), self.swing_type_all[ids].contiguous(), torch.full((T,), f, **i32),
+                                         torch.full((T,), int(bool(self.cfg_v2p.get("righthand", True))), **i32), bind, thf.NUM_ITERS if num_iters is None else num_iters, settings=st)
 
     def summary(self):
         """{meter: mean of its `avg` over the envs with count > 0 (NaN without one), meter + '_envs': their number} - how a controller is
